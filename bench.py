@@ -49,6 +49,8 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-rows", type=int, default=0, help="rows of the workload timed on the CPU oracle (0 = auto)")
     ap.add_argument("--also", default="q6_sf10,q6_sf1,q3_sf10,q1_sf10_decimal", help="extra workloads reported under 'also' (N>1: q1 weak, q6_sf10 and q3_sf10 sharded)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes the result rows of the main workload's last timed step to DIR/*.npy (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -472,6 +474,52 @@ def measure_q3_sharded(rt, tpch, abi, torch, dist, sf, rank, world):
             "note": "probe side sharded by chunk, build side replicated; max over ranks, host-timed median of 7, collectives included"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(abi, out_dir, rows):
+    """The finalized rows of one execution, as a caller of the path receives them, written as float64 .npy files:
+      key<k>.npy    [groups] the k-th group key (Utf8 keys: [groups, max bytes], the UTF-8 bytes padded with -1)
+      agg<a>.npy    [groups] the a-th aggregate (Decimal128: raw / 10**scale; NULL: NaN)
+      nulls.npy     [groups, keys + aggregates] 1.0 where the key / aggregate cell is NULL
+    Groups in the order the library hands them over.  Beyond DUMP_LIMIT_BYTES a fixed, seeded sample of the groups is
+    written (sample.npy: the group indices kept)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_keys = len(rows[0].keys) if rows else 0
+    n_aggs = len(rows[0].values) if rows else 0
+
+    def number(v):
+        if v.is_null:
+            return float("nan")
+        if isinstance(v.value, str):
+            raise TypeError("Utf8 cell in a numeric column")
+        return float(v.value) / 10 ** v.scale if v.dtype == abi.DT_DECIMAL128 else float(v.value)
+
+    widths = [max([len(r.keys[k].value.encode()) for r in rows if isinstance(r.keys[k].value, str)] or [0]) for k in range(n_keys)]
+    per_group = 8 * (sum(max(w, 1) for w in widths) + 2 * n_aggs + n_keys)
+    keep = np.arange(len(rows))
+    if per_group * len(rows) > DUMP_LIMIT_BYTES:
+        n = DUMP_LIMIT_BYTES // (per_group + 8)  # + its entry in sample.npy
+        keep = np.sort(np.random.default_rng(0).choice(len(rows), n, replace=False))
+        np.save(os.path.join(out_dir, "sample.npy"), keep.astype(np.float64))
+    picked = [rows[i] for i in keep]
+    for k in range(n_keys):
+        cells = [r.keys[k] for r in picked]
+        if widths[k]:
+            a = np.full((len(cells), widths[k]), -1.0)
+            for i, c in enumerate(cells):
+                if not c.is_null:
+                    b = c.value.encode()
+                    a[i, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+        else:
+            a = np.array([number(c) for c in cells], dtype=np.float64)
+        np.save(os.path.join(out_dir, f"key{k}.npy"), a)
+    for j in range(n_aggs):
+        np.save(os.path.join(out_dir, f"agg{j}.npy"), np.array([number(r.values[j]) for r in picked], dtype=np.float64))
+    np.save(os.path.join(out_dir, "nulls.npy"),
+            np.array([[float(c.is_null) for c in r.keys + r.values] for r in picked], dtype=np.float64).reshape(len(picked), n_keys + n_aggs))
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks with torch.distributed.run as a CHILD process
     (this process never touches the GPU — a process that has initialised it must not exec another program), relay
@@ -650,6 +698,9 @@ def main():
         st["host_to_hbm_gbs"] = st["copy_bytes"] / max(st["copy_seconds"], 1e-9) / 1e9
         st["rows_per_s_including_staging"] = main_res["total_rows"] / world / (st["wall_seconds"] + main_res["seconds"] / args.steps)
         out["staging"] = st
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(abi, args.dump_outputs, main_res["rows_result"] or [])
 
     # free the main workload's HBM image before staging the next one
     main_res.pop("prepared").close()

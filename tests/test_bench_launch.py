@@ -59,3 +59,47 @@ def test_a_rank_without_the_communicator_ends_every_rank_with_a_nonzero_code():
     assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert "rank 0: the library's RCCL communicator could not be created on another rank" in p.stderr
     assert "rank 1: the library's RCCL communicator could not be created (rehearsed failure)" in p.stderr
+
+
+def test_dump_outputs_writes_the_result_rows_as_float_arrays(tmp_path):
+    """`--dump-outputs DIR`: the finalized rows of the last timed step as float64 .npy files (keys, aggregates, a NULL mask);
+    beyond the size cap a seeded sample of the groups, the same one every time."""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    abi = importlib.import_module("rust-llkv_amd.abi")
+    V = abi.Value
+
+    class Row:
+        def __init__(self, keys, values):
+            self.keys, self.values = keys, values
+
+    rows = [Row([V(abi.DT_UTF8, False, "A"), V(abi.DT_INT64, False, 3)],
+                [V(abi.DT_FLOAT64, False, 1.5), V(abi.DT_INT64, False, 7), V(abi.DT_DECIMAL128, False, 12345, 15, 2), V(abi.DT_FLOAT64, True, None)]),
+            Row([V(abi.DT_UTF8, False, "NO"), V(abi.DT_INT64, True, None)],
+                [V(abi.DT_FLOAT64, False, -2.5), V(abi.DT_INT64, False, 8), V(abi.DT_DECIMAL128, False, -5, 15, 2), V(abi.DT_FLOAT64, False, 3.0)])]
+    out = tmp_path / "all"
+    bench.dump_outputs(abi, str(out), rows)
+    assert sorted(os.listdir(out)) == ["agg0.npy", "agg1.npy", "agg2.npy", "agg3.npy", "key0.npy", "key1.npy", "nulls.npy"]
+    load = lambda name: np.load(out / name)
+    assert all(load(n).dtype == np.float64 for n in os.listdir(out))
+    assert load("key0.npy").tolist() == [[65.0, -1.0], [78.0, 79.0]]
+    assert load("key1.npy")[0] == 3.0 and np.isnan(load("key1.npy")[1])
+    assert load("agg0.npy").tolist() == [1.5, -2.5] and load("agg1.npy").tolist() == [7.0, 8.0]
+    assert load("agg2.npy").tolist() == [123.45, -0.05]
+    assert np.isnan(load("agg3.npy")[0]) and load("agg3.npy")[1] == 3.0
+    assert load("nulls.npy").tolist() == [[0, 0, 0, 0, 0, 1], [0, 1, 0, 0, 0, 0]]
+
+    many = [rows[i % 2] for i in range(1000)]
+    limit, bench.DUMP_LIMIT_BYTES = bench.DUMP_LIMIT_BYTES, 10_000
+    try:
+        a, b = tmp_path / "a", tmp_path / "b"
+        bench.dump_outputs(abi, str(a), many)
+        bench.dump_outputs(abi, str(b), many)
+    finally:
+        bench.DUMP_LIMIT_BYTES = limit
+    assert sum(os.path.getsize(a / n) for n in os.listdir(a)) < 10_000 + 128 * len(os.listdir(a))  # + the .npy headers
+    kept = np.load(a / "sample.npy")
+    assert 0 < len(kept) < 1000 and kept.tolist() == np.load(b / "sample.npy").tolist()
+    assert np.load(a / "agg0.npy").tolist() == [many[int(i)].values[0].value for i in kept]
