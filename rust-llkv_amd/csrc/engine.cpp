@@ -256,7 +256,7 @@ int prepare_query(const Table *table, const llkv_filter *filters, uint32_t n_fil
   for (size_t i = 0; i < p.lit_i.size(); ++i) q->params.lit_i[i] = p.lit_i[i];
   for (size_t i = 0; i < p.lit_f.size(); ++i) q->params.lit_f[i] = p.lit_f[i];
   for (size_t i = 0; i < p.key_strides.size(); ++i) q->params.key_stride[i] = p.key_strides[i];
-  q->params.tiles = ts->d_tiles;
+  q->params.tiles = ts->d_tiles.get<TileDesc>();
   q->params.n_tiles = ts->n_tiles;
   q->params.scan_grid = pick_scan_grid(p, ts->n_tiles);
 
@@ -605,7 +605,7 @@ int Query::emit_values(const LoweredPlan &ep, Scratch *vals, uint64_t *n_out) {
   for (size_t i = 0; i < ep.slot_fields.size(); ++i) sp.col[i] = slot_buffer(table->cols, ep, i);
   for (size_t i = 0; i < ep.lit_i.size(); ++i) sp.lit_i[i] = ep.lit_i[i];
   for (size_t i = 0; i < ep.lit_f.size(); ++i) sp.lit_f[i] = ep.lit_f[i];
-  sp.tiles = ts->d_tiles;
+  sp.tiles = ts->d_tiles.get<TileDesc>();
   sp.n_tiles = ts->n_tiles;
   sp.sub_rows = 8192 / (kBlock / 64);
   sp.tile_partials = counts.as<uint64_t>();

@@ -41,21 +41,50 @@ struct Context {
 extern Context g_ctx;
 int ensure_device();
 
+// Device memory a Table owns (hipMalloc, outside the scratch cache: it lives as long as the table): move-only, freed with its
+// owner.  cap_rows() = the rows it can hold (slack included); an append (llkv_hip_table_append_chunks) that outgrows it moves the
+// image into a larger buffer.
+class DeviceBuffer {
+ public:
+  DeviceBuffer() = default;
+  DeviceBuffer(DeviceBuffer &&o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_rows_(std::exchange(o.cap_rows_, 0)) {}
+  DeviceBuffer &operator=(DeviceBuffer &&o) noexcept {
+    if (this != &o) { reset(); p_ = std::exchange(o.p_, nullptr); cap_rows_ = std::exchange(o.cap_rows_, 0); }
+    return *this;
+  }
+  ~DeviceBuffer() { reset(); }
+  hipError_t alloc(uint64_t rows, size_t row_bytes) {
+    reset();
+    const hipError_t e = hipMalloc(&p_, rows * row_bytes);
+    if (e == hipSuccess) cap_rows_ = rows;
+    else p_ = nullptr;
+    return e;
+  }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+    cap_rows_ = 0;
+  }
+  template <class T = void> T *get() const { return static_cast<T *>(p_); }
+  uint64_t cap_rows() const { return cap_rows_; }
+  explicit operator bool() const { return p_ != nullptr; }
+
+ private:
+  void *p_ = nullptr;
+  uint64_t cap_rows_ = 0;
+};
+
 struct DeviceColumn {
   ColumnInfo info;
-  void *d_values = nullptr;
+  DeviceBuffer d_values;
   bool has_local_stats = false; // min / max of this rank's rows (info.has_stats / min_i / max_i are table-wide)
   int64_t local_min = 0, local_max = 0;
   bool has_local_fstats = false; // float columns: largest finite |v| of this rank's rows (info.has_fstats / f_absmax are table-wide)
   double local_f_absmax = 0.0, local_f_absmin_nz = 0.0;
   bool local_f_all_finite = false; // … and none of this rank's values is NaN / ±∞
   bool local_f_no_neg_zero = false; // … nor −0.0
-  uint8_t *d_valid = nullptr; // 1 B/row validity mask (info.nullable), same row layout as d_values
-  void *d_hi = nullptr;       // Decimal128 values beyond 64 bits (info.wide128): d_values holds the low halves, this the high halves
-  bool owned = false;
-  // rows the buffers above can hold (slack included); 0 = exactly the table's image + slack as allocated at staging.  An append
-  // (llkv_hip_table_append_chunks) that outgrows it moves the column into a larger buffer with headroom.
-  uint64_t cap_rows = 0, valid_cap_rows = 0;
+  DeviceBuffer d_valid; // uint8_t: 1 B/row validity mask (info.nullable), same row layout as d_values
+  DeviceBuffer d_hi;    // Decimal128 values beyond 64 bits (info.wide128): d_values holds the low halves, this the high halves
 };
 
 // Device buffer read by slot `s` of a lowered plan: the field's values, its validity mask, or the high halves of a wide
@@ -63,15 +92,15 @@ struct DeviceColumn {
 inline const void *slot_buffer(const std::map<uint32_t, DeviceColumn> &cols, const LoweredPlan &p, size_t s) {
   const DeviceColumn &c = cols.at(p.slot_fields[s]);
   const uint8_t part = s < p.slot_is_valid.size() ? p.slot_is_valid[s] : 0;
-  return part == 1 ? (const void *)c.d_valid : part == 2 ? (const void *)c.d_hi : (const void *)c.d_values;
+  return part == 1 ? c.d_valid.get() : part == 2 ? c.d_hi.get() : c.d_values.get();
 }
 
 struct TileSet {
-  TileDesc *d_tiles = nullptr;
+  DeviceBuffer d_tiles; // TileDesc
   uint32_t n_tiles = 0;
   uint32_t tile_rows = 0;
   // every kTileSampleStride-th tile, for selectivity estimates (stream.cpp: run_selection_lowered)
-  TileDesc *d_sample = nullptr;
+  DeviceBuffer d_sample; // TileDesc
   uint32_t n_sample = 0;
   uint64_t sample_rows = 0;
   uint32_t octant_tile_begin[kOctantsHost + 1] = {0};
@@ -82,7 +111,7 @@ struct TileSet {
 // order-bits scan's.  Built on first use (one pass: 8 B in, 4 B out per row), kept with the table, same row layout; an append
 // (a new generation) drops it.  Sparse lookups (an owner's key, a payload) stay on the column itself.
 struct KeyImage {
-  void *d = nullptr;
+  DeviceBuffer d;
   ColumnInfo info; // the column's, with dtype = Int32
 };
 
@@ -100,16 +129,14 @@ struct Table {
   std::map<uint32_t, TileSet> tilesets;
   std::map<uint32_t, KeyImage> key_images;
   // Row ids that are not the positions 0 … n − 1 (llkv_hip_table_set_row_ids): the id of every local row, in the row layout of
-  // the column images; nullptr = dense ids.  Everything inside works on positions; the calls that REPORT row ids translate.
-  uint64_t *d_row_ids = nullptr;
-  uint64_t row_ids_cap = 0;   // rows d_row_ids can hold
+  // the column images; empty = dense ids.  Everything inside works on positions; the calls that REPORT row ids translate.
+  DeviceBuffer d_row_ids; // uint64_t
   uint64_t last_row_id = 0;   // the id of the table's last row (ids ascend strictly; appended chunks must continue above it)
   // llkv_hip_table_append_chunks: every append is a new generation of the image — buffers may have moved, statistics and tile
   // lists have changed — and a query prepared over an older one refuses to launch (prepare it again: lowering + a cache lookup)
   uint64_t generation = 0;
-  std::vector<void *> retired; // tile lists of older generations (freed with the table: a stale handle may still name them)
+  std::vector<DeviceBuffer> retired; // tile lists of older generations (freed with the table: a stale handle may still name them)
   std::mutex mu;
-  ~Table();
 };
 
 void compute_layout(Table &t);
@@ -304,12 +331,17 @@ bool scratch_can_hold(size_t bytes); // whether scratch_alloc(bytes) could succe
 void scratch_release_all();
 struct Scratch { // RAII temporary
   void *p = nullptr;
+  size_t cap = 0;
+  Scratch() = default;
+  Scratch(Scratch &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
   ~Scratch() { if (p) scratch_free(p); }
   int alloc(size_t bytes) {
     if (p) scratch_free(p);
     p = scratch_alloc(bytes);
+    cap = p ? bytes : 0;
     return p ? LLKV_OK : set_error(LLKV_INTERNAL, "device scratch allocation of " + std::to_string(bytes) + " bytes failed");
   }
+  int ensure(size_t bytes) { return p && bytes <= cap ? LLKV_OK : alloc(bytes ? bytes : 8); } // grow-only
   template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
@@ -334,6 +366,27 @@ void *pinned_acquire(size_t *bytes);
 void pinned_release(void *p, size_t bytes);
 void pinned_release_all();
 void pinned_stats(uint64_t *cached, uint64_t *outstanding); // bytes in the cache / handed out and not yet released
+// A block of that cache, returned to it by the destructor: pinning memory costs far more than a selective scan (hundreds
+// of µs per buffer).  `bytes` = the block's size class.
+struct PinnedBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+  ~PinnedBuf() { if (p) pinned_release(p, bytes); }
+  int alloc(size_t n) {
+    if (p) pinned_release(p, bytes);
+    bytes = n ? n : 8;
+    p = pinned_acquire(&bytes);
+    if (p) return LLKV_OK;
+    bytes = 0;
+    return set_error(LLKV_INTERNAL, "pinned host allocation of " + std::to_string(n ? n : 8) + " bytes failed");
+  }
+  int ensure(size_t n) { return n <= bytes ? LLKV_OK : alloc(n); } // grow-only
+};
+// Grow-only pinned host buffer outside the cache (hipHostMalloc, 25 % + 64 B headroom; *p / *cap are the caller's, who frees
+// *p with hipHostFree).
+int pinned_reserve(void **p, size_t *cap, size_t bytes);
 
 // Result buffers of llkv_hip_free-able arrays: pinned (recycled) blocks for large ones; result_release returns false
 // for a pointer it did not hand out (a plain malloc).

@@ -81,18 +81,6 @@ uint32_t part_block_threads() {
 void part_groupby_free(PartGroupBy *p) { delete p; }
 const LoweredPlan *part_groupby_plan(const PartGroupBy *p) { return &p->plan; }
 
-namespace {
-int pinned_reserve(void **p, size_t *cap, size_t bytes) {
-  if (bytes <= *cap) return LLKV_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(hipHostMalloc(p, bytes + bytes / 4 + 64, hipHostMallocDefault));
-  *cap = bytes + bytes / 4 + 64;
-  return LLKV_OK;
-}
-} // namespace
-
 // Admission: what the shared-image lowering takes (statistics-bounded keys, order-free lanes) with up to 2^24 dense
 // groups; in first-appearance order or in key order.  Over a sharded table every rank reduces its own rows and the
 // partial groups are merged like the sort-based route's (sorted_groupby_merge: the lanes are order-free, lane 1 is a
@@ -227,7 +215,7 @@ int PartGroupBy::run(LazyGroups *out) {
   for (size_t i = 0; i < p.lit_f.size(); ++i) sp.lit_f[i] = p.lit_f[i];
   for (size_t i = 0; i < p.key_strides.size(); ++i) sp.key_stride[i] = p.key_strides[i];
   sp.dict_num = d_dict_num;
-  sp.tiles = ts->d_tiles;
+  sp.tiles = ts->d_tiles.get<TileDesc>();
   sp.n_tiles = n_tiles;
   sp.part_hist = cell_table.as<uint32_t>();
   sp.part_val = rec_val.as<uint64_t>();
@@ -281,7 +269,7 @@ int PartGroupBy::run(LazyGroups *out) {
     }
     if ((rc = tmp2.alloc(tb_max))) return rc;
     for (uint32_t c = 0; c < n_ranges; ++c) {
-      HIP_TRY(launch_part_reduce(cell_table.as<uint32_t>(), rec_val.as<uint64_t>(), ts->d_tiles, group_rows.as<uint64_t>(), d_lane_tables, d_lane_tables + kl,
+      HIP_TRY(launch_part_reduce(cell_table.as<uint32_t>(), rec_val.as<uint64_t>(), ts->d_tiles.get<TileDesc>(), group_rows.as<uint64_t>(), d_lane_tables, d_lane_tables + kl,
                                  d_lane_tables + kl + k, n_tiles, np, ngs, ng, kl, k, s, part_at[c], part_at[c + 1] - part_at[c]));
       if (group_at[c + 1] > group_at[c]) { // ids relative to the range's first group
         size_t tb = tb_max;
@@ -312,7 +300,7 @@ int PartGroupBy::run(LazyGroups *out) {
     mark("reduce + copy out");
     if (n_groups == 0) return LLKV_OK;
   } else {
-  HIP_TRY(launch_part_reduce(cell_table.as<uint32_t>(), rec_val.as<uint64_t>(), ts->d_tiles, group_rows.as<uint64_t>(), d_lane_tables, d_lane_tables + kl,
+  HIP_TRY(launch_part_reduce(cell_table.as<uint32_t>(), rec_val.as<uint64_t>(), ts->d_tiles.get<TileDesc>(), group_rows.as<uint64_t>(), d_lane_tables, d_lane_tables + kl,
                              d_lane_tables + kl + k, n_tiles, np, ngs, ng, kl, k, s, 0, np));
   mark("partition reduce");
   // ---- the groups that have rows, in first-appearance order --------------------------------------------------------

@@ -162,18 +162,6 @@ int sorted_groupby_merge(SortedGroupBy *s, uint32_t world, const uint64_t *rank_
   return LLKV_OK;
 }
 
-namespace {
-int pinned_reserve(void **p, size_t *cap, size_t bytes) {
-  if (bytes <= *cap) return LLKV_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(hipHostMalloc(p, bytes + bytes / 4 + 64, hipHostMallocDefault));
-  *cap = bytes + bytes / 4 + 64;
-  return LLKV_OK;
-}
-} // namespace
-
 // Admission: GROUP BY shapes the dense kernel turned down for capacity reasons only.
 int sorted_groupby_prepare(const Table *table, const llkv_filter *filters, uint32_t n_filters, const llkv_eval_op *ops, uint32_t n_ops,
                            const uint32_t *key_fields, uint32_t n_keys, const llkv_aggregate_spec *aggs, uint32_t n_aggs,
@@ -224,8 +212,8 @@ namespace {
 int key_column_of(const Table *t, uint32_t field, JoinKeyColumn *kc, long long *base, uint32_t *bits) {
   const DeviceColumn &c = t->cols.at(field);
   std::memset(kc, 0, sizeof *kc);
-  kc->values = c.d_values;
-  kc->valid = c.info.nullable ? c.d_valid : nullptr;
+  kc->values = c.d_values.get();
+  kc->valid = c.info.nullable ? c.d_valid.get<uint8_t>() : nullptr;
   *bits = 64;
   switch (c.info.dtype) {
   case LLKV_DT_INT64: kc->width = 8; kc->is_signed = 1; *base = INT64_MIN; break;
@@ -324,8 +312,8 @@ int SortedGroupBy::run(LazyGroups *out) {
     drows = diota.as<uint64_t>();
   } else if (has_distinct) {
     const DeviceColumn &dc = table->cols.at((uint32_t)red_plan.distinct_field);
-    dcol.values = dc.d_values;
-    dcol.valid = dc.info.nullable ? dc.d_valid : nullptr;
+    dcol.values = dc.d_values.get();
+    dcol.valid = dc.info.nullable ? dc.d_valid.get<uint8_t>() : nullptr;
     dcol.width = dc.info.dtype == LLKV_DT_DATE32 ? 4 : (dc.info.dtype == LLKV_DT_INT64 || dc.info.dtype == LLKV_DT_FLOAT64 || dc.info.dtype == LLKV_DT_DECIMAL128) ? 8 : 1; // (the 64-bit image of a decimal; dictionary codes and Booleans: a byte)
     dcol.is_signed = dc.info.dtype == LLKV_DT_DATE32; // otherwise only equality matters: the cell's pattern (Float64: "by bit pattern", llkv-aggregate/src/lib.rs:252-331)
   }

@@ -15,33 +15,6 @@
 namespace llkv {
 
 namespace {
-struct DBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  ~DBuf() { scratch_free(p); }
-  int ensure(size_t bytes) {
-    if (bytes <= cap && p) return LLKV_OK;
-    scratch_free(p);
-    p = scratch_alloc(bytes ? bytes : 8);
-    if (!p) return set_error(LLKV_INTERNAL, "device scratch allocation failed");
-    cap = bytes;
-    return LLKV_OK;
-  }
-};
-struct HBuf { // pinned, recycled (engine.cpp: pinned_acquire)
-  void *p = nullptr;
-  size_t cap = 0;
-  ~HBuf() { if (p) pinned_release(p, cap); }
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return LLKV_OK;
-    if (p) pinned_release(p, cap);
-    cap = bytes ? bytes : 8;
-    p = pinned_acquire(&cap);
-    if (!p) { cap = 0; return set_error(LLKV_INTERNAL, "pinned host allocation failed"); }
-    return LLKV_OK;
-  }
-};
-
 constexpr uint32_t kJoinTileRows = 8192;
 // probe rows per device step: 32 reference scan batches.  (One batch per step — 8 workgroups, two synchronisations,
 // three small copies — ran at 0.13 G probe rows/s.)
@@ -58,8 +31,8 @@ int key_part(const Table *t, uint32_t field, const DeviceColumn **col, JoinKeyPa
   if (c.info.wide128) return set_error(LLKV_UNSUPPORTED, "join key over Decimal128 values beyond 64 bits (field " + std::to_string(field) + ")");
   *col = &c;
   std::memset(out, 0, sizeof *out);
-  out->values = c.d_values;
-  out->valid = c.info.nullable ? c.d_valid : nullptr;
+  out->values = c.d_values.get();
+  out->valid = c.info.nullable ? c.d_valid.get<uint8_t>() : nullptr;
   out->width = c.info.dtype == LLKV_DT_UTF8 ? 1u : dtype_width(c.info.dtype);
   out->is_signed = c.info.dtype == LLKV_DT_INT32 ? 1u : 0u;
   return LLKV_OK;
@@ -81,9 +54,9 @@ struct JoinPlan {
   uint64_t batch_size = 8192;
   int jt = LLKV_JOIN_INNER;
   JoinKeySet lk, rk;
-  DBuf translate;
+  Scratch translate;
   uint64_t n_build = 0, cap = 0;
-  DBuf owner, slot_of, dev_of, log_of, seg_start, seg_count, idx_in, slot_sorted, idx_sorted, tile_base, tmp;
+  Scratch owner, slot_of, dev_of, log_of, seg_start, seg_count, idx_in, slot_sorted, idx_sorted, tile_base, tmp;
   const TileSet *tr = nullptr, *tl = nullptr;
   JoinPlan() { std::memset(&lk, 0, sizeof lk); std::memset(&rk, 0, sizeof rk); }
 };
@@ -115,7 +88,7 @@ static int join_key_setup(const Table *left, const Table *right, const llkv_join
   if (n_keys > kMaxJoinKeys) return set_error(LLKV_UNSUPPORTED, "GPU join path takes at most " + std::to_string(kMaxJoinKeys) + " key pairs");
   if (!keys) return set_error(LLKV_INVALID_ARGUMENT, "join keys is NULL");
   JoinKeySet &lk = jp->lk, &rk = jp->rk;
-  DBuf &translate = jp->translate;
+  Scratch &translate = jp->translate;
   lk.n = rk.n = n_keys;
   const DeviceColumn *lc[kMaxJoinKeys], *rc_[kMaxJoinKeys];
   for (uint32_t i = 0; i < n_keys; ++i)
@@ -230,7 +203,7 @@ static int join_build(const Table *left, const Table *right, JoinPlan *jp, hipSt
   uint32_t bits = 10;
   while (cap < 2 * n_build) { cap <<= 1; ++bits; }
   jp->cap = cap;
-  DBuf &owner = jp->owner, &slot_of = jp->slot_of, &dev_of = jp->dev_of, &log_of = jp->log_of, &seg_start = jp->seg_start, &seg_count = jp->seg_count,
+  Scratch &owner = jp->owner, &slot_of = jp->slot_of, &dev_of = jp->dev_of, &log_of = jp->log_of, &seg_start = jp->seg_start, &seg_count = jp->seg_count,
        &idx_in = jp->idx_in, &slot_sorted = jp->slot_sorted, &idx_sorted = jp->idx_sorted, &tile_base = jp->tile_base, &tmp = jp->tmp;
   if ((rc = owner.ensure(cap * 8)) || (rc = seg_start.ensure((cap + 1) * 4)) || (rc = seg_count.ensure((cap + 1) * 4)) ||
       (rc = slot_of.ensure(n_build * 4)) || (rc = dev_of.ensure(n_build * 8)) || (rc = log_of.ensure(n_build * 8)) ||
@@ -247,7 +220,7 @@ static int join_build(const Table *left, const Table *right, JoinPlan *jp, hipSt
     for (size_t i = 0; i < tiles.size(); ++i) base[i + 1] = base[i] + tiles[i].rows;
     HIP_TRY(hipMemcpyAsync(tile_base.p, base.data(), base.size() * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s)); // `base` is pageable host memory
-    HIP_TRY(hj_launch_claim(jp->rk, tr->d_tiles, tr->n_tiles, kJoinTileRows, (unsigned long long *)owner.p, cap - 1, (uint32_t *)slot_of.p,
+    HIP_TRY(hj_launch_claim(jp->rk, tr->d_tiles.get<TileDesc>(), tr->n_tiles, kJoinTileRows, (unsigned long long *)owner.p, cap - 1, (uint32_t *)slot_of.p,
                             (uint64_t *)dev_of.p, (uint64_t *)log_of.p, (const uint64_t *)tile_base.p, s));
     HIP_TRY(hj_launch_iota((uint32_t *)idx_in.p, (uint32_t)n_build, s));
     size_t tmp_bytes = 0;
@@ -284,8 +257,8 @@ int run_join(const Table *left, const Table *right, const llkv_join_key *keys, u
     if (nr == 0 && jt == LLKV_JOIN_INNER) return LLKV_OK;
     constexpr uint64_t kWin = 65536;
     hipStream_t s = g_ctx.stream;
-    DBuf d_l, d_r;
-    HBuf h_l, h_r;
+    Scratch d_l, d_r;
+    PinnedBuf h_l, h_r;
     for (uint64_t l0 = 0; l0 < nl; l0 += kWin) {
       const uint64_t ln = std::min(kWin, nl - l0);
       if (nr == 0) { // LEFT: NULL-padded right side (synthesize_left_join_nulls)
@@ -327,12 +300,12 @@ int run_join(const Table *left, const Table *right, const llkv_join_key *keys, u
   if ((rc = join_build(left, right, &jp, s))) return rc;
   const TileSet *tl = jp.tl;
   const uint64_t n_build = jp.n_build, cap = jp.cap;
-  DBuf &owner = jp.owner, &log_of = jp.log_of, &seg_start = jp.seg_start, &seg_count = jp.seg_count, &idx_sorted = jp.idx_sorted;
+  Scratch &owner = jp.owner, &log_of = jp.log_of, &seg_start = jp.seg_start, &seg_count = jp.seg_count, &idx_sorted = jp.idx_sorted;
 
   if (trace) { (void)hipStreamSynchronize(s); std::fprintf(stderr, "[llkv join] build %9.3f ms (%llu rows)\n", lap(), (unsigned long long)n_build); }
   // ---- probe (left), window by window ----
   const uint32_t win_pos = std::min(kWindowTiles, std::max(1u, tl->n_tiles)) * kJoinTileRows;
-  DBuf counts, mslot, offsets, scan_tmp;
+  Scratch counts, mslot, offsets, scan_tmp;
   if ((rc = counts.ensure((size_t)(win_pos + 1) * 8)) || (rc = mslot.ensure((size_t)win_pos * 4)) || (rc = offsets.ensure((size_t)(win_pos + 1) * 8))) return rc;
   const bool left_only = jp.left_only;
   // Batches.  The reference probes one scan batch (65 536 rows of the left table) at a time and flushes after the
@@ -353,8 +326,8 @@ int run_join(const Table *left, const Table *right, const llkv_join_key *keys, u
   // Two pair buffers: while the pairs of step i cross PCIe on the copy stream and the host cuts step i − 1 into
   // batches, the compute stream already counts step i + 1.
   struct Step {
-    DBuf out_l, out_r;
-    HBuf h_l, h_r;
+    Scratch out_l, out_r;
+    PinnedBuf h_l, h_r;
     hipEvent_t written = nullptr, copied = nullptr;
     uint64_t total = 0, L0 = 0, L1 = 0;
     bool live = false;
@@ -428,7 +401,7 @@ int run_join(const Table *left, const Table *right, const llkv_join_key *keys, u
     ProbeParams p;
     std::memset(&p, 0, sizeof p);
     p.lkey = lk; p.rkey = rk;
-    p.tiles = tl->d_tiles + t0; p.n_tiles = nt; p.tile_rows = kJoinTileRows;
+    p.tiles = tl->d_tiles.get<TileDesc>() + t0; p.n_tiles = nt; p.tile_rows = kJoinTileRows;
     p.slot_owner = (const unsigned long long *)owner.p; p.cap_mask = cap - 1;
     p.seg_start = (const uint32_t *)seg_start.p; p.seg_count = (const uint32_t *)seg_count.p;
     p.sorted_idx = (const uint32_t *)idx_sorted.p; p.build_logical = (const uint64_t *)log_of.p;
@@ -558,7 +531,7 @@ struct SideOut {
 };
 
 // live[dev row] of a side whose user columns all have NULL cells (else no row can be dropped: *live stays empty)
-int side_live_mask(const SideOut &so, DBuf *live, uint64_t *dead, hipStream_t s, bool *synthetic) {
+int side_live_mask(const SideOut &so, Scratch *live, uint64_t *dead, hipStream_t s, bool *synthetic) {
   *dead = 0;
   *synthetic = false;
   if (!so.all_nullable || so.n() == 0 || so.t->local_rows == 0) return LLKV_OK;
@@ -568,11 +541,11 @@ int side_live_mask(const SideOut &so, DBuf *live, uint64_t *dead, hipStream_t s,
   if (rc) return rc;
   LiveMaskCols lc;
   std::memset(&lc, 0, sizeof lc);
-  for (uint32_t f : so.fields) lc.valid[lc.n++] = so.t->cols.at(f).d_valid;
-  DBuf d_dead;
+  for (uint32_t f : so.fields) lc.valid[lc.n++] = so.t->cols.at(f).d_valid.get<uint8_t>();
+  Scratch d_dead;
   if ((rc = live->ensure(so.t->dev_rows + 8)) || (rc = d_dead.ensure(8))) return rc;
   HIP_TRY(hipMemsetAsync(d_dead.p, 0, 8, s));
-  HIP_TRY(hj_launch_live_mask(lc, ts->d_tiles, ts->n_tiles, (uint8_t *)live->p, (unsigned long long *)d_dead.p, s));
+  HIP_TRY(hj_launch_live_mask(lc, ts->d_tiles.get<TileDesc>(), ts->n_tiles, (uint8_t *)live->p, (unsigned long long *)d_dead.p, s));
   Readback rb;
   if ((rc = rb.add(dead, d_dead.p, 8, s)) || (rc = rb.wait())) return rc;
   // a table whose every row is dropped comes out of the reference's scan as ONE synthetic batch of total_rows NULL rows
@@ -588,8 +561,8 @@ int side_live_mask(const SideOut &so, DBuf *live, uint64_t *dead, hipStream_t s,
 
 // Output buffers of one device step and what the host needs to hand its batches out
 struct OutStep {
-  std::vector<DBuf> d, d_valid;
-  std::vector<HBuf> h, h_valid;
+  std::vector<Scratch> d, d_valid;
+  std::vector<PinnedBuf> h, h_valid;
   hipEvent_t written = nullptr, copied = nullptr;
   bool live = false;
   uint64_t carry_in = 0;              // rows of the running batch that earlier steps hold (the device saw the same number)
@@ -613,7 +586,7 @@ struct JoinEmitter {
   void *user = nullptr;
   OutStep steps[2];
   hipStream_t copy_stream = nullptr;
-  DBuf d_err;
+  Scratch d_err;
   // rows of a batch that began in an earlier step
   uint64_t pend_rows = 0;
   std::vector<std::vector<uint8_t>> pend_vals;
@@ -850,7 +823,7 @@ int run_join_batches(const Table *left, const Table *right, const llkv_join_key 
     if ((rc = windows(lsel, &lw)) || (rc = windows(rsel, &rw))) return rc;
     if (l_one) lw = {0, lsel.n};
     if (r_one) rw = {0, rsel.n};
-    DBuf d_l, d_r;
+    Scratch d_l, d_r;
     int cur = 0;
     for (size_t li = 0; li + 1 < lw.size(); ++li) {
       const uint64_t ln = lw[li + 1] - lw[li];
@@ -887,7 +860,7 @@ int run_join_batches(const Table *left, const Table *right, const llkv_join_key 
   // no left columns: the reference scans nothing (hash_join.rs:226)
   if (em.L.n() == 0) return LLKV_OK;
   // rows the two scans drop (NULL in every user column); the executor's join reads its tables with their NULL rows
-  DBuf l_live, r_live;
+  Scratch l_live, r_live;
   uint64_t l_dead = 0, r_dead = 0;
   bool l_synthetic = false, r_synthetic = false; // (the build side's batches do not show in a hash join's output)
   if (!jp.executor && ((rc = side_live_mask(em.L, &l_live, &l_dead, s, &l_synthetic)) || (rc = side_live_mask(em.R, &r_live, &r_dead, s, &r_synthetic)))) return rc;
@@ -912,8 +885,8 @@ int run_join_batches(const Table *left, const Table *right, const llkv_join_key 
   }
 
   const uint32_t win_pos = std::min(kWindowTiles, std::max(1u, tl->n_tiles)) * kJoinTileRows;
-  DBuf counts, mslot, offsets, scan_tmp, seg_pos_d, seg_cuts, seg_base, cuts_d, carry_d, shift_d, d_lrows, d_rrows;
-  HBuf seg_pos_h, cuts_h, shift_h;
+  Scratch counts, mslot, offsets, scan_tmp, seg_pos_d, seg_cuts, seg_base, cuts_d, carry_d, shift_d, d_lrows, d_rrows;
+  PinnedBuf seg_pos_h, cuts_h, shift_h;
   if ((rc = counts.ensure((size_t)(win_pos + 1) * 8)) || (rc = mslot.ensure((size_t)win_pos * 4)) || (rc = offsets.ensure((size_t)(win_pos + 1) * 8)) || (rc = carry_d.ensure(8))) return rc;
   std::vector<TileDesc> ltiles;
   {
@@ -932,7 +905,7 @@ int run_join_batches(const Table *left, const Table *right, const llkv_join_key 
     ProbeParams p;
     std::memset(&p, 0, sizeof p);
     p.lkey = jp.lk; p.rkey = jp.rk;
-    p.tiles = tl->d_tiles + t0; p.n_tiles = nt; p.tile_rows = kJoinTileRows;
+    p.tiles = tl->d_tiles.get<TileDesc>() + t0; p.n_tiles = nt; p.tile_rows = kJoinTileRows;
     p.slot_owner = (const unsigned long long *)jp.owner.p; p.cap_mask = jp.cap - 1;
     p.seg_start = (const uint32_t *)jp.seg_start.p; p.seg_count = (const uint32_t *)jp.seg_count.p;
     p.sorted_idx = (const uint32_t *)jp.idx_sorted.p; p.build_logical = (const uint64_t *)jp.log_of.p;

@@ -34,7 +34,7 @@ int int_key_column(const Table *t, uint32_t field, JoinKeyColumn *out) {
   auto it = t->cols.find(field);
   if (it == t->cols.end()) return set_error(LLKV_NOT_FOUND, "field " + std::to_string(field) + " not found");
   if (it->second.info.nullable) return set_error(LLKV_UNSUPPORTED, "key column with NULL cells in the join-aggregate pipeline");
-  out->values = it->second.d_values;
+  out->values = it->second.d_values.get();
   switch (it->second.info.dtype) {
   case LLKV_DT_INT64: case LLKV_DT_UINT64: out->width = 8; out->is_signed = 1; return LLKV_OK;
   case LLKV_DT_INT32: case LLKV_DT_DATE32: out->width = 4; out->is_signed = 1; return LLKV_OK;
@@ -238,7 +238,7 @@ struct ImageBinds {
   }
   const void *buffer(const LoweredPlan &lp, size_t slot) const {
     const uint8_t part = slot < lp.slot_is_valid.size() ? lp.slot_is_valid[slot] : 0;
-    if (part == 0) for (const auto &b : of) if (b.first == lp.slot_fields[slot]) return b.second->d;
+    if (part == 0) for (const auto &b : of) if (b.first == lp.slot_fields[slot]) return b.second->d.get();
     return slot_buffer(t->cols, lp, slot);
   }
   int add(uint32_t field, const llkv_filter *f, uint32_t nf, const llkv_expr_token *e = nullptr, uint32_t ne = 0) {
@@ -372,7 +372,7 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
         for (size_t i = 0; i < kp2.slot_fields.size(); ++i) p2.col[i] = slot_buffer(t2->cols, kp2, i);
         for (size_t i = 0; i < kp2.lit_i.size(); ++i) p2.lit_i[i] = kp2.lit_i[i];
         for (size_t i = 0; i < kp2.lit_f.size(); ++i) p2.lit_f[i] = kp2.lit_f[i];
-        p2.tiles = ts2->d_tiles;
+        p2.tiles = ts2->d_tiles.get<TileDesc>();
         p2.n_tiles = ts2->n_tiles;
         p2.aux_out = (uint64_t *)set2_bits.bits.p;
         p2.aux_out32 = set2_bits.flag_p + 1; // predicate-error word (read with the pair count)
@@ -411,7 +411,7 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
       for (size_t i = 0; i < kp.slot_fields.size(); ++i) pd.col[i] = img_d.buffer(kp, i);
       for (size_t i = 0; i < kp.lit_i.size(); ++i) pd.lit_i[i] = kp.lit_i[i];
       for (size_t i = 0; i < kp.lit_f.size(); ++i) pd.lit_f[i] = kp.lit_f[i];
-      pd.tiles = tsd->d_tiles;
+      pd.tiles = tsd->d_tiles.get<TileDesc>();
       pd.n_tiles = tsd->n_tiles;
       pd.aux_out = (uint64_t *)dt.bits.p;
       pd.aux_out32 = dt.flag_p + 1; // predicate-error word
@@ -560,7 +560,7 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
   for (size_t i = 0; i < plan.slot_fields.size(); ++i) p.col[i] = img_f.buffer(plan, i);
   for (size_t i = 0; i < plan.lit_i.size(); ++i) p.lit_i[i] = plan.lit_i[i];
   for (size_t i = 0; i < plan.lit_f.size(); ++i) p.lit_f[i] = plan.lit_f[i];
-  p.tiles = ts->d_tiles;
+  p.tiles = ts->d_tiles.get<TileDesc>();
   p.n_tiles = ts->n_tiles;
   p.sub_rows = probe_tile / (kBlock / 64);
   p.tile_partials = (uint64_t *)counts.p;

@@ -37,8 +37,8 @@ int key_col_of(const Table *t, uint32_t field, JoinKeyColumn *out, const ColumnI
   const ColumnInfo &ci = it->second.info;
   if (ci.nullable && !allow_null) return set_error(LLKV_UNSUPPORTED, "join key column with NULL cells in the join → GROUP BY pipeline");
   std::memset(out, 0, sizeof *out);
-  out->values = it->second.d_values;
-  out->valid = ci.nullable ? it->second.d_valid : nullptr;
+  out->values = it->second.d_values.get();
+  out->valid = ci.nullable ? it->second.d_valid.get<uint8_t>() : nullptr;
   switch (ci.dtype) {
   case LLKV_DT_INT64: out->width = 8; out->is_signed = 1; break;
   case LLKV_DT_INT32: case LLKV_DT_DATE32: out->width = 4; out->is_signed = 1; break;

@@ -403,6 +403,16 @@ void pinned_release_all() {
   g_pinned.cached = 0;
 }
 
+int pinned_reserve(void **p, size_t *cap, size_t bytes) {
+  if (bytes <= *cap) return LLKV_OK;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  HIP_TRY(hipHostMalloc(p, bytes + bytes / 4 + 64, hipHostMallocDefault));
+  *cap = bytes + bytes / 4 + 64;
+  return LLKV_OK;
+}
+
 // ---- large results handed to the caller ------------------------------------------------
 // A fresh malloc of hundreds of MB is page-faulted in while it is filled (≈ 6 GB/s); results of that size are
 // handed out in recycled pinned blocks instead, which the device writes at PCIe speed.  llkv_hip_free tells the

@@ -15,18 +15,6 @@ static constexpr uint32_t kRowStreamChunk = 65536; // ROW_STREAM_CHUNK_SIZE, llk
 static constexpr uint32_t kSelectTileRows = 8192;
 
 using DeviceBuf = Scratch;
-// Pinned host buffers are recycled: pinning memory costs far more than a selective scan (hundreds of µs per
-// buffer), so freed blocks wait in a small cache for the next stream.
-struct PinnedBuf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  ~PinnedBuf() { if (p) pinned_release(p, bytes); }
-  int alloc(size_t n) {
-    bytes = n ? n : 8;
-    p = pinned_acquire(&bytes);
-    return p ? LLKV_OK : set_error(LLKV_INTERNAL, "pinned host allocation of " + std::to_string(bytes) + " bytes failed");
-  }
-};
 
 int run_selection(const Table *t, const llkv_filter *filters, uint32_t n_filters, const llkv_eval_op *ops,
                   uint32_t n_ops, Selection *sel, const uint32_t *drop_null_fields, uint32_t n_drop_null_fields) {
@@ -66,7 +54,7 @@ int run_selection_lowered(const Table *t, const LoweredPlan &plan, Selection *se
   for (size_t s = 0; s < plan.slot_fields.size(); ++s) p.col[s] = slot_buffer(t->cols, plan, s);
   for (size_t i = 0; i < plan.lit_i.size(); ++i) p.lit_i[i] = plan.lit_i[i];
   for (size_t i = 0; i < plan.lit_f.size(); ++i) p.lit_f[i] = plan.lit_f[i];
-  p.tiles = ts->d_tiles;
+  p.tiles = ts->d_tiles.get<TileDesc>();
   p.n_tiles = ts->n_tiles;
   p.sub_rows = kSelectTileRows / (kBlock / 64);
   p.tile_partials = (uint64_t *)counts.p;
@@ -82,7 +70,7 @@ int run_selection_lowered(const Table *t, const LoweredPlan &plan, Selection *se
     DeviceBuf sample_counts;
     if ((rc = sample_counts.alloc((size_t)sample_slots * 8))) return rc;
     ScanParams ps = p;
-    ps.tiles = ts->d_sample;
+    ps.tiles = ts->d_sample.get<TileDesc>();
     ps.n_tiles = ts->n_sample;
     ps.tile_partials = (uint64_t *)sample_counts.p;
     if ((rc = jit_launch_raw(k.fn, ts->n_sample, &ps, sizeof ps, stream))) return rc;
@@ -141,7 +129,7 @@ int run_selection_lowered(const Table *t, const LoweredPlan &plan, Selection *se
 // column of scan windows — are the table's; translated in place from the device row indices, after any sort of the selection.
 static int selection_report_ids(const Table *t, Selection *sel) {
   if (!t->d_row_ids || sel->n == 0) return LLKV_OK;
-  HIP_TRY(hj_launch_gather_u64_by_row(t->d_row_ids, sel->d_dev, sel->n, sel->d_ids, g_ctx.stream));
+  HIP_TRY(hj_launch_gather_u64_by_row(t->d_row_ids.get<uint64_t>(), sel->d_dev, sel->n, sel->d_ids, g_ctx.stream));
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   return LLKV_OK;
 }
@@ -167,8 +155,8 @@ static int sort_selection(const Table *t, const llkv_scan_options *o, Selection 
   hipStream_t s = g_ctx.stream;
   JoinKeyColumn kc;
   std::memset(&kc, 0, sizeof kc);
-  kc.values = c.d_values;
-  kc.valid = c.info.nullable ? c.d_valid : nullptr;
+  kc.values = c.d_values.get();
+  kc.valid = c.info.nullable ? c.d_valid.get<uint8_t>() : nullptr;
   long long base = 0;
   Scratch rank_d;
   const uint8_t *code_rank = nullptr;

@@ -19,21 +19,6 @@ static uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 // ---------------------------------------------------------------------------------
 // Table image
 // ---------------------------------------------------------------------------------
-Table::~Table() {
-  for (auto &kv : cols) {
-    if (kv.second.owned && kv.second.d_values) (void)hipFree(kv.second.d_values);
-    if (kv.second.d_valid) (void)hipFree(kv.second.d_valid);
-    if (kv.second.d_hi) (void)hipFree(kv.second.d_hi);
-  }
-  if (d_row_ids) (void)hipFree(d_row_ids);
-  for (void *p : retired) (void)hipFree(p);
-  for (auto &kv : key_images) if (kv.second.d) (void)hipFree(kv.second.d);
-  for (auto &kv : tilesets) {
-    if (kv.second.d_tiles) (void)hipFree(kv.second.d_tiles);
-    if (kv.second.d_sample) (void)hipFree(kv.second.d_sample);
-  }
-}
-
 // Canonical octant bounds over the global chunk list and the shard of this rank
 // (DESIGN.md "Sharding").  Pure host logic: also exercised by the CPU tests.
 void compute_layout(Table &t) {
@@ -103,17 +88,17 @@ int get_tileset(const Table &tc, uint32_t tile_rows, const TileSet **out) {
   ts.n_tiles = (uint32_t)tiles.size();
   ts.tile_rows = tile_rows;
   if (ts.n_tiles) {
-    HIP_TRY(hipMalloc((void **)&ts.d_tiles, tiles.size() * sizeof(TileDesc)));
-    HIP_TRY(hipMemcpy(ts.d_tiles, tiles.data(), tiles.size() * sizeof(TileDesc), hipMemcpyHostToDevice));
+    HIP_TRY(ts.d_tiles.alloc(tiles.size(), sizeof(TileDesc)));
+    HIP_TRY(hipMemcpy(ts.d_tiles.get(), tiles.data(), tiles.size() * sizeof(TileDesc), hipMemcpyHostToDevice));
     std::vector<TileDesc> sample;
     for (size_t i = kTileSampleStride / 2; i < tiles.size(); i += kTileSampleStride) { sample.push_back(tiles[i]); ts.sample_rows += tiles[i].rows; }
     ts.n_sample = (uint32_t)sample.size();
     if (ts.n_sample) {
-      HIP_TRY(hipMalloc((void **)&ts.d_sample, sample.size() * sizeof(TileDesc)));
-      HIP_TRY(hipMemcpy(ts.d_sample, sample.data(), sample.size() * sizeof(TileDesc), hipMemcpyHostToDevice));
+      HIP_TRY(ts.d_sample.alloc(sample.size(), sizeof(TileDesc)));
+      HIP_TRY(hipMemcpy(ts.d_sample.get(), sample.data(), sample.size() * sizeof(TileDesc), hipMemcpyHostToDevice));
     }
   }
-  auto ins = t.tilesets.emplace(tile_rows, ts);
+  auto ins = t.tilesets.emplace(tile_rows, std::move(ts));
   *out = &ins.first->second;
   return LLKV_OK;
 }
@@ -138,9 +123,9 @@ int get_key_image(const Table &tc, uint32_t field, uint64_t min_rows, const KeyI
   // (padding rows between chunks and the slack behind the image hold what the column holds there — zeros or copies of real rows,
   // truncated like any other: no tile names them)
   const uint64_t rows = t.dev_rows + kSlackRows;
-  HIP_TRY(hipMalloc(&img.d, rows * 4));
-  HIP_TRY(launch_narrow_i64((const int64_t *)c.d_values, rows, (int32_t *)img.d, g_ctx.stream));
-  auto ins = t.key_images.emplace(field, img);
+  HIP_TRY(img.d.alloc(rows, 4));
+  HIP_TRY(launch_narrow_i64(c.d_values.get<const int64_t>(), rows, img.d.get<int32_t>(), g_ctx.stream));
+  auto ins = t.key_images.emplace(field, std::move(img));
   *out = &ins.first->second;
   return LLKV_OK;
 }
@@ -154,11 +139,11 @@ uint64_t table_chunk_rows(const llkv_hip_table *table, uint32_t global_chunk) {
 // `rows_overwritten`: every row of the image is about to be staged over (value buffers of a table without padding rows
 // between its chunks): only the slack behind the image is zeroed — the runtime's fill moves ~130 GB/s, which made zeroing
 // SF10's five 480 MB columns a fifth of their staging time
-static int alloc_column(Table &t, uint32_t width, void **d_out, bool rows_overwritten = false) {
-  const uint64_t bytes = (t.dev_rows + kSlackRows) * width;
-  HIP_TRY(hipMalloc(d_out, bytes));
-  if (rows_overwritten && t.dev_rows == t.local_rows) HIP_TRY(hipMemsetAsync((char *)*d_out + t.dev_rows * width, 0, kSlackRows * width, g_ctx.stream));
-  else HIP_TRY(hipMemsetAsync(*d_out, 0, bytes, g_ctx.stream));
+static int alloc_column(Table &t, uint32_t width, DeviceBuffer &out, bool rows_overwritten = false) {
+  const uint64_t rows = t.dev_rows + kSlackRows;
+  HIP_TRY(out.alloc(rows, width));
+  if (rows_overwritten && t.dev_rows == t.local_rows) HIP_TRY(hipMemsetAsync(out.get<char>() + t.dev_rows * width, 0, kSlackRows * width, g_ctx.stream));
+  else HIP_TRY(hipMemsetAsync(out.get(), 0, rows * width, g_ctx.stream));
   return LLKV_OK;
 }
 
@@ -207,20 +192,20 @@ static int fill_chunk_padding(Table &t, void *d_values, uint32_t width) {
 
 static int column_stats_device(Table &t, DeviceColumn &c) {
   if (t.dev_rows != t.local_rows && c.d_values) {
-    const int rc = fill_chunk_padding(t, c.d_values, dtype_width(c.info.dtype));
+    const int rc = fill_chunk_padding(t, c.d_values.get(), dtype_width(c.info.dtype));
     if (rc) return rc;
   }
   if ((c.info.dtype == LLKV_DT_FLOAT64 || c.info.dtype == LLKV_DT_FLOAT32) && t.dev_rows) {
     // largest and smallest non-zero finite |v|: they bound aggregate arguments from above and below, which lets the
     // shared-image GROUP BY keep f64 sums exact (padding rows between ragged chunks hold copies of real values)
-    uint64_t *d = nullptr, bits[3] = {0, 0x7FF0000000000000ull, 0};
-    HIP_TRY(hipMalloc((void **)&d, 24));
-    HIP_TRY(hipMemcpyAsync(d, bits, 24, hipMemcpyHostToDevice, g_ctx.stream));
-    if (c.info.dtype == LLKV_DT_FLOAT64) HIP_TRY(launch_absrange_f64((const double *)c.d_values, t.dev_rows, d, g_ctx.stream));
-    else HIP_TRY(launch_absrange_f32((const float *)c.d_values, t.dev_rows, d, g_ctx.stream));
-    HIP_TRY(hipMemcpyAsync(bits, d, 24, hipMemcpyDeviceToHost, g_ctx.stream));
+    uint64_t bits[3] = {0, 0x7FF0000000000000ull, 0};
+    DeviceBuffer d;
+    HIP_TRY(d.alloc(3, 8));
+    HIP_TRY(hipMemcpyAsync(d.get(), bits, 24, hipMemcpyHostToDevice, g_ctx.stream));
+    if (c.info.dtype == LLKV_DT_FLOAT64) HIP_TRY(launch_absrange_f64(c.d_values.get<const double>(), t.dev_rows, d.get<uint64_t>(), g_ctx.stream));
+    else HIP_TRY(launch_absrange_f32(c.d_values.get<const float>(), t.dev_rows, d.get<uint64_t>(), g_ctx.stream));
+    HIP_TRY(hipMemcpyAsync(bits, d.get(), 24, hipMemcpyDeviceToHost, g_ctx.stream));
     HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-    (void)hipFree(d);
     c.has_local_fstats = true;
     std::memcpy(&c.local_f_absmax, &bits[0], 8);
     std::memcpy(&c.local_f_absmin_nz, &bits[1], 8);
@@ -232,25 +217,25 @@ static int column_stats_device(Table &t, DeviceColumn &c) {
   }
   if (c.info.dtype != LLKV_DT_INT64 && c.info.dtype != LLKV_DT_INT32 && c.info.dtype != LLKV_DT_DATE32 && c.info.dtype != LLKV_DT_DECIMAL128) return LLKV_OK;
   if (t.dev_rows == 0) return LLKV_OK;
-  int64_t init[3] = {INT64_MAX, INT64_MIN, 0}, *d = nullptr;
-  HIP_TRY(hipMalloc((void **)&d, sizeof init));
-  HIP_TRY(hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, g_ctx.stream));
+  int64_t init[3] = {INT64_MAX, INT64_MIN, 0};
+  DeviceBuffer d;
+  HIP_TRY(d.alloc(3, 8));
+  HIP_TRY(hipMemcpyAsync(d.get(), init, sizeof init, hipMemcpyHostToDevice, g_ctx.stream));
   // (padding rows between ragged chunks hold a copy of a real value: fill_chunk_padding)
-  if (c.info.dtype == LLKV_DT_INT64 || c.info.dtype == LLKV_DT_DECIMAL128) HIP_TRY(launch_minmax_i64((const int64_t *)c.d_values, t.dev_rows, d, g_ctx.stream));
-  else HIP_TRY(launch_minmax_i32((const int32_t *)c.d_values, t.dev_rows, d, g_ctx.stream));
+  if (c.info.dtype == LLKV_DT_INT64 || c.info.dtype == LLKV_DT_DECIMAL128) HIP_TRY(launch_minmax_i64(c.d_values.get<const int64_t>(), t.dev_rows, d.get<int64_t>(), g_ctx.stream));
+  else HIP_TRY(launch_minmax_i32(c.d_values.get<const int32_t>(), t.dev_rows, d.get<int64_t>(), g_ctx.stream));
   // … and whether the rows are in strictly ascending value order (a clustered key): a dimension selected from such a
   // column is in key order and has no key twice (join_agg.cpp)
   const bool ordered_type = c.info.dtype != LLKV_DT_DECIMAL128;
   const TileSet *ts = nullptr;
   if (ordered_type && t.world == 1) {
     const int rc = get_tileset(t, 8192, &ts);
-    if (rc) { (void)hipFree(d); return rc; }
-    HIP_TRY(launch_ascending_check(c.d_values, c.info.dtype == LLKV_DT_INT64 ? 8 : 4, ts->d_tiles, ts->n_tiles, reinterpret_cast<uint32_t *>(d + 2), g_ctx.stream));
+    if (rc) return rc;
+    HIP_TRY(launch_ascending_check(c.d_values.get(), c.info.dtype == LLKV_DT_INT64 ? 8 : 4, ts->d_tiles.get<TileDesc>(), ts->n_tiles, reinterpret_cast<uint32_t *>(d.get<int64_t>() + 2), g_ctx.stream));
   }
   int64_t mm[3];
-  HIP_TRY(hipMemcpyAsync(mm, d, sizeof mm, hipMemcpyDeviceToHost, g_ctx.stream));
+  HIP_TRY(hipMemcpyAsync(mm, d.get(), sizeof mm, hipMemcpyDeviceToHost, g_ctx.stream));
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  (void)hipFree(d);
   c.has_local_stats = true;
   c.local_min = mm[0];
   c.local_max = mm[1];
@@ -260,6 +245,229 @@ static int column_stats_device(Table &t, DeviceColumn &c) {
     c.info.max_i = mm[1];
     c.info.ascending = ts != nullptr && mm[2] == 0;
   }
+  return LLKV_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// Encoders: a run of the caller's chunks → a host image laid out like the device image.  First staging runs over the
+// local chunks (the image is the whole column), an append over its new chunks (the rows behind the old image).
+// ---------------------------------------------------------------------------------
+struct ChunkRun {
+  uint32_t n = 0;
+  const uint64_t *rows = nullptr; // [n] rows of each chunk
+  const uint64_t *dst = nullptr;  // [n + 1] first image row of each chunk (16-row aligned), then the image's end
+  uint64_t image_rows() const { return dst[n]; }
+};
+
+static ChunkRun local_run(const Table &t) { return {t.n_local_chunks, t.global_chunk_rows.data() + t.first_chunk, t.chunk_dev_off.data()}; }
+
+// fixed width: one staging piece per chunk, straight from the caller's buffer to its rows of the device image at `d_image`
+// (pieces = nullptr: only the chunk pointers are checked)
+static int fixed_width_pieces(const ChunkRun &run, const void *const *values, uint32_t width, char *d_image, std::vector<StagePiece> *pieces) {
+  for (uint32_t i = 0; i < run.n; ++i) {
+    if (!run.rows[i]) continue;
+    if (!values[i]) return set_error(LLKV_INVALID_ARGUMENT, "chunk values pointer is NULL");
+    if (pieces) pieces->push_back({d_image + run.dst[i] * width, values[i], run.rows[i] * width});
+  }
+  return LLKV_OK;
+}
+
+// every string of the chunk is one byte long (then string r is the byte data[off[0] + r])
+static bool all_unit_strings(const int32_t *off, uint64_t rows) {
+  if (rows == 0 || (int64_t)off[rows] - (int64_t)off[0] != (int64_t)rows) return false;
+  uint32_t bad = 0;
+  for (uint64_t r = 0; r < rows; ++r) bad |= (uint32_t)(off[r + 1] - off[r]) ^ 1u; // (branch-free: vectorises)
+  return bad == 0;
+}
+
+// Utf8 → 1 B/row dictionary codes (SURVEY.md §7 "Utf8 group keys") in `codes`, image_rows() + 16 bytes: padding rows and the
+// tail are zeroed, every other byte is written by the coding pass.  `dict` maps strings to codes.  `fixed`: a string outside
+// it is refused; else the new strings join it, and `words`, in order of first appearance over the run after the entries
+// already there, up to 256 (`too_many`: the refusal beyond).
+static int encode_utf8(const ChunkRun &run, const int32_t *const *offsets, const uint8_t *const *data, std::map<std::string, uint8_t> &dict,
+                       bool fixed, std::vector<std::string> &words, const std::string &too_many, uint8_t *codes) {
+  for (uint32_t i = 0; i < run.n; ++i) {
+    if (run.rows[i] && (!offsets[i] || !data[i])) return set_error(LLKV_INVALID_ARGUMENT, "chunk pointer is NULL");
+    const uint64_t end = run.dst[i] + run.rows[i];
+    std::memset(codes + end, 0, run.dst[i + 1] - end);
+  }
+  std::memset(codes + run.image_rows(), 0, 16);
+  const auto descending = [] { return set_error(LLKV_INVALID_ARGUMENT, "Utf8 offsets must not descend"); };
+  int rc;
+  if (!fixed) {
+    // every chunk lists its distinct values in order of first appearance (in parallel), the lists are merged in chunk order
+    std::vector<std::vector<std::string>> seen(run.n);
+    rc = for_each_chunk_parallel(run.n, [&](uint32_t i) -> int {
+      const uint64_t rows = run.rows[i];
+      const int32_t *off = offsets[i];
+      const uint8_t *bytes = data[i];
+      bool one_byte[256] = {};
+      std::map<std::string, int> local;
+      if (all_unit_strings(off, rows)) { // a chunk of 1-byte strings (TPC-H flags): the byte is the string
+        const uint8_t *b = bytes + off[0];
+        for (uint64_t r = 0; r < rows; ++r)
+          if (!one_byte[b[r]]) { one_byte[b[r]] = true; seen[i].emplace_back(1, (char)b[r]); }
+        return LLKV_OK;
+      }
+      for (uint64_t r = 0; r < rows; ++r) {
+        if (off[r + 1] < off[r]) return descending();
+        const int32_t len = off[r + 1] - off[r];
+        if (len == 1) {
+          const uint8_t ch = bytes[off[r]];
+          if (!one_byte[ch]) { one_byte[ch] = true; seen[i].emplace_back(1, (char)ch); }
+        } else {
+          std::string s((const char *)bytes + off[r], (size_t)len);
+          if (local.emplace(s, 0).second) seen[i].push_back(std::move(s));
+        }
+        if (seen[i].size() > 256) return set_error(LLKV_UNSUPPORTED, too_many);
+      }
+      return LLKV_OK;
+    });
+    if (rc) return rc;
+    for (uint32_t i = 0; i < run.n; ++i)
+      for (std::string &s : seen[i])
+        if (!dict.count(s)) {
+          if (dict.size() >= 256) return set_error(LLKV_UNSUPPORTED, too_many);
+          dict.emplace(s, (uint8_t)dict.size());
+          words.push_back(s);
+        }
+  }
+  return for_each_chunk_parallel(run.n, [&](uint32_t i) -> int {
+    const uint64_t rows = run.rows[i];
+    const int32_t *off = offsets[i];
+    const uint8_t *bytes = data[i];
+    uint8_t *dst = codes + run.dst[i];
+    int16_t lut[256]; // fast path for 1-byte strings (TPC-H flags)
+    std::fill(std::begin(lut), std::end(lut), (int16_t)-1);
+    auto code_of = [&](const std::string &s, uint8_t *out) -> int {
+      auto it = dict.find(s);
+      if (it == dict.end()) return set_error(LLKV_INVALID_ARGUMENT, "value '" + s + "' is not in the supplied dictionary");
+      *out = it->second;
+      return LLKV_OK;
+    };
+    if (all_unit_strings(off, rows)) {
+      uint8_t code_of_byte[256];
+      bool known[256] = {};
+      const uint8_t *b = bytes + off[0];
+      for (uint64_t r = 0; r < rows; ++r) { // (first: which bytes occur — a dictionary miss is reported before anything is written)
+        if (known[b[r]]) continue;
+        int e;
+        if ((e = code_of(std::string(1, (char)b[r]), &code_of_byte[b[r]]))) return e;
+        known[b[r]] = true;
+      }
+      for (uint64_t r = 0; r < rows; ++r) dst[r] = code_of_byte[b[r]];
+      return LLKV_OK;
+    }
+    for (uint64_t r = 0; r < rows; ++r) {
+      if (off[r + 1] < off[r]) return descending();
+      const int32_t len = off[r + 1] - off[r];
+      int e;
+      if (len == 1) {
+        const uint8_t ch = bytes[off[r]];
+        if (lut[ch] < 0) {
+          uint8_t code;
+          if ((e = code_of(std::string(1, (char)ch), &code))) return e;
+          lut[ch] = code;
+        }
+        dst[r] = (uint8_t)lut[ch];
+      } else if ((e = code_of(std::string((const char *)bytes + off[r], (size_t)len), &dst[r]))) {
+        return e;
+      }
+    }
+    return LLKV_OK;
+  });
+}
+
+// Decimal128 (lo, hi) pairs → the 8 B/row image of the low halves in `lo` (image_rows() + 16, padding rows zero); *wide: some
+// value needs more than 64 bits.  Given `hi`, a wide run also gets the image of its high halves there and the values'
+// min / max / max|v| in `info`.
+static int encode_decimal128(const ChunkRun &run, const void *const *values, std::vector<int64_t> &lo, bool *wide,
+                             std::vector<int64_t> *hi = nullptr, ColumnInfo *info = nullptr) {
+  lo.assign(run.image_rows() + 16, 0);
+  std::atomic<bool> any_wide{false};
+  const int rc = for_each_chunk_parallel(run.n, [&](uint32_t i) -> int {
+    const uint64_t rows = run.rows[i];
+    if (rows && !values[i]) return set_error(LLKV_INVALID_ARGUMENT, "chunk values pointer is NULL");
+    const int64_t *src = static_cast<const int64_t *>(values[i]); // (lo, hi) pairs, little endian
+    int64_t *dst = lo.data() + run.dst[i];
+    bool w = false;
+    for (uint64_t r = 0; r < rows; ++r) {
+      const int64_t l = src[2 * r], h = src[2 * r + 1];
+      w |= h != (l >> 63);
+      dst[r] = l;
+    }
+    if (w) any_wide = true;
+    return LLKV_OK;
+  });
+  if (rc) return rc;
+  *wide = any_wide;
+  if (!*wide || !hi) return LLKV_OK;
+  hi->assign(run.image_rows() + 16, 0);
+  unsigned __int128 absmax = 0;
+  __int128 vmin = (__int128)(~(unsigned __int128)0 >> 1), vmax = -vmin - 1; // smallest / largest value (MIN / MAX run over v − min, plan.cpp)
+  for (uint32_t i = 0; i < run.n; ++i) { // (sequential: wide columns are rare, and max|v| is one value)
+    const int64_t *src = static_cast<const int64_t *>(values[i]);
+    int64_t *dst = hi->data() + run.dst[i];
+    for (uint64_t r = 0; r < run.rows[i]; ++r) {
+      dst[r] = src[2 * r + 1];
+      const __int128 v = ((__int128)src[2 * r + 1] << 64) | (unsigned __int128)(uint64_t)src[2 * r];
+      const unsigned __int128 mag = v < 0 ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
+      absmax = mag > absmax ? mag : absmax;
+      vmin = v < vmin ? v : vmin;
+      vmax = v > vmax ? v : vmax;
+    }
+  }
+  info->wide128 = true;
+  info->wide_absmax_hi = (uint64_t)(absmax >> 64);
+  info->wide_absmax_lo = (uint64_t)absmax;
+  info->wide_min_hi = (uint64_t)(vmin >> 64); info->wide_min_lo = (uint64_t)vmin;
+  info->wide_max_hi = (uint64_t)(vmax >> 64); info->wide_max_lo = (uint64_t)vmax;
+  return LLKV_OK;
+}
+
+// Arrow validity bitmaps → 1 B/row in `mask` (image_rows() + 16; padding rows stay 0: tiles never select them).  A chunk
+// without a bitmap (all of them when `bitmaps` is NULL) has every cell present.  *nulls = the NULL cells of the run.
+static int encode_validity(const ChunkRun &run, const uint8_t *const *bitmaps, std::vector<uint8_t> &mask, uint64_t *nulls) {
+  mask.assign(run.image_rows() + 16, 0);
+  std::atomic<uint64_t> n_null{0};
+  const int rc = for_each_chunk_parallel(run.n, [&](uint32_t i) -> int {
+    const uint64_t rows = run.rows[i];
+    uint8_t *dst = mask.data() + run.dst[i];
+    const uint8_t *bits = bitmaps ? bitmaps[i] : nullptr;
+    if (!bits) { std::memset(dst, 1, rows); return LLKV_OK; }
+    uint64_t n = 0;
+    for (uint64_t r = 0; r < rows; ++r) {
+      const uint8_t v = (bits[r >> 3] >> (r & 7)) & 1u;
+      dst[r] = v;
+      n += !v;
+    }
+    n_null += n;
+    return LLKV_OK;
+  });
+  *nulls = n_null;
+  return rc;
+}
+
+// Row ids ascend strictly over the run (positions and ids order alike: scans, windows, first-appearance order and the joins'
+// probe order all follow the position), and above *last when `have`; *last becomes the run's last id.  *dense: every id is
+// its position, the run's first row being position `at` (dense ids need no translation).  `append`: the refusal names the
+// table's last id instead of the row.
+static int walk_row_ids(const ChunkRun &run, const uint64_t *const *ids, uint64_t at, bool have, uint64_t *last, bool *dense, bool append) {
+  uint64_t prev = *last;
+  *dense = true;
+  for (uint32_t i = 0; i < run.n; ++i) {
+    if (run.rows[i] && !ids[i]) return set_error(LLKV_INVALID_ARGUMENT, "chunk row-id pointer is NULL");
+    for (uint64_t r = 0; r < run.rows[i]; ++r, ++at) {
+      const uint64_t id = ids[i][r];
+      if (have && id <= prev)
+        return set_error(LLKV_INVALID_ARGUMENT, append ? std::string("row ids must ascend strictly beyond the table's last id")
+                                                       : "row ids must ascend strictly (chunk " + std::to_string(i) + ", row " + std::to_string(r) + ")");
+      prev = id;
+      have = true;
+      *dense &= id == at;
+    }
+  }
+  *last = prev;
   return LLKV_OK;
 }
 
@@ -314,33 +522,18 @@ llkv_status llkv_hip_table_set_row_ids(llkv_hip_table *table, const uint64_t *co
   if (t->d_row_ids) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "row ids already set");
   int rc = ensure_device();
   if (rc) return (llkv_status)rc;
-  // strictly ascending over the local chunks (positions and ids order alike: scans, windows, first-appearance order and
-  // the joins' probe order all follow the position); dense ids from the table's first position need no translation
-  bool dense = true, have = false;
-  uint64_t prev = 0, at = t->local_logical_start;
-  for (uint32_t i = 0; i < n_chunks; ++i) {
-    const uint64_t rows = t->global_chunk_rows[t->first_chunk + i];
-    if (rows && !chunk_row_ids[i]) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "chunk row-id pointer is NULL");
-    for (uint64_t r = 0; r < rows; ++r, ++at) {
-      const uint64_t id = chunk_row_ids[i][r];
-      if (have && id <= prev) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "row ids must ascend strictly (chunk " + std::to_string(i) + ", row " + std::to_string(r) + ")");
-      prev = id;
-      have = true;
-      dense &= id == at;
-    }
-  }
+  const ChunkRun run = local_run(*t);
+  bool dense = true;
+  uint64_t last = 0;
+  if ((rc = walk_row_ids(run, chunk_row_ids, t->local_logical_start, false, &last, &dense, false))) return (llkv_status)rc;
   if (dense) return LLKV_OK;
-  void *d = nullptr;
-  if ((rc = alloc_column(*t, 8, &d))) return (llkv_status)rc;
+  DeviceBuffer d;
+  if ((rc = alloc_column(*t, 8, d))) return (llkv_status)rc;
   std::vector<StagePiece> pieces;
-  for (uint32_t i = 0; i < n_chunks; ++i) {
-    const uint64_t rows = t->global_chunk_rows[t->first_chunk + i];
-    if (rows) pieces.push_back({(char *)d + t->chunk_dev_off[i] * 8, chunk_row_ids[i], rows * 8});
-  }
-  if (hipStreamSynchronize(g_ctx.stream) != hipSuccess || (rc = stage_to_device(pieces))) { (void)hipFree(d); return (llkv_status)(rc ? rc : set_error(LLKV_INTERNAL, "staging copy failed")); }
-  t->d_row_ids = static_cast<uint64_t *>(d);
-  t->row_ids_cap = t->dev_rows + kSlackRows;
-  t->last_row_id = prev;
+  if ((rc = fixed_width_pieces(run, reinterpret_cast<const void *const *>(chunk_row_ids), 8, d.get<char>(), &pieces))) return (llkv_status)rc;
+  if (hipStreamSynchronize(g_ctx.stream) != hipSuccess || (rc = stage_to_device(pieces))) return (llkv_status)(rc ? rc : set_error(LLKV_INTERNAL, "staging copy failed"));
+  t->d_row_ids = std::move(d);
+  t->last_row_id = last;
   return LLKV_OK;
 }
 
@@ -356,27 +549,14 @@ llkv_status llkv_hip_table_append_column(llkv_hip_table *table, uint32_t field_i
   c.info.field_id = field_id;
   c.info.dtype = dtype;
   c.info.rows = t->total_rows;
-  c.owned = true;
-  if ((rc = alloc_column(*t, w, &c.d_values, true))) return (llkv_status)rc;
+  if ((rc = alloc_column(*t, w, c.d_values, true))) return (llkv_status)rc;
   std::vector<StagePiece> pieces;
-  for (uint32_t i = 0; i < n_chunks; ++i) {
-    const uint64_t rows = t->global_chunk_rows[t->first_chunk + i];
-    if (rows && !chunk_values[i]) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "chunk values pointer is NULL");
-    if (rows) pieces.push_back({(char *)c.d_values + t->chunk_dev_off[i] * w, chunk_values[i], rows * w});
-  }
+  if ((rc = fixed_width_pieces(local_run(*t), chunk_values, w, c.d_values.get<char>(), &pieces))) return (llkv_status)rc;
   if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) return (llkv_status)set_error(LLKV_INTERNAL, "staging copy failed"); // the image is zeroed
   if ((rc = stage_to_device(pieces))) return (llkv_status)rc;
   if ((rc = column_stats_device(*t, c))) return (llkv_status)rc;
   t->cols.emplace(field_id, std::move(c));
   return LLKV_OK;
-}
-
-// every string of the chunk is one byte long (then string r is the byte data[off[0] + r])
-static bool all_unit_strings(const int32_t *off, uint64_t rows) {
-  if (rows == 0 || (int64_t)off[rows] - (int64_t)off[0] != (int64_t)rows) return false;
-  uint32_t bad = 0;
-  for (uint64_t r = 0; r < rows; ++r) bad |= (uint32_t)(off[r + 1] - off[r]) ^ 1u; // (branch-free: vectorises)
-  return bad == 0;
 }
 
 llkv_status llkv_hip_table_append_utf8_column(llkv_hip_table *table, uint32_t field_id,
@@ -393,10 +573,6 @@ llkv_status llkv_hip_table_append_utf8_column(llkv_hip_table *table, uint32_t fi
   c.info.field_id = field_id;
   c.info.dtype = LLKV_DT_UTF8;
   c.info.rows = t->total_rows;
-  c.owned = true;
-  // dictionary-encode on the host at staging (SURVEY.md §7 "Utf8 group keys"): 1 B/row in HBM
-  // (not value-initialised: 60 MB of zeroes written by one thread cost as much as coding the column on sixteen; the padding
-  // rows between ragged chunks are zeroed below, every other byte is written by the coding pass)
   const bool trace = std::getenv("LLKV_HIP_TRACE") != nullptr;
   auto t_last = std::chrono::steady_clock::now();
   auto mark = [&](const char *what) {
@@ -405,22 +581,10 @@ llkv_status llkv_hip_table_append_utf8_column(llkv_hip_table *table, uint32_t fi
     std::fprintf(stderr, "[llkv utf8 staging] %-18s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
     t_last = now;
   };
-  // … and not a fresh heap block either: 60 MB of new pages are faulted in while they are written, pinned for the copy and
-  // unmapped on the way out (≈ 10 ms a column at SF10) — a recycled block of the pinned cache is written and copied at once
-  size_t codes_bytes = (size_t)t->dev_rows + 16;
-  struct PinnedBlock {
-    void *p = nullptr; size_t bytes = 0;
-    ~PinnedBlock() { if (p) pinned_release(p, bytes); }
-  } codes_block;
-  codes_block.p = pinned_acquire(&codes_bytes);
-  codes_block.bytes = codes_bytes;
-  if (!codes_block.p) return (llkv_status)set_error(LLKV_INTERNAL, "no pinned host memory for the dictionary codes");
-  struct { uint8_t *p; uint8_t *data() const { return p; } } codes{static_cast<uint8_t *>(codes_block.p)};
-  for (uint32_t i = 0; i < n_chunks; ++i) {
-    const uint64_t end = t->chunk_dev_off[i] + t->global_chunk_rows[t->first_chunk + i];
-    std::memset(codes.data() + end, 0, t->chunk_dev_off[i + 1] - end);
-  }
-  std::memset(codes.data() + t->dev_rows, 0, 16);
+  // the codes go to a recycled block of the pinned cache: a fresh heap block has its 60 MB of new pages faulted in while they
+  // are written, pinned for the copy and unmapped on the way out (≈ 10 ms a column at SF10)
+  PinnedBuf codes;
+  if (codes.alloc((size_t)t->dev_rows + 16)) return (llkv_status)set_error(LLKV_INTERNAL, "no pinned host memory for the dictionary codes");
   std::map<std::string, uint8_t> dict;
   const bool fixed = dictionary != nullptr;
   for (uint32_t d = 0; d < dict_size && fixed; ++d) {
@@ -429,94 +593,14 @@ llkv_status llkv_hip_table_append_utf8_column(llkv_hip_table *table, uint32_t fi
     c.info.dictionary.push_back(s);
   }
   mark("buffer");
-  if (!fixed) {
-    // codes follow the order of first appearance: every chunk lists its distinct values in that order (in
-    // parallel), the lists are merged in chunk order
-    std::vector<std::vector<std::string>> seen(n_chunks);
-    rc = for_each_chunk_parallel(n_chunks, [&](uint32_t i) -> int {
-      const uint64_t rows = t->global_chunk_rows[t->first_chunk + i];
-      const int32_t *off = chunk_offsets[i];
-      const uint8_t *data = chunk_data[i];
-      bool one_byte[256] = {};
-      std::map<std::string, int> local;
-      if (all_unit_strings(off, rows)) { // a chunk of 1-byte strings (TPC-H flags): the byte is the string
-        const uint8_t *b = data + off[0];
-        for (uint64_t r = 0; r < rows; ++r)
-          if (!one_byte[b[r]]) { one_byte[b[r]] = true; seen[i].emplace_back(1, (char)b[r]); }
-        return LLKV_OK;
-      }
-      for (uint64_t r = 0; r < rows; ++r) {
-        const int32_t len = off[r + 1] - off[r];
-        if (len == 1) {
-          const uint8_t ch = data[off[r]];
-          if (!one_byte[ch]) { one_byte[ch] = true; seen[i].emplace_back(1, (char)ch); }
-        } else {
-          std::string s((const char *)data + off[r], (size_t)len);
-          if (local.emplace(s, 0).second) seen[i].push_back(std::move(s));
-        }
-        if (seen[i].size() > 256) return set_error(LLKV_UNSUPPORTED, "Utf8 column has more than 256 distinct values");
-      }
-      return LLKV_OK;
-    });
-    if (rc) return (llkv_status)rc;
-    for (uint32_t i = 0; i < n_chunks; ++i)
-      for (std::string &s : seen[i])
-        if (!dict.count(s)) {
-          if (dict.size() >= 256) return (llkv_status)set_error(LLKV_UNSUPPORTED, "Utf8 column has more than 256 distinct values");
-          dict.emplace(s, (uint8_t)dict.size());
-          c.info.dictionary.push_back(s);
-        }
-  }
-  mark("distinct values");
-  rc = for_each_chunk_parallel(n_chunks, [&](uint32_t i) -> int {
-    const uint64_t rows = t->global_chunk_rows[t->first_chunk + i];
-    const int32_t *off = chunk_offsets[i];
-    const uint8_t *data = chunk_data[i];
-    uint8_t *dst = codes.data() + t->chunk_dev_off[i];
-    int16_t lut[256]; // fast path for 1-byte strings (TPC-H flags)
-    std::fill(std::begin(lut), std::end(lut), (int16_t)-1);
-    auto code_of = [&](const std::string &s, uint8_t *out) -> int {
-      auto it = dict.find(s);
-      if (it == dict.end()) return set_error(LLKV_INVALID_ARGUMENT, "value '" + s + "' is not in the supplied dictionary");
-      *out = it->second;
-      return LLKV_OK;
-    };
-    if (all_unit_strings(off, rows)) {
-      uint8_t code_of_byte[256];
-      bool known[256] = {};
-      const uint8_t *b = data + off[0];
-      for (uint64_t r = 0; r < rows; ++r) { // (first: which bytes occur — a dictionary miss is reported before anything is written)
-        if (known[b[r]]) continue;
-        int e;
-        if ((e = code_of(std::string(1, (char)b[r]), &code_of_byte[b[r]]))) return e;
-        known[b[r]] = true;
-      }
-      for (uint64_t r = 0; r < rows; ++r) dst[r] = code_of_byte[b[r]];
-      return LLKV_OK;
-    }
-    for (uint64_t r = 0; r < rows; ++r) {
-      const int32_t len = off[r + 1] - off[r];
-      int e;
-      if (len == 1) {
-        const uint8_t ch = data[off[r]];
-        if (lut[ch] < 0) {
-          uint8_t code;
-          if ((e = code_of(std::string(1, (char)ch), &code))) return e;
-          lut[ch] = code;
-        }
-        dst[r] = (uint8_t)lut[ch];
-      } else if ((e = code_of(std::string((const char *)data + off[r], (size_t)len), &dst[r]))) {
-        return e;
-      }
-    }
-    return LLKV_OK;
-  });
-  if (rc) return (llkv_status)rc;
+  if ((rc = encode_utf8(local_run(*t), chunk_offsets, chunk_data, dict, fixed, c.info.dictionary, "Utf8 column has more than 256 distinct values",
+                        static_cast<uint8_t *>(codes.p))))
+    return (llkv_status)rc;
   mark("codes");
-  if ((rc = alloc_column(*t, 1, &c.d_values))) return (llkv_status)rc;
+  if ((rc = alloc_column(*t, 1, c.d_values))) return (llkv_status)rc;
   if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) return (llkv_status)set_error(LLKV_INTERNAL, "staging copy failed");
   mark("device buffer");
-  if ((rc = stage_from_pinned(c.d_values, codes.data(), (size_t)t->dev_rows))) return (llkv_status)rc;
+  if ((rc = stage_from_pinned(c.d_values.get(), codes.p, (size_t)t->dev_rows))) return (llkv_status)rc;
   mark("copy");
   t->cols.emplace(field_id, std::move(c));
   return LLKV_OK;
@@ -613,71 +697,26 @@ llkv_status llkv_hip_table_append_decimal128_column(llkv_hip_table *table, uint3
   if (precision < 1 || precision > 38 || scale > precision || scale < -128)
     return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "invalid Decimal128 precision/scale");
   if ((rc = ensure_device())) return (llkv_status)rc;
-  // narrow the 16-byte raw values to the 8 B/row device image.  A column with a value that needs more than 64 bits is
-  // staged as two 8 B/row buffers instead (low halves, high halves): SUM / TOTAL / AVG and the counts take it, every
-  // other use keeps the caller's CPU route (plan.cpp: slot_of)
-  std::vector<int64_t> narrow(t->dev_rows + 16, 0), high;
-  std::atomic<bool> any_wide{false};
-  rc = for_each_chunk_parallel(n_chunks, [&](uint32_t i) -> int {
-    const uint64_t rows = t->global_chunk_rows[t->first_chunk + i];
-    if (rows && !chunk_values[i]) return set_error(LLKV_INVALID_ARGUMENT, "chunk values pointer is NULL");
-    const int64_t *src = static_cast<const int64_t *>(chunk_values[i]); // (lo, hi) pairs, little endian
-    int64_t *dst = narrow.data() + t->chunk_dev_off[i];
-    bool wide = false;
-    for (uint64_t r = 0; r < rows; ++r) {
-      const int64_t lo = src[2 * r], hi = src[2 * r + 1];
-      wide |= hi != (lo >> 63);
-      dst[r] = lo;
-    }
-    if (wide) any_wide = true;
-    return LLKV_OK;
-  });
-  if (rc) return (llkv_status)rc;
   DeviceColumn c;
   c.info.field_id = field_id;
   c.info.dtype = LLKV_DT_DECIMAL128;
   c.info.precision = precision;
   c.info.scale = scale;
   c.info.rows = t->total_rows;
-  c.owned = true;
-  if (any_wide) {
-    // (a sharded table would need the ranks to agree on the layout and on max|v|: not exchanged yet)
-    if (t->world != 1) return (llkv_status)set_error(LLKV_UNSUPPORTED, "Decimal128 value beyond 64 bits in field " + std::to_string(field_id) + " of a sharded table");
-    high.assign(t->dev_rows + 16, 0);
-    unsigned __int128 absmax = 0;
-    __int128 vmin = (__int128)(~(unsigned __int128)0 >> 1), vmax = -vmin - 1; // smallest / largest value (MIN / MAX run over v − min, plan.cpp)
-    for (uint32_t i = 0; i < n_chunks; ++i) { // (sequential: wide columns are rare, and max|v| is one value)
-      const uint64_t rows = t->global_chunk_rows[t->first_chunk + i];
-      const int64_t *src = static_cast<const int64_t *>(chunk_values[i]);
-      int64_t *dst = high.data() + t->chunk_dev_off[i];
-      for (uint64_t r = 0; r < rows; ++r) {
-        dst[r] = src[2 * r + 1];
-        const __int128 v = ((__int128)src[2 * r + 1] << 64) | (unsigned __int128)(uint64_t)src[2 * r];
-        const unsigned __int128 mag = v < 0 ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
-        absmax = mag > absmax ? mag : absmax;
-        vmin = v < vmin ? v : vmin;
-        vmax = v > vmax ? v : vmax;
-      }
-    }
-    c.info.wide128 = true;
-    c.info.wide_absmax_hi = (uint64_t)(absmax >> 64);
-    c.info.wide_absmax_lo = (uint64_t)absmax;
-    c.info.wide_min_hi = (uint64_t)(vmin >> 64); c.info.wide_min_lo = (uint64_t)vmin;
-    c.info.wide_max_hi = (uint64_t)(vmax >> 64); c.info.wide_max_lo = (uint64_t)vmax;
-  }
-  if ((rc = alloc_column(*t, 8, &c.d_values)) || (any_wide && (rc = alloc_column(*t, 8, &c.d_hi)))) {
-    if (c.d_values) (void)hipFree(c.d_values);
-    return (llkv_status)rc;
-  }
+  // narrow the 16-byte raw values to the 8 B/row device image.  A column with a value that needs more than 64 bits is
+  // staged as two 8 B/row buffers instead (low halves, high halves): SUM / TOTAL / AVG and the counts take it, every
+  // other use keeps the caller's CPU route (plan.cpp: slot_of)
+  std::vector<int64_t> narrow, high;
+  bool wide = false;
+  if ((rc = encode_decimal128(local_run(*t), chunk_values, narrow, &wide, t->world == 1 ? &high : nullptr, &c.info))) return (llkv_status)rc;
+  // (a sharded table would need the ranks to agree on the layout and on max|v|: not exchanged yet)
+  if (wide && t->world != 1) return (llkv_status)set_error(LLKV_UNSUPPORTED, "Decimal128 value beyond 64 bits in field " + std::to_string(field_id) + " of a sharded table");
+  if ((rc = alloc_column(*t, 8, c.d_values)) || (wide && (rc = alloc_column(*t, 8, c.d_hi)))) return (llkv_status)rc;
   if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) return (llkv_status)set_error(LLKV_INTERNAL, "staging copy failed");
-  rc = any_wide ? stage_to_device({{c.d_values, narrow.data(), (size_t)t->dev_rows * 8}, {c.d_hi, high.data(), (size_t)t->dev_rows * 8}})
-                : stage_to_device({{c.d_values, narrow.data(), (size_t)t->dev_rows * 8}});
-  if (!rc && !any_wide) rc = column_stats_device(*t, c); // (integer statistics describe the narrowed image only)
-  if (rc) {
-    (void)hipFree(c.d_values);
-    if (c.d_hi) (void)hipFree(c.d_hi);
-    return (llkv_status)rc;
-  }
+  rc = wide ? stage_to_device({{c.d_values.get(), narrow.data(), (size_t)t->dev_rows * 8}, {c.d_hi.get(), high.data(), (size_t)t->dev_rows * 8}})
+            : stage_to_device({{c.d_values.get(), narrow.data(), (size_t)t->dev_rows * 8}});
+  if (!rc && !wide) rc = column_stats_device(*t, c); // (integer statistics describe the narrowed image only)
+  if (rc) return (llkv_status)rc;
   t->cols.emplace(field_id, std::move(c));
   return LLKV_OK;
 }
@@ -694,37 +733,21 @@ llkv_status llkv_hip_table_set_column_validity(llkv_hip_table *table, uint32_t f
   int rc = ensure_device();
   if (rc) return (llkv_status)rc;
   DeviceColumn &c = it->second;
-  // Arrow bitmaps → 1 B/row in the device row layout (rows of padding between chunks stay 0; tiles never
-  // select them)
-  std::vector<uint8_t> mask(t->dev_rows + 16, 0);
-  std::atomic<uint64_t> nulls{0};
-  rc = for_each_chunk_parallel(n_chunks, [&](uint32_t i) -> int {
-    const uint64_t rows = t->global_chunk_rows[t->first_chunk + i];
-    uint8_t *dst = mask.data() + t->chunk_dev_off[i];
-    const uint8_t *bits = chunk_validity[i];
-    if (!bits) { std::memset(dst, 1, rows); return LLKV_OK; }
-    uint64_t n = 0;
-    for (uint64_t r = 0; r < rows; ++r) {
-      const uint8_t v = (bits[r >> 3] >> (r & 7)) & 1u;
-      dst[r] = v;
-      n += !v;
-    }
-    nulls += n;
-    return LLKV_OK;
-  });
-  if (rc) return (llkv_status)rc;
-  if (c.d_valid) { (void)hipFree(c.d_valid); c.d_valid = nullptr; }
+  std::vector<uint8_t> mask;
+  uint64_t nulls = 0;
+  if ((rc = encode_validity(local_run(*t), chunk_validity, mask, &nulls))) return (llkv_status)rc;
+  c.d_valid.reset();
   c.info.nullable = false;
   // whether a column "has NULL cells" must not depend on the shard: with world > 1 any supplied bitmap makes
   // the column nullable on every rank (plans must agree across ranks)
   bool any_bitmap = false;
   for (uint32_t i = 0; i < n_chunks; ++i) any_bitmap |= chunk_validity[i] != nullptr;
   if (nulls == 0 && !(t->world > 1 && any_bitmap)) return LLKV_OK;
-  void *d = nullptr;
-  if ((rc = alloc_column(*t, 1, &d))) return (llkv_status)rc;
-  if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) { (void)hipFree(d); return (llkv_status)set_error(LLKV_INTERNAL, "staging copy failed"); }
-  if ((rc = stage_to_device({{d, mask.data(), (size_t)t->dev_rows}}))) { (void)hipFree(d); return (llkv_status)rc; }
-  c.d_valid = (uint8_t *)d;
+  DeviceBuffer d;
+  if ((rc = alloc_column(*t, 1, d))) return (llkv_status)rc;
+  if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) return (llkv_status)set_error(LLKV_INTERNAL, "staging copy failed");
+  if ((rc = stage_to_device({{d.get(), mask.data(), (size_t)t->dev_rows}}))) return (llkv_status)rc;
+  c.d_valid = std::move(d);
   c.info.nullable = true;
   return LLKV_OK;
 }
@@ -788,14 +811,12 @@ llkv_status llkv_hip_table_share_metadata(llkv_hip_table *table) {
     }
     if (any_nullable && !c.info.nullable) { // no NULL cell here: an all-present mask keeps this rank's plans those of its neighbours
       if ((rc = ensure_device())) return (llkv_status)rc;
-      void *d = nullptr;
+      DeviceBuffer d;
       const uint64_t bytes = t->dev_rows + kSlackRows;
-      if (hipMalloc(&d, bytes) != hipSuccess) return (llkv_status)set_error(LLKV_INTERNAL, "device allocation failed");
-      if (hipMemsetAsync(d, 1, bytes, g_ctx.stream) != hipSuccess || hipStreamSynchronize(g_ctx.stream) != hipSuccess) {
-        (void)hipFree(d);
+      if (d.alloc(bytes, 1) != hipSuccess) return (llkv_status)set_error(LLKV_INTERNAL, "device allocation failed");
+      if (hipMemsetAsync(d.get(), 1, bytes, g_ctx.stream) != hipSuccess || hipStreamSynchronize(g_ctx.stream) != hipSuccess)
         return (llkv_status)set_error(LLKV_INTERNAL, "validity mask could not be initialised");
-      }
-      c.d_valid = static_cast<uint8_t *>(d);
+      c.d_valid = std::move(d);
       c.info.nullable = true;
     }
     ++i;
@@ -813,12 +834,6 @@ llkv_status llkv_hip_table_share_metadata(llkv_hip_table *table) {
 // first buffer is touched.  Unsharded tables only: with world > 1 the canonical octants ⌊j·C/8⌋ move with the chunk count and
 // rows would change ranks.
 namespace {
-struct GrownBuffer {
-  void **slot = nullptr;   // the DeviceColumn member to repoint
-  void *fresh = nullptr;
-  uint32_t width = 0;
-  uint8_t fill = 0;
-};
 uint64_t with_headroom(uint64_t rows) { return rows + rows / 4 + kSlackRows; }
 } // namespace
 
@@ -836,186 +851,126 @@ static int append_chunks_impl(Table *t, const uint64_t *chunk_rows, uint32_t n_n
     if (!by_field.emplace(columns[i].field_id, &columns[i]).second) return set_error(LLKV_INVALID_ARGUMENT, "field " + std::to_string(columns[i].field_id) + " given twice");
   }
   // ---- the new layout (nothing of the table is touched yet) ------------------------------------------------------------------
+  // the new chunks' rows behind the old image (compute_layout rounds every chunk's end up to 16 rows: the old image ends on such
+  // a boundary)
   const uint32_t old_chunks = t->n_local_chunks;
   const uint64_t old_dev_rows = t->dev_rows;
-  std::vector<uint64_t> off(n_new + 1);
-  off[0] = old_dev_rows; // (compute_layout rounds every chunk's end up to 16 rows: the old image ends on such a boundary)
+  std::vector<uint64_t> off(n_new + 1, 0);
   uint64_t new_rows = 0;
   for (uint32_t i = 0; i < n_new; ++i) { off[i + 1] = round_up(off[i] + chunk_rows[i], 16); new_rows += chunk_rows[i]; }
-  const uint64_t new_dev_rows = off[n_new];
+  const ChunkRun run{n_new, chunk_rows, off.data()};
+  const uint64_t span = run.image_rows(), new_dev_rows = old_dev_rows + span;
   if (t->total_rows + new_rows >= (1ull << 38)) return set_error(LLKV_UNSUPPORTED, "table beyond 2^38 rows");
 
   // ---- host-side preparation per column: everything the DATA can refuse ------------------------------------------------------
   struct Prepared {
-    std::vector<StagePiece> pieces;        // straight from the caller's buffers (fixed width)
-    std::vector<int64_t> narrow;           // Decimal128: the 64-bit images of the new rows, [new_dev_rows − old_dev_rows]
-    std::vector<uint8_t> codes;            // Utf8: dictionary codes of the new rows
+    std::vector<int64_t> narrow;           // Decimal128: the 64-bit images of the new rows
+    PinnedBuf codes;                       // Utf8: dictionary codes of the new rows
     std::vector<std::string> new_words;    // … and the strings that join the dictionary
     std::vector<uint8_t> mask;             // validity bytes of the new rows (empty: every cell present and the column stays without a mask)
-    bool new_nulls = false;
   };
   std::map<uint32_t, Prepared> prep;
-  const uint64_t span = new_dev_rows - old_dev_rows;
   for (auto &kv : t->cols) {
     DeviceColumn &c = kv.second;
     const llkv_column_chunks &in = *by_field[kv.first];
     Prepared &p = prep[kv.first];
-    if (!c.owned) return set_error(LLKV_UNSUPPORTED, "append to a column the library does not own");
     if (c.info.wide128) return set_error(LLKV_UNSUPPORTED, "append to a Decimal128 column with values beyond 64 bits: re-stage it");
     const uint32_t w = dtype_width(c.info.dtype);
     if (c.info.dtype == LLKV_DT_UTF8) {
       if (!in.offsets || !in.data) return set_error(LLKV_INVALID_ARGUMENT, "Utf8 field " + std::to_string(kv.first) + " needs offsets and data");
       std::map<std::string, uint8_t> dict;
       for (size_t d = 0; d < c.info.dictionary.size(); ++d) dict.emplace(c.info.dictionary[d], (uint8_t)d);
-      p.codes.assign(span + 16, 0);
-      for (uint32_t i = 0; i < n_new; ++i) {
-        if (chunk_rows[i] && (!in.offsets[i] || !in.data[i])) return set_error(LLKV_INVALID_ARGUMENT, "chunk pointer is NULL");
-        const int32_t *o = in.offsets[i];
-        for (uint64_t r = 0; r < chunk_rows[i]; ++r) {
-          if (o[r + 1] < o[r]) return set_error(LLKV_INVALID_ARGUMENT, "Utf8 offsets must not descend");
-          std::string sv((const char *)in.data[i] + o[r], (size_t)(o[r + 1] - o[r]));
-          auto it = dict.find(sv);
-          if (it == dict.end()) {
-            if (dict.size() >= 256) return set_error(LLKV_UNSUPPORTED, "the append takes Utf8 field " + std::to_string(kv.first) + " beyond 256 distinct values: re-stage the table");
-            it = dict.emplace(sv, (uint8_t)dict.size()).first;
-            p.new_words.push_back(sv);
-          }
-          p.codes[off[i] - old_dev_rows + r] = it->second;
-        }
-      }
+      if ((rc = p.codes.alloc(span + 16)) ||
+          (rc = encode_utf8(run, in.offsets, in.data, dict, false, p.new_words,
+                            "the append takes Utf8 field " + std::to_string(kv.first) + " beyond 256 distinct values: re-stage the table", static_cast<uint8_t *>(p.codes.p))))
+        return rc;
     } else if (c.info.dtype == LLKV_DT_DECIMAL128) {
       if (!in.values) return set_error(LLKV_INVALID_ARGUMENT, "field " + std::to_string(kv.first) + " needs values");
-      p.narrow.assign(span + 16, 0);
-      for (uint32_t i = 0; i < n_new; ++i) {
-        if (chunk_rows[i] && !in.values[i]) return set_error(LLKV_INVALID_ARGUMENT, "chunk values pointer is NULL");
-        const int64_t *src = static_cast<const int64_t *>(in.values[i]);
-        for (uint64_t r = 0; r < chunk_rows[i]; ++r) {
-          if (src[2 * r + 1] != (src[2 * r] >> 63)) return set_error(LLKV_UNSUPPORTED, "the append brings a Decimal128 value beyond 64 bits into field " + std::to_string(kv.first) + ": re-stage the column");
-          p.narrow[off[i] - old_dev_rows + r] = src[2 * r];
-        }
-      }
+      bool wide = false;
+      if ((rc = encode_decimal128(run, in.values, p.narrow, &wide))) return rc;
+      if (wide) return set_error(LLKV_UNSUPPORTED, "the append brings a Decimal128 value beyond 64 bits into field " + std::to_string(kv.first) + ": re-stage the column");
     } else {
       if (!in.values || w == 0) return set_error(LLKV_INVALID_ARGUMENT, "field " + std::to_string(kv.first) + " needs values");
-      for (uint32_t i = 0; i < n_new; ++i) {
-        if (chunk_rows[i] && !in.values[i]) return set_error(LLKV_INVALID_ARGUMENT, "chunk values pointer is NULL");
-        if (chunk_rows[i]) p.pieces.push_back({nullptr, in.values[i], (size_t)chunk_rows[i] * w}); // (destination: once the buffer is known)
-      }
+      if ((rc = fixed_width_pieces(run, in.values, w, nullptr, nullptr))) return rc; // (the pieces: once the buffer is known)
     }
     bool any_bitmap = false;
     for (uint32_t i = 0; in.validity && i < n_new; ++i) any_bitmap |= in.validity[i] != nullptr;
     if (any_bitmap || c.info.nullable) {
-      p.mask.assign(span + 16, 0);
-      for (uint32_t i = 0; i < n_new; ++i) {
-        uint8_t *dst = p.mask.data() + (off[i] - old_dev_rows);
-        const uint8_t *bits = in.validity ? in.validity[i] : nullptr;
-        if (!bits) { std::memset(dst, 1, chunk_rows[i]); continue; }
-        for (uint64_t r = 0; r < chunk_rows[i]; ++r) { dst[r] = (bits[r >> 3] >> (r & 7)) & 1u; p.new_nulls |= !dst[r]; }
-      }
-      if (!c.info.nullable && !p.new_nulls) p.mask.clear(); // still no NULL cell: still no mask
+      uint64_t nulls = 0;
+      if ((rc = encode_validity(run, in.validity, p.mask, &nulls))) return rc;
+      if (!c.info.nullable && nulls == 0) p.mask.clear(); // still no NULL cell: still no mask
     }
   }
   // row ids: ascending beyond the table's last id; the dense continuation of a table with dense ids needs no image
   bool ids_dense = true;
+  uint64_t last_id = t->d_row_ids ? t->last_row_id : (t->total_rows ? t->local_logical_start + t->local_rows - 1 : 0);
   if (chunk_row_ids) {
-    uint64_t prev = t->d_row_ids ? t->last_row_id : (t->total_rows ? t->local_logical_start + t->local_rows - 1 : 0), at = t->local_logical_start + t->local_rows;
-    bool have = t->total_rows != 0;
-    for (uint32_t i = 0; i < n_new; ++i) {
-      if (chunk_rows[i] && !chunk_row_ids[i]) return set_error(LLKV_INVALID_ARGUMENT, "chunk row-id pointer is NULL");
-      for (uint64_t r = 0; r < chunk_rows[i]; ++r, ++at) {
-        const uint64_t id = chunk_row_ids[i][r];
-        if (have && id <= prev) return set_error(LLKV_INVALID_ARGUMENT, "row ids must ascend strictly beyond the table's last id");
-        prev = id; have = true;
-        ids_dense &= id == at;
-      }
-    }
+    if ((rc = walk_row_ids(run, chunk_row_ids, t->local_logical_start + t->local_rows, t->total_rows != 0, &last_id, &ids_dense, true))) return rc;
   } else if (t->d_row_ids) {
     return set_error(LLKV_INVALID_ARGUMENT, "the table has its own row ids: the appended chunks need theirs");
   }
-  const bool want_id_image = t->d_row_ids != nullptr || (chunk_row_ids && !ids_dense);
+  const bool ids_were_dense = !t->d_row_ids;
+  const bool want_id_image = !ids_were_dense || (chunk_row_ids && !ids_dense);
 
   // ---- device side: larger buffers first (all of them, or none), then the copies ---------------------------------------------
   HIP_TRY(hipDeviceSynchronize()); // executions launched over the old image have finished before a buffer moves
   hipStream_t s = g_ctx.stream;
-  const uint64_t need = new_dev_rows + kSlackRows;
-  std::vector<GrownBuffer> grown;
-  auto release_fresh = [&] { for (GrownBuffer &g : grown) if (g.fresh) (void)hipFree(g.fresh); };
-  auto want_room = [&](void **slot, uint64_t cap, uint32_t width, uint8_t fill) -> int {
-    if (cap >= need) return LLKV_OK;
-    GrownBuffer g{slot, nullptr, width, fill};
-    if (hipMalloc(&g.fresh, with_headroom(new_dev_rows) * width) != hipSuccess) { release_fresh(); return set_error(LLKV_INTERNAL, "device allocation failed while growing a column"); }
-    grown.push_back(g);
+  const uint64_t need = new_dev_rows + kSlackRows, grown_cap = with_headroom(new_dev_rows);
+  struct Grown {
+    DeviceBuffer *slot; // the buffer to replace
+    DeviceBuffer fresh;
+    uint32_t width;
+    uint8_t fill;
+  };
+  std::vector<Grown> grown; // (a refusal on the way frees the fresh buffers with it)
+  auto want_room = [&](DeviceBuffer &slot, uint32_t width, uint8_t fill) -> int {
+    if (slot.cap_rows() >= need) return LLKV_OK;
+    grown.push_back({&slot, DeviceBuffer(), width, fill});
+    if (grown.back().fresh.alloc(grown_cap, width) != hipSuccess) return set_error(LLKV_INTERNAL, "device allocation failed while growing a column");
     return LLKV_OK;
   };
   for (auto &kv : t->cols) {
     DeviceColumn &c = kv.second;
-    const uint32_t w = dtype_width(c.info.dtype);
-    const uint64_t cap = c.cap_rows ? c.cap_rows : old_dev_rows + kSlackRows;
-    if ((rc = want_room(&c.d_values, cap, w, 0))) return rc;
-    Prepared &p = prep[kv.first];
-    if (!p.mask.empty()) {
-      void **vslot = reinterpret_cast<void **>(&c.d_valid);
-      const uint64_t vcap = c.d_valid ? (c.valid_cap_rows ? c.valid_cap_rows : old_dev_rows + kSlackRows) : 0;
-      if ((rc = want_room(vslot, vcap, 1, 1))) return rc;
-    }
+    if ((rc = want_room(c.d_values, dtype_width(c.info.dtype), 0))) return rc;
+    if (!prep[kv.first].mask.empty() && (rc = want_room(c.d_valid, 1, 1))) return rc;
   }
-  void *ids_slot = t->d_row_ids;
-  if (want_id_image && (rc = want_room(&ids_slot, t->d_row_ids ? t->row_ids_cap : 0, 8, 0))) return rc;
-  for (GrownBuffer &g : grown) { // old rows move on the device; what lies behind them starts as `fill`
-    void *old = *g.slot;
-    const uint64_t cap_rows = with_headroom(new_dev_rows);
-    if (old) HIP_TRY(hipMemcpyAsync(g.fresh, old, old_dev_rows * g.width, hipMemcpyDeviceToDevice, s));
-    else if (g.fill) HIP_TRY(hipMemsetAsync(g.fresh, g.fill, old_dev_rows * g.width, s)); // a validity mask that did not exist: every old cell present
-    HIP_TRY(hipMemsetAsync((char *)g.fresh + old_dev_rows * g.width, 0, (cap_rows - old_dev_rows) * g.width, s));
+  if (want_id_image && (rc = want_room(t->d_row_ids, 8, 0))) return rc;
+  for (Grown &g : grown) { // old rows move on the device; what lies behind them starts as `fill`
+    if (*g.slot) HIP_TRY(hipMemcpyAsync(g.fresh.get(), g.slot->get(), old_dev_rows * g.width, hipMemcpyDeviceToDevice, s));
+    else if (g.fill) HIP_TRY(hipMemsetAsync(g.fresh.get(), g.fill, old_dev_rows * g.width, s)); // a validity mask that did not exist: every old cell present
+    HIP_TRY(hipMemsetAsync(g.fresh.get<char>() + old_dev_rows * g.width, 0, (grown_cap - old_dev_rows) * g.width, s));
   }
   HIP_TRY(hipStreamSynchronize(s));
-  for (GrownBuffer &g : grown) {
-    if (*g.slot && g.slot != &ids_slot) (void)hipFree(*g.slot);
-    *g.slot = g.fresh;
-  }
-  const uint64_t grown_cap = with_headroom(new_dev_rows);
-  for (auto &kv : t->cols) {
-    DeviceColumn &c = kv.second;
-    for (GrownBuffer &g : grown) {
-      if (g.slot == &c.d_values) c.cap_rows = grown_cap;
-      if (g.slot == reinterpret_cast<void **>(&c.d_valid)) c.valid_cap_rows = grown_cap;
-    }
-    if (!c.cap_rows) c.cap_rows = old_dev_rows + kSlackRows;
-  }
-  if (want_id_image) {
-    const bool moved = ids_slot != t->d_row_ids;
-    if (moved) {
-      if (t->d_row_ids) (void)hipFree(t->d_row_ids);
-      else HIP_TRY(hj_launch_iota_u64(static_cast<uint64_t *>(ids_slot), old_dev_rows, t->local_logical_start, s)); // dense until now (world = 1: no padding rows matter — ids of padding rows are never read)
-      t->d_row_ids = static_cast<uint64_t *>(ids_slot);
-      t->row_ids_cap = grown_cap;
-    }
-  }
+  for (Grown &g : grown) *g.slot = std::move(g.fresh);
+  if (want_id_image && ids_were_dense) // dense until now (world = 1: no padding rows matter — ids of padding rows are never read)
+    HIP_TRY(hj_launch_iota_u64(t->d_row_ids.get<uint64_t>(), old_dev_rows, t->local_logical_start, s));
   // the new chunks' bytes: the only host → HBM traffic of the append
   for (auto &kv : t->cols) {
     DeviceColumn &c = kv.second;
     Prepared &p = prep[kv.first];
     const uint32_t w = dtype_width(c.info.dtype);
+    char *image = c.d_values.get<char>() + old_dev_rows * w; // (the new chunks' rows)
     if (c.info.dtype == LLKV_DT_UTF8) {
-      if ((rc = stage_to_device({{(char *)c.d_values + old_dev_rows, p.codes.data(), (size_t)span}}))) return rc;
+      if ((rc = stage_from_pinned(image, p.codes.p, (size_t)span))) return rc;
       for (std::string &wd : p.new_words) c.info.dictionary.push_back(wd);
     } else if (c.info.dtype == LLKV_DT_DECIMAL128) {
-      if ((rc = stage_to_device({{(char *)c.d_values + old_dev_rows * 8, p.narrow.data(), (size_t)span * 8}}))) return rc;
+      if ((rc = stage_to_device({{image, p.narrow.data(), (size_t)span * 8}}))) return rc;
     } else {
-      size_t k = 0;
-      for (uint32_t i = 0; i < n_new; ++i) if (chunk_rows[i]) p.pieces[k++].d_dst = (char *)c.d_values + off[i] * w;
-      if ((rc = stage_to_device(p.pieces))) return rc;
+      std::vector<StagePiece> pieces;
+      if ((rc = fixed_width_pieces(run, by_field[kv.first]->values, w, image, &pieces)) || (rc = stage_to_device(pieces))) return rc;
     }
     if (!p.mask.empty()) {
-      if ((rc = stage_to_device({{c.d_valid + old_dev_rows, p.mask.data(), (size_t)span}}))) return rc;
+      if ((rc = stage_to_device({{c.d_valid.get<uint8_t>() + old_dev_rows, p.mask.data(), (size_t)span}}))) return rc;
       c.info.nullable = true;
     }
   }
   if (want_id_image) {
     std::vector<StagePiece> pieces;
-    for (uint32_t i = 0; i < n_new; ++i) if (chunk_rows[i]) pieces.push_back({(char *)t->d_row_ids + off[i] * 8, chunk_row_ids[i], (size_t)chunk_rows[i] * 8});
-    if ((rc = stage_to_device(pieces))) return rc;
+    if ((rc = fixed_width_pieces(run, reinterpret_cast<const void *const *>(chunk_row_ids), 8, t->d_row_ids.get<char>() + old_dev_rows * 8, &pieces)) ||
+        (rc = stage_to_device(pieces)))
+      return rc;
   }
-  if (chunk_row_ids) for (uint32_t i = n_new; i-- > 0;) if (chunk_rows[i]) { t->last_row_id = chunk_row_ids[i][chunk_rows[i] - 1]; break; }
+  if (chunk_row_ids && new_rows) t->last_row_id = last_id;
 
   // ---- the table is the grown one from here: layout, tile lists, statistics, generation --------------------------------------
   for (uint32_t i = 0; i < n_new; ++i) t->global_chunk_rows.push_back(chunk_rows[i]);
@@ -1023,9 +978,12 @@ static int append_chunks_impl(Table *t, const uint64_t *chunk_rows, uint32_t n_n
   if (t->n_local_chunks != old_chunks + n_new || t->dev_rows != new_dev_rows) return set_error(LLKV_INTERNAL, "append: the layout disagrees with the table's");
   {
     std::lock_guard<std::mutex> lk(t->mu);
-    for (auto &kv : t->tilesets) { if (kv.second.d_tiles) t->retired.push_back(kv.second.d_tiles); if (kv.second.d_sample) t->retired.push_back(kv.second.d_sample); }
+    for (auto &kv : t->tilesets) {
+      if (kv.second.d_tiles) t->retired.push_back(std::move(kv.second.d_tiles));
+      if (kv.second.d_sample) t->retired.push_back(std::move(kv.second.d_sample));
+    }
     t->tilesets.clear();
-    for (auto &kv : t->key_images) if (kv.second.d) t->retired.push_back(kv.second.d);
+    for (auto &kv : t->key_images) if (kv.second.d) t->retired.push_back(std::move(kv.second.d));
     t->key_images.clear();
   }
   for (auto &kv : t->cols) {
@@ -1065,10 +1023,9 @@ llkv_status llkv_hip_table_adopt_device_column(llkv_hip_table *table, uint32_t f
   c.info.field_id = field_id;
   c.info.dtype = dtype;
   c.info.rows = t->total_rows;
-  c.owned = true;
   // the adopted buffer has no slack past its end; keep an owned image with slack instead
-  if ((rc = alloc_column(*t, w, &c.d_values))) return (llkv_status)rc;
-  if (hipMemcpyAsync(c.d_values, device_values, t->dev_rows * w, hipMemcpyDeviceToDevice, g_ctx.stream) != hipSuccess ||
+  if ((rc = alloc_column(*t, w, c.d_values))) return (llkv_status)rc;
+  if (hipMemcpyAsync(c.d_values.get(), device_values, t->dev_rows * w, hipMemcpyDeviceToDevice, g_ctx.stream) != hipSuccess ||
       hipStreamSynchronize(g_ctx.stream) != hipSuccess)
     return (llkv_status)set_error(LLKV_INTERNAL, "device copy failed");
   if ((rc = column_stats_device(*t, c))) return (llkv_status)rc;
