@@ -537,6 +537,35 @@ llkv_status llkv_hip_query_partial_groups(const llkv_hip_query *query, uint64_t 
 llkv_status llkv_hip_query_merge_groups(llkv_hip_query *query, uint32_t world, const uint64_t *rank_groups,
                                         const int64_t *const *key_values, const uint8_t *const *key_valid,
                                         const uint64_t *const *lanes);
+
+/* ORDER BY <output column> [DESC] [NULLS FIRST|LAST] … then OFFSET / LIMIT over the groups of a prepared GROUP BY —
+ * sort_record_batch_with_order llkv-executor/src/lib.rs:13762-13868 (called for GROUP BY at :4388 and :5347) and the
+ * offset / limit of SelectExecution::stream :10918-10955.  Terms compare the finalized cells the query returns, as arrow's
+ * lexsort does: integers, Date32 and Boolean numerically, Utf8 by their bytes, Decimal128 by value, Float64 by
+ * f64::total_cmp; NULLs first or last per term, whatever `descending` says.  Ties keep the group's position in the
+ * unordered output (first appearance, or key order with `order_by_keys`), so the result is the same for any rank count.
+ * The sort-based and partitioned routes order on the device (a top-k of offset + limit ≤ 1024 groups, only those rows are
+ * copied out); the dense routes, larger limits and terms without a bit-exact device form order on the host.  The route
+ * note says which: "; order: device top-k" or "; order: host (<reason>)".
+ * Takes effect from the next finish / collect / finish_from_host / merge_groups; num_groups / group_key / value then read
+ * the ordered, trimmed rows.  n_order = 0 with a limit = LIMIT without ORDER BY; n_order = 0, offset = 0,
+ * limit = UINT64_MAX clears it.  LLKV_INVALID_ARGUMENT for an index out of range ("ORDER BY position … is out of
+ * bounds"), an ungrouped query, a join → GROUP BY query (llkv_hip_join_groupby_rows orders those) and executions in
+ * flight.  A sharded table orders after the exchange: finish → partial_groups → all-gather → set_group_order →
+ * merge_groups (a group can straddle ranks); partial_groups refuses a query with an order set.                      */
+typedef enum llkv_group_order_kind {
+  LLKV_GROUP_ORDER_KEY = 0,      /* index = position in key_fields */
+  LLKV_GROUP_ORDER_AGGREGATE = 1 /* index = position in aggs       */
+} llkv_group_order_kind;
+typedef struct llkv_group_order_key {
+  int32_t kind; /* llkv_group_order_kind */
+  uint32_t index;
+  int32_t descending;
+  int32_t nulls_first;
+} llkv_group_order_key;
+llkv_status llkv_hip_query_set_group_order(llkv_hip_query *query, const llkv_group_order_key *order, uint32_t n_order,
+                                           uint64_t offset, uint64_t limit /* UINT64_MAX = no limit */);
+uint64_t llkv_hip_query_total_groups(const llkv_hip_query *query); /* groups of the last finish before OFFSET / LIMIT */
 /* Status a finalize step produced for one aggregate (e.g. "integer overflow"
  * is LLKV_INVALID_ARGUMENT, llkv-aggregate/src/lib.rs:816-829).              */
 

@@ -167,6 +167,35 @@ class CJoinOrderKey(C.Structure):
 JOIN_ORDER_AGGREGATE, JOIN_ORDER_PAYLOAD, JOIN_ORDER_KEY = 0, 1, 2
 
 
+class CGroupOrderKey(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("index", C.c_uint32), ("descending", C.c_int32), ("nulls_first", C.c_int32)]
+
+
+GROUP_ORDER_KEY, GROUP_ORDER_AGGREGATE = 0, 1
+
+
+@dataclass(frozen=True)
+class GroupOrder:
+    """One ORDER BY term over the output columns of a GROUP BY (llkv_group_order_key): a key (position in the keys) or an
+    aggregate (position in the aggregates); NULLs first or last whatever the direction (the planner's default is the
+    caller's to pass)."""
+    kind: int
+    index: int
+    descending: bool = False
+    nulls_first: bool = False
+
+    @staticmethod
+    def key(index: int, descending: bool = False, nulls_first: bool = False) -> "GroupOrder":
+        return GroupOrder(GROUP_ORDER_KEY, index, descending, nulls_first)
+
+    @staticmethod
+    def agg(index: int, descending: bool = False, nulls_first: bool = False) -> "GroupOrder":
+        return GroupOrder(GROUP_ORDER_AGGREGATE, index, descending, nulls_first)
+
+    def to_c(self) -> CGroupOrderKey:
+        return CGroupOrderKey(self.kind, self.index, int(bool(self.descending)), int(bool(self.nulls_first)))
+
+
 class CColumnDesc(C.Structure):
     _fields_ = [("field_id", C.c_uint32), ("dtype", C.c_int32), ("rows", C.c_uint64), ("has_stats", C.c_int32),
                 ("min_i", C.c_int64), ("max_i", C.c_int64), ("dict_size", C.c_uint32),

@@ -215,7 +215,8 @@ static int finish_sharded(Query *q, hipStream_t stream) {
       ln[r] = reinterpret_cast<const uint64_t *>(b + 24 + nk * h[0] * 8);
       kva[r] = b + 24 + nk * h[0] * 8 + h[0] * k * 8;
     }
-    return sorted_groupby_merge(q->sorted, world, counts.data(), kv.data(), kva.data(), ln.data(), &q->lazy);
+    if ((rc = sorted_groupby_merge(q->sorted, world, counts.data(), kv.data(), kva.data(), ln.data(), &q->lazy))) return rc;
+    return q->apply_merged_order();
   }
   while (q->n_submitted < q->n_launched) {
     if ((rc = q->all_reduce(stream)) || (rc = q->submit(stream))) return rc;

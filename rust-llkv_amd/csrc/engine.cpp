@@ -340,7 +340,14 @@ int Query::launch(hipStream_t stream) {
     return set_error(LLKV_INVALID_ARGUMENT, "the table was appended to after this query was prepared (its buffers, statistics and tile lists have changed): prepare it again");
   if (sorted) { // the sort-based route runs to completion here; submit / collect only hand the result over
     if (n_launched != n_collected) return set_error(LLKV_INVALID_ARGUMENT, "a sort-based GROUP BY keeps one execution in flight");
-    const int rc = sorted_groupby_run(sorted, &lazy);
+    // (a sharded table orders the merged groups: llkv_hip_query_merge_groups / finish_sharded)
+    const bool local_order = order.active() && table->world == 1;
+    row_mapped = false;
+    row_map.clear();
+    GroupOrderDone done;
+    int rc = sorted_groupby_run(sorted, &lazy, local_order ? &order : nullptr, &done);
+    if (!rc && local_order) rc = apply_order(&done);
+    else if (!rc) { row_mapped = false; row_map.clear(); order_note.clear(); total_groups = lazy.n; }
     if (rc) return rc;
     n_launched++;
     return LLKV_OK;
@@ -900,6 +907,8 @@ int Query::finish_from_exchange(const uint64_t *exchange) {
   else fold_exchange_host(exchange, p.lane_ops.data(), (uint32_t)p.lanes, state.data());
   mark("fold");
   groups.reset(0, 0, 0);
+  row_mapped = false;
+  row_map.clear();
   if (state[(size_t)p.ng * p.k] != 0) // checked arithmetic failed on a selected row
     return set_error(LLKV_INTERNAL, arith_error_message(state[(size_t)p.ng * p.k]));
   const int base = p.track_first ? 2 : 1;
@@ -982,6 +991,68 @@ int Query::finish_from_exchange(const uint64_t *exchange) {
         if (distinct[a].kind >= 0 && table->world == 1) { int rc = distinct_value(a, &groups.value(at, a)); if (rc) return rc; } // sharded: merge_distinct
   }
   mark("groups");
+  return apply_order(nullptr);
+}
+
+// The order of llkv_hip_query_set_group_order over the result of the latest finish: the device top-k already left only the
+// returned rows (`done->device`); otherwise the rows are sorted here and read through row_map.  done = nullptr: a dense route.
+int Query::apply_order(const GroupOrderDone *done) {
+  row_mapped = false;
+  row_map.clear();
+  order_note.clear();
+  total_groups = result_rows();
+  if (!order.active() || !plan_grouped()) return LLKV_OK;
+  if (done && done->device) {
+    total_groups = done->total;
+    order_note = "; order: device top-k";
+    return LLKV_OK;
+  }
+  const int rc = group_order_host(order, total_groups, [&](uint64_t r, const llkv_group_order_key &t, llkv_value *v) {
+    return t.kind == LLKV_GROUP_ORDER_KEY ? cell_key(r, t.index, v) : cell_value(r, t.index, v);
+  }, &row_map);
+  if (rc) { row_map.clear(); return rc; }
+  row_mapped = true;
+  order_note = "; order: host (" + (!done ? std::string("dense route") : done->why_host.empty() ? std::string("no groups") : done->why_host) + ")";
+  return LLKV_OK;
+}
+
+// One cell of the result before the order (row = its position in the unordered output).
+int Query::cell_key(uint64_t group, uint32_t key, llkv_value *out) const {
+  if (lazy.active) { // sort-based route: decode the cell on request
+    const LazyGroups &lz = lazy;
+    if (group >= lz.n || key >= lz.n_keys) return set_error(LLKV_INVALID_ARGUMENT, "group/key index out of range");
+    std::memset(out, 0, sizeof *out);
+    const ColumnInfo *ci = lz.key_cols[key];
+    const int64_t v = lz.key_vals[(size_t)key * lz.n + group];
+    out->is_null = lz.key_valid[(size_t)key * lz.n + group] ? 0 : 1;
+    if (ci->dtype == LLKV_DT_UTF8) {
+      out->dtype = LLKV_DT_UTF8;
+      out->str = (!out->is_null && (uint64_t)v < ci->dictionary.size()) ? ci->dictionary[(size_t)v].c_str() : "";
+    } else {
+      out->dtype = LLKV_DT_INT64;
+      out->i64 = out->is_null ? 0 : v;
+    }
+    return LLKV_OK;
+  }
+  if (group >= groups.size() || key >= groups.n_keys) return set_error(LLKV_INVALID_ARGUMENT, "group/key index out of range");
+  std::memset(out, 0, sizeof *out);
+  const GroupKey &gk = groups.key(group, key);
+  if (gk.is_int) { out->dtype = LLKV_DT_INT64; out->i64 = gk.i; }
+  else { out->dtype = LLKV_DT_UTF8; out->str = gk.s.c_str(); }
+  out->is_null = gk.is_null ? 1 : 0;
+  return LLKV_OK;
+}
+
+int Query::cell_value(uint64_t group, uint32_t agg, llkv_value *out) const {
+  if (lazy.active) {
+    const LazyGroups &lz = lazy;
+    if (group >= lz.n || agg >= lz.plan->aggs.size()) return set_error(LLKV_INVALID_ARGUMENT, "group/aggregate index out of range");
+    std::string err;
+    const int rc = finalize_value(lz.plan->aggs[agg], lz.lanes + (size_t)group * lz.k, 2, out, &err, false);
+    return rc ? set_error(rc, err) : LLKV_OK;
+  }
+  if (group >= groups.size() || agg >= groups.n_values) return set_error(LLKV_INVALID_ARGUMENT, "group/aggregate index out of range");
+  *out = groups.value(group, agg);
   return LLKV_OK;
 }
 
@@ -1199,6 +1270,7 @@ llkv_status llkv_hip_query_collect(llkv_hip_query *query) {
 uint32_t llkv_hip_query_num_groups(const llkv_hip_query *query) {
   if (!query) return 0;
   const Query *q = reinterpret_cast<const Query *>(query);
+  if (q->row_mapped) return (uint32_t)q->row_map.size();
   return q->lazy.active ? (uint32_t)q->lazy.n : (uint32_t)q->groups.size();
 }
 uint32_t llkv_hip_query_num_keys(const llkv_hip_query *query) { return query ? (uint32_t) reinterpret_cast<const Query *>(query)->n_user_keys : 0; }
@@ -1206,51 +1278,51 @@ uint32_t llkv_hip_query_num_aggregates(const llkv_hip_query *query) { return que
 
 llkv_status llkv_hip_query_group_key(const llkv_hip_query *query, uint32_t group, uint32_t key, llkv_value *out) {
   const Query *q = reinterpret_cast<const Query *>(query);
-  if (q && out && q->lazy.active) { // sort-based route: decode the cell on request
-    const LazyGroups &lz = q->lazy;
-    if (group >= lz.n || key >= lz.n_keys) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/key index out of range");
-    std::memset(out, 0, sizeof *out);
-    const ColumnInfo *ci = lz.key_cols[key];
-    const int64_t v = lz.key_vals[(size_t)key * lz.n + group];
-    out->is_null = lz.key_valid[(size_t)key * lz.n + group] ? 0 : 1;
-    if (ci->dtype == LLKV_DT_UTF8) {
-      out->dtype = LLKV_DT_UTF8;
-      out->str = (!out->is_null && (uint64_t)v < ci->dictionary.size()) ? ci->dictionary[(size_t)v].c_str() : "";
-    } else {
-      out->dtype = LLKV_DT_INT64;
-      out->i64 = out->is_null ? 0 : v;
-    }
-    return LLKV_OK;
-  }
-  if (!q || !out || group >= q->groups.size() || key >= q->groups.n_keys)
-    return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/key index out of range");
-  std::memset(out, 0, sizeof *out);
-  const GroupKey &gk = q->groups.key(group, key);
-  if (gk.is_int) { out->dtype = LLKV_DT_INT64; out->i64 = gk.i; }
-  else { out->dtype = LLKV_DT_UTF8; out->str = gk.s.c_str(); }
-  out->is_null = gk.is_null ? 1 : 0;
-  return LLKV_OK;
+  if (!q || !out) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/key index out of range");
+  if (q->row_mapped && group >= q->row_map.size()) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/key index out of range");
+  return (llkv_status)q->cell_key(q->row_mapped ? q->row_map[group] : group, key, out);
 }
 
 llkv_status llkv_hip_query_value(const llkv_hip_query *query, uint32_t group, uint32_t agg, llkv_value *out) {
   const Query *q = reinterpret_cast<const Query *>(query);
-  if (q && out && q->lazy.active) {
-    const LazyGroups &lz = q->lazy;
-    if (group >= lz.n || agg >= lz.plan->aggs.size()) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/aggregate index out of range");
-    std::string err;
-    const int rc = finalize_value(lz.plan->aggs[agg], lz.lanes + (size_t)group * lz.k, 2, out, &err, false);
-    return rc ? (llkv_status)set_error(rc, err) : LLKV_OK;
+  if (!q || !out) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/aggregate index out of range");
+  if (q->row_mapped && group >= q->row_map.size()) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/aggregate index out of range");
+  return (llkv_status)q->cell_value(q->row_mapped ? q->row_map[group] : group, agg, out);
+}
+
+llkv_status llkv_hip_query_set_group_order(llkv_hip_query *query, const llkv_group_order_key *order, uint32_t n_order, uint64_t offset, uint64_t limit) {
+  Query *q = reinterpret_cast<Query *>(query);
+  if (!q) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "query is NULL");
+  if (n_order && !order) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "order is NULL");
+  if (q->join_state) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "a join → GROUP BY query is ordered by llkv_hip_join_groupby_rows");
+  if (!q->plan_grouped()) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "ORDER BY over groups needs a GROUP BY query (this one is ungrouped)");
+  if (q->n_launched != q->n_collected) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "executions in flight");
+  const uint32_t n_cols = q->n_user_keys + q->n_user_aggs;
+  for (uint32_t i = 0; i < n_order; ++i) {
+    const llkv_group_order_key &k = order[i];
+    if (k.kind != LLKV_GROUP_ORDER_KEY && k.kind != LLKV_GROUP_ORDER_AGGREGATE)
+      return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "ORDER BY term " + std::to_string(i) + ": unknown kind " + std::to_string(k.kind));
+    const uint64_t position = (k.kind == LLKV_GROUP_ORDER_KEY ? 0ull : (uint64_t)q->n_user_keys) + k.index;
+    if ((k.kind == LLKV_GROUP_ORDER_KEY && k.index >= q->n_user_keys) || (k.kind == LLKV_GROUP_ORDER_AGGREGATE && k.index >= q->n_user_aggs))
+      return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "ORDER BY position " + std::to_string(position + 1) + " is out of bounds for " + std::to_string(n_cols) + " columns");
   }
-  if (!q || !out || group >= q->groups.size() || agg >= q->groups.n_values)
-    return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/aggregate index out of range");
-  *out = q->groups.value(group, agg);
+  q->order.terms.assign(order, order + n_order);
+  q->order.offset = offset;
+  q->order.limit = limit;
   return LLKV_OK;
+}
+
+uint64_t llkv_hip_query_total_groups(const llkv_hip_query *query) {
+  const Query *q = reinterpret_cast<const Query *>(query);
+  return q ? q->total_groups : 0;
 }
 
 llkv_status llkv_hip_query_partial_groups(const llkv_hip_query *query, uint64_t *n_groups, uint32_t *n_keys, uint32_t *lanes_per_group,
                                           const int64_t **key_values, const uint8_t **key_valid, const uint64_t **lanes) {
   const Query *q = reinterpret_cast<const Query *>(query);
   if (!q || !q->sorted || !q->lazy.active) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "not a finished sort-based GROUP BY");
+  if (q->order.active())
+    return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "partial groups of a query with an ORDER BY / LIMIT: order the merged groups (set_group_order before merge_groups)");
   if (n_groups) *n_groups = q->lazy.n;
   if (n_keys) *n_keys = q->lazy.n_keys;
   if (lanes_per_group) *lanes_per_group = (uint32_t)q->lazy.k;
@@ -1265,7 +1337,9 @@ llkv_status llkv_hip_query_merge_groups(llkv_hip_query *query, uint32_t world, c
   Query *q = reinterpret_cast<Query *>(query);
   if (!q || !q->sorted || !q->lazy.active) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "not a finished sort-based GROUP BY");
   if (world == 0 || !rank_groups || !key_values || !key_valid || !lanes) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "NULL argument");
-  return (llkv_status)sorted_groupby_merge(q->sorted, world, rank_groups, key_values, key_valid, lanes, &q->lazy);
+  int rc = sorted_groupby_merge(q->sorted, world, rank_groups, key_values, key_valid, lanes, &q->lazy);
+  if (!rc) rc = q->apply_merged_order();
+  return (llkv_status)rc;
 }
 
 llkv_status llkv_hip_query_distinct_partial(llkv_hip_query *query, uint32_t agg, const uint64_t **values, uint64_t *n_values) {
@@ -1316,8 +1390,13 @@ uint64_t llkv_hip_query_algorithmic_bytes(const llkv_hip_query *query) {
 const char *llkv_hip_query_route_note(const llkv_hip_query *query) {
   const Query *q = reinterpret_cast<const Query *>(query);
   if (!q) return "";
-  if (!q->route_note.empty()) return q->route_note.c_str();
-  return q->plan.acc_lds ? "GROUP BY with per-thread accumulator columns in LDS" : q->plan.grouped ? "GROUP BY with register accumulators" : "ungrouped aggregates, register accumulators";
+  const char *base = !q->route_note.empty() ? q->route_note.c_str()
+                     : q->plan.acc_lds      ? "GROUP BY with per-thread accumulator columns in LDS"
+                     : q->plan.grouped      ? "GROUP BY with register accumulators"
+                                            : "ungrouped aggregates, register accumulators";
+  if (q->order_note.empty()) return base;
+  q->note_buf = std::string(base) + q->order_note;
+  return q->note_buf.c_str();
 }
 
 const char *llkv_hip_query_kernel_signature(const llkv_hip_query *query) {

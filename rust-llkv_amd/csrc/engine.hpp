@@ -8,6 +8,7 @@
 #include "plan.hpp"
 #include "scan_params.h"
 
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -200,6 +201,40 @@ struct LazyGroups {
 
 struct Scratch;
 
+// ORDER BY output columns, then OFFSET / LIMIT, over the groups of a GROUP BY (llkv_hip_query_set_group_order; group_order.hip).
+// sort_record_batch_with_order llkv-executor/src/lib.rs:13762-13868 and SelectExecution::stream :10918-10955: arrow's lexsort
+// over the finalized cells; ties keep the group's position in the unordered output.
+constexpr uint64_t kGroupOrderDeviceRows = 1024; // offset + limit the device top-k serves (its survivors are ranked in LDS tiles)
+struct GroupOrderSpec {
+  std::vector<llkv_group_order_key> terms;
+  uint64_t offset = 0, limit = UINT64_MAX;
+  bool active() const { return !terms.empty() || offset != 0 || limit != UINT64_MAX; }
+  uint64_t end(uint64_t n) const { // rows [offset, end) of the ordered groups are returned
+    const uint64_t e = limit > UINT64_MAX - offset ? UINT64_MAX : offset + limit;
+    return e < n ? e : n;
+  }
+};
+// What a sort-based / partitioned run did with the order: the device top-k left only the returned rows, in order, in its
+// LazyGroups (`device`), or it copied out every group and `why_host` says why (the caller sorts them on the host).
+struct GroupOrderDone {
+  bool device = false;
+  uint64_t total = 0; // groups before OFFSET / LIMIT
+  std::string why_host;
+};
+// Whether every term has a bit-exact device twin of its host finalize and the rows fit the device bound (else *why).
+bool group_order_device_ok(const GroupOrderSpec &o, const LazyGroups &lz, std::string *why);
+// Device top-k over `n` groups in unordered output order ([n][k] lanes, [n_keys][n] key cells and validity in HBM): error-flag
+// reduction of the aggregates whose finalize can fail (the host's message for the first failing group), order-key images, exact
+// radix select of the first end(n) groups, rank of the survivors, gather of rows [offset, end) into the pinned buffers (grown
+// with pinned_reserve).  *n_out = rows returned.
+int group_order_device(const GroupOrderSpec &o, const LazyGroups &lz, const uint64_t *d_lanes, const int64_t *d_kv, const uint8_t *d_kvalid,
+                       uint64_t n, hipStream_t s, void **h_lanes, size_t *cap_lanes, void **h_kv, size_t *cap_kv, void **h_kvalid, size_t *cap_kvalid,
+                       uint64_t *n_out);
+// Host order: the rows [offset, end) of `n` rows, ordered; cell(row, term, &v) yields the finalized cell of a term (an error
+// status ends the sort with it).
+int group_order_host(const GroupOrderSpec &o, uint64_t n, const std::function<int(uint64_t, const llkv_group_order_key &, llkv_value *)> &cell,
+                     std::vector<uint64_t> *rows);
+
 // Message of a device-side arithmetic error code (fused_scan.hip.h: kErrOverflow = 1, kErrDivZero = 2), as the
 // reference's arrow kernels word it (Error::Internal).
 inline const char *arith_error_message(uint64_t code) {
@@ -210,7 +245,7 @@ inline const char *arith_error_message(uint64_t code) {
 struct PartGroupBy;
 int part_groupby_prepare(const Table *table, const llkv_filter *filters, uint32_t n_filters, const llkv_eval_op *ops, uint32_t n_ops,
                          const uint32_t *key_fields, uint32_t n_keys, const llkv_aggregate_spec *aggs, uint32_t n_aggs, bool order_by_keys, PartGroupBy **out);
-int part_groupby_run(PartGroupBy *p, LazyGroups *out);
+int part_groupby_run(PartGroupBy *p, LazyGroups *out, const GroupOrderSpec *order = nullptr, GroupOrderDone *done = nullptr);
 void part_groupby_free(PartGroupBy *p);
 const LoweredPlan *part_groupby_plan(const PartGroupBy *p);
 
@@ -225,7 +260,7 @@ struct KeySetView;
 int sorted_groupby_prepare(const Table *table, const llkv_filter *filters, uint32_t n_filters, const llkv_eval_op *ops, uint32_t n_ops,
                            const uint32_t *key_fields, uint32_t n_keys, const llkv_aggregate_spec *aggs, uint32_t n_aggs,
                            bool order_by_keys, SortedGroupBy **out, const KeySetView *key_set = nullptr, uint32_t key_set_field = 0);
-int sorted_groupby_run(SortedGroupBy *s, LazyGroups *out);
+int sorted_groupby_run(SortedGroupBy *s, LazyGroups *out, const GroupOrderSpec *order = nullptr, GroupOrderDone *done = nullptr);
 void sorted_groupby_free(SortedGroupBy *s);
 // Sharded table: the ranks' partial groups ([n_keys][n] key cells and validity, [n][k] lanes per rank, rank order)
 // become the table-wide groups of `out` (group_sort.cpp).
@@ -270,6 +305,20 @@ struct Query {
   bool order_by_keys = false;
   uint32_t n_user_aggs = 0, n_user_keys = 0;
   GroupStore groups;
+  // ORDER BY / OFFSET / LIMIT over the groups (llkv_hip_query_set_group_order): applied by the device top-k of the sort-based and
+  // partitioned routes, or on the host — then output row i reads the result's row row_map[i]
+  GroupOrderSpec order;
+  bool row_mapped = false;
+  std::vector<uint64_t> row_map;
+  uint64_t total_groups = 0;
+  std::string order_note;           // "; order: …" — which path served the order at the last finish
+  mutable std::string note_buf;     // route_note + order_note
+  uint64_t result_rows() const { return lazy.active ? lazy.n : groups.size(); } // before the order
+  int apply_order(const GroupOrderDone *done);
+  int apply_merged_order() { GroupOrderDone d; d.why_host = "merged groups"; return apply_order(&d); } // a sharded table's groups after the merge
+  bool plan_grouped() const { return sorted != nullptr || plan.grouped; }
+  int cell_key(uint64_t group, uint32_t key, llkv_value *out) const;     // the result before the order
+  int cell_value(uint64_t group, uint32_t agg, llkv_value *out) const;
   // ungrouped SUM/AVG(Int64) without overflow-excluding statistics: plan that emits the argument values of
   // the selected rows in row order, for the exact prefix-overflow check (index = aggregate, empty = n/a)
   std::vector<LoweredPlan> exact_plans;

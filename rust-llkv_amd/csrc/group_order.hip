@@ -1,0 +1,607 @@
+// group_order.hip — ORDER BY output columns, then OFFSET / LIMIT, over the groups of a GROUP BY
+// (sort_record_batch_with_order llkv-executor/src/lib.rs:13762-13868, SelectExecution::stream :10918-10955).
+//
+// Device top-k (sort-based and partitioned routes, offset + limit ≤ kGroupOrderDeviceRows), over the groups the route left in
+// HBM in their unordered output order ([n][k] lanes, [n_keys][n] key cells and validity):
+//   order keys   order_key_kernel    per group and term: a NULL word (0 / 1 by NULLS FIRST / LAST) and one or two value words,
+//                                    an order-preserving unsigned image of the cell the host finalize returns (i64: sign bit
+//                                    flipped, f64: the total_cmp flip, Decimal128: two words, Utf8: rank of the dictionary
+//                                    code; DESC: complemented).  The same pass records, per aggregate whose finalize can fail
+//                                    (i64 SUM / AVG), the first group that fails — the host then finalizes that one group for
+//                                    the status and message of the unordered query.
+//   select       order_radix_pass    exact radix select of the first m = offset + limit groups over the composite key (the
+//                                    words, then the position = the tie break): one 8-bit digit per launch, a histogram of the
+//                                    groups still tied with the threshold; the last workgroup to arrive picks the digit and
+//                                    moves the threshold (no workgroup waits for another).  Words whose upper bytes are known
+//                                    to be zero (NULL words, positions) skip those digits; once the tied groups are exactly
+//                                    the ones still needed the remaining launches return at once.
+//                order_select_kernel the m groups at or below the threshold
+//   rank         order_rank_kernel   each survivor counts the survivors below it (LDS tiles of 128): its output position
+//   gather       order_gather_kernel rows [offset, m) in order → copied out (only those)
+// Host order (group_order_host): the same images from the finalized cells, std::partial_sort — the dense routes, the merged
+// groups of a sharded table, larger limits and terms without a device form (a computed DECIMAL argument's precision check).
+#include "engine.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+namespace llkv {
+
+int finalize_value(const AggOut &a, const uint64_t *g, int base, llkv_value *out, std::string *err, bool prefixes_checked);
+
+namespace {
+
+typedef __int128 i128;
+typedef unsigned __int128 u128;
+
+constexpr int kMaxTerms = 8;
+constexpr int kMaxWords = 16;   // order-key words of the terms (a term: its NULL word and one or two value words)
+constexpr int kMaxErrAggs = 16; // aggregates whose finalize can fail
+constexpr uint32_t kOrderBlock = 256;
+
+enum TermKind : int32_t { kTermKeyInt = 0, kTermKeyUtf8 = 1, kTermAgg = 2 };
+
+struct OrderTerm {
+  int32_t kind, key;        // key terms: the key's index
+  int32_t fin;              // aggregate terms: AggFinal
+  int32_t lane, count_lane; // relative to the group's aggregate lanes (after rows and first row id)
+  int32_t word;             // first key word of the term
+  int32_t desc, nulls_first;
+  int32_t typed_by_first_value, fast_sum, wide, plain_minmax, null_without_values, fixed_point, fixed_exp, exact_levels, wide_delta;
+  uint64_t wide_base_hi, wide_base_lo;
+  const uint32_t *rank; // Utf8 keys: dictionary code → position in byte order
+};
+
+struct OrderParams {
+  const uint64_t *lanes;
+  const int64_t *kv;
+  const uint8_t *kvalid;
+  uint64_t n;
+  int32_t k, n_terms, n_words, n_err;
+  uint64_t *keys;                // [n_words][n]
+  unsigned long long *first_bad; // [n_err]: smallest group whose finalize of that aggregate fails
+  int32_t err_lane[kMaxErrAggs], err_count_lane[kMaxErrAggs];
+  OrderTerm t[kMaxTerms];
+};
+
+// Threshold of the radix select: the composite keys (words 0 … n_words − 1, then the position) whose bits under `mask` equal
+// `prefix` are still tied with it; `need` of them are still to be taken.
+struct SelectState {
+  unsigned long long need;
+  uint32_t done, pad;
+  unsigned long long prefix[kMaxWords + 1], mask[kMaxWords + 1];
+};
+
+__device__ inline double as_f64(uint64_t b) { return __longlong_as_double((long long)b); }
+__device__ inline uint64_t as_u64(double d) { return (uint64_t)__double_as_longlong(d); }
+__device__ inline uint64_t i64_image(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }
+__device__ inline uint64_t f64_image(uint64_t b) { return (b >> 63) ? ~b : (b | 0x8000000000000000ull); } // f64::total_cmp
+
+// The host's (x86-64 SSE2) NaN results, so that a NaN orders where the host's would: an operand NaN comes back quieted, the
+// first one first; an invalid operation yields the default NaN, sign bit set.
+constexpr uint64_t kQuiet = 0x0008000000000000ull;
+__device__ inline double host_add(double a, double b) {
+  if (__builtin_isnan(a)) return as_f64(as_u64(a) | kQuiet);
+  if (__builtin_isnan(b)) return as_f64(as_u64(b) | kQuiet);
+  const double r = a + b;
+  return __builtin_isnan(r) ? as_f64(0xFFF8000000000000ull) : r;
+}
+__device__ inline double host_div_rows(double a, int64_t rows) { // rows > 0
+  if (__builtin_isnan(a)) return as_f64(as_u64(a) | kQuiet);
+  return a / (double)rows;
+}
+
+// (double) of an i128, rounded to nearest even like the host's conversion
+__device__ double i128_to_f64(i128 v) {
+  const bool neg = v < 0;
+  const u128 m = neg ? (u128)0 - (u128)v : (u128)v;
+  const uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
+  if (!hi && !(lo >> 53)) { const double r = (double)lo; return neg ? -r : r; } // exact
+  const int msb = hi ? 127 - __builtin_clzll(hi) : 63 - __builtin_clzll(lo);
+  const int sh = msb - 52; // keep 53 bits
+  u128 q = m >> sh;
+  const u128 rem = m & (((u128)1 << sh) - 1), half = (u128)1 << (sh - 1);
+  if (rem > half || (rem == half && (q & 1))) q += 1; // (a carry to 2^53 is still exact)
+  const double r = ldexp((double)(uint64_t)q, sh);
+  return neg ? -r : r;
+}
+
+// |m| / d and its remainder (d > 0): AVG over Decimal128
+__device__ void udiv128(u128 m, uint64_t d, u128 *q, uint64_t *r) {
+  if (!(uint64_t)(m >> 64)) { *q = (uint64_t)m / d; *r = (uint64_t)m % d; return; }
+  u128 quo = 0, rem = 0;
+  for (int i = 127; i >= 0; --i) {
+    rem = (rem << 1) | ((m >> i) & 1);
+    if (rem >= d) { rem -= d; quo |= (u128)1 << i; }
+  }
+  *q = quo;
+  *r = (uint64_t)rem;
+}
+
+__device__ inline i128 exact_total(const uint64_t *l) { return ((i128)(int64_t)l[1] << 32) + (i128)(u128)l[0]; }
+
+// finalize_value (engine.cpp) of one aggregate, as an image: *null, or the value's words (one, two for Decimal128)
+__device__ void agg_image(const OrderTerm &t, const uint64_t *g, bool *null, uint64_t *w0, uint64_t *w1) {
+  const int64_t rows = t.count_lane >= 0 ? (int64_t)g[2 + t.count_lane] : (int64_t)g[0];
+  const uint64_t *l = g + 2 + (t.lane >= 0 ? t.lane : 0);
+  const AggFinal fin = (AggFinal)t.fin;
+  *null = false;
+  *w0 = *w1 = 0;
+  if (t.typed_by_first_value && rows == 0 &&
+      (fin == AggFinal::SumF64 || fin == AggFinal::MinF64 || fin == AggFinal::MaxF64 || fin == AggFinal::SumDec || fin == AggFinal::MinDec || fin == AggFinal::MaxDec)) {
+    *null = true;
+    return;
+  }
+  auto f64_sum = [&]() -> double {
+    if (t.fixed_point) return ldexp(i128_to_f64(exact_total(l)), t.fixed_exp);
+    if (t.exact_levels <= 1) return as_f64(l[0]);
+    double v = as_f64(l[t.exact_levels - 1]);
+    for (int j = t.exact_levels - 2; j >= 0; --j) v = host_add(v, as_f64(l[j]));
+    return v;
+  };
+  auto dec = [&](i128 v) {
+    *w0 = (uint64_t)(v >> 64) ^ 0x8000000000000000ull;
+    *w1 = (uint64_t)v;
+  };
+  switch (fin) {
+  case AggFinal::MinDec: case AggFinal::MaxDec: {
+    if (rows == 0) { *null = true; return; }
+    if (t.wide_delta) {
+      const i128 base = (i128)(((u128)t.wide_base_hi << 64) | t.wide_base_lo);
+      dec(t.wide_delta == 1 ? base + (i128)(u128)l[0] : base - (i128)(u128)l[0]);
+    } else dec((i128)(int64_t)l[0]);
+    return;
+  }
+  case AggFinal::SumDec: case AggFinal::TotalDec: case AggFinal::AvgDec: {
+    const i128 sum = t.wide ? (i128)((u128)l[0] + ((u128)l[1] << 32) + ((u128)l[2] << 64) + ((u128)l[3] << 96))
+                            : t.fast_sum ? (i128)(int64_t)l[0] : exact_total(l);
+    if (fin == AggFinal::AvgDec) {
+      if (rows <= 0) { *null = true; return; }
+      const bool neg = sum < 0;
+      u128 q;
+      uint64_t r;
+      udiv128(neg ? (u128)0 - (u128)sum : (u128)sum, (uint64_t)rows, &q, &r);
+      i128 v = neg ? -(i128)q : (i128)q;
+      if ((u128)r * 2 >= (u128)(uint64_t)rows) v += neg ? -1 : 1; // half away from zero
+      dec(v);
+      return;
+    }
+    if (t.null_without_values && rows == 0) { *null = true; return; }
+    dec(sum);
+    return;
+  }
+  case AggFinal::CountRows: *w0 = i64_image(rows); return;
+  case AggFinal::CountNullsZero: *w0 = i64_image(0); return;
+  case AggFinal::CountValid: *w0 = i64_image((int64_t)l[0]); return;
+  case AggFinal::CountNulls: *w0 = i64_image((int64_t)g[0] - (int64_t)l[0]); return;
+  case AggFinal::SumI64Fast: case AggFinal::MinI64: case AggFinal::MaxI64:
+    if (rows == 0) { *null = true; return; }
+    *w0 = i64_image((int64_t)l[0]);
+    return;
+  case AggFinal::SumI64:
+    if (rows == 0) { *null = true; return; }
+    *w0 = i64_image((int64_t)exact_total(l)); // (a total outside i64 fails the query: order_key_kernel's error record)
+    return;
+  case AggFinal::SumF64: if (rows == 0) { *null = true; return; } *w0 = f64_image(as_u64(f64_sum())); return;
+  case AggFinal::TotalF64: *w0 = f64_image(as_u64(f64_sum())); return;
+  case AggFinal::AvgI64Fast:
+    if (rows == 0) { *null = true; return; }
+    *w0 = f64_image(as_u64((double)(int64_t)l[0] / (double)rows));
+    return;
+  case AggFinal::AvgI64:
+    if (rows == 0) { *null = true; return; }
+    *w0 = f64_image(as_u64((double)(int64_t)exact_total(l) / (double)rows));
+    return;
+  case AggFinal::AvgF64: if (rows == 0) { *null = true; return; } *w0 = f64_image(as_u64(host_div_rows(f64_sum(), rows))); return;
+  case AggFinal::MinF64: case AggFinal::MaxF64: {
+    if (rows == 0) { *null = true; return; }
+    const uint64_t nan = 0x7FF8000000000000ull; // std::nan("")
+    auto key_to_f64 = [](int64_t key) { return (uint64_t)(key < 0 ? (key ^ 0x7FFFFFFFFFFFFFFFll) : key); };
+    if (t.plain_minmax) { *w0 = f64_image(key_to_f64((int64_t)l[0])); return; }
+    if (l[2] & 1u) { *w0 = f64_image(nan); return; }
+    const uint64_t none = fin == AggFinal::MinF64 ? 0x7FFFFFFFFFFFFFFFull : 0x8000000000000000ull;
+    if (l[0] == none) { *w0 = f64_image(nan); return; }
+    uint64_t v = key_to_f64((int64_t)l[0]);
+    if (as_f64(v) == 0.0 && l[1] != 0x7FFFFFFFFFFFFFFFull && (l[1] & 1u)) v = 0x8000000000000000ull; // −0.0
+    *w0 = f64_image(v);
+    return;
+  }
+  }
+}
+
+__global__ __launch_bounds__(kOrderBlock) void order_key_kernel(OrderParams p) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += stride) {
+    const uint64_t *g = p.lanes + i * (uint64_t)p.k;
+    for (int e = 0; e < p.n_err; ++e) { // SUM / AVG over i64: the total outside i64, or a prefix that may have left it
+      const int64_t rows = p.err_count_lane[e] >= 0 ? (int64_t)g[2 + p.err_count_lane[e]] : (int64_t)g[0];
+      if (rows == 0) continue;
+      const uint64_t *l = g + 2 + p.err_lane[e];
+      const i128 total = exact_total(l);
+      const bool bad = total > (i128)INT64_MAX || total < (i128)INT64_MIN || __umul64hi(l[2], (uint64_t)rows) != 0 ||
+                       l[2] * (uint64_t)rows > (uint64_t)INT64_MAX;
+      if (bad) atomicMin(p.first_bad + e, (unsigned long long)i);
+    }
+    for (int j = 0; j < p.n_terms; ++j) {
+      const OrderTerm &t = p.t[j];
+      bool null;
+      uint64_t w0, w1 = 0;
+      if (t.kind == kTermAgg) agg_image(t, g, &null, &w0, &w1);
+      else {
+        null = !p.kvalid[(uint64_t)t.key * p.n + i];
+        const int64_t v = p.kv[(uint64_t)t.key * p.n + i];
+        w0 = null ? 0 : t.kind == kTermKeyUtf8 ? (uint64_t)t.rank[(uint64_t)v & 255u] : i64_image(v);
+      }
+      if (null) w0 = w1 = 0;
+      else if (t.desc) { w0 = ~w0; w1 = ~w1; }
+      const bool two = t.kind == kTermAgg && ((AggFinal)t.fin == AggFinal::SumDec || (AggFinal)t.fin == AggFinal::TotalDec || (AggFinal)t.fin == AggFinal::AvgDec ||
+                                              (AggFinal)t.fin == AggFinal::MinDec || (AggFinal)t.fin == AggFinal::MaxDec);
+      p.keys[(uint64_t)t.word * p.n + i] = null == (bool)t.nulls_first ? 0u : 1u;
+      p.keys[(uint64_t)(t.word + 1) * p.n + i] = w0;
+      if (two) p.keys[(uint64_t)(t.word + 2) * p.n + i] = w1;
+    }
+  }
+}
+
+__device__ inline uint64_t key_word(const uint64_t *keys, uint64_t n, int n_words, int j, uint64_t i) {
+  return j == n_words ? i : keys[(uint64_t)j * n + i];
+}
+
+__global__ __launch_bounds__(kOrderBlock) void order_radix_pass(const uint64_t *keys, uint64_t n, int n_words, int w, int shift, SelectState *st,
+                                                               unsigned int *hist, unsigned int *arrived) {
+  __shared__ unsigned int h[256];
+  __shared__ unsigned long long pre[kMaxWords + 1], msk[kMaxWords + 1];
+  __shared__ uint32_t done;
+  for (uint32_t b = threadIdx.x; b < 256; b += blockDim.x) h[b] = 0;
+  for (int j = threadIdx.x; j <= w; j += blockDim.x) { pre[j] = st->prefix[j]; msk[j] = st->mask[j]; }
+  if (threadIdx.x == 0) done = st->done;
+  __syncthreads();
+  if (done) return; // (the whole grid: the state is the previous launch's)
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    bool live = true;
+    for (int j = 0; j <= w && live; ++j) live = (key_word(keys, n, n_words, j, i) & msk[j]) == pre[j];
+    if (live) atomicAdd(&h[(key_word(keys, n, n_words, w, i) >> shift) & 255u], 1u);
+  }
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < 256; b += blockDim.x)
+    if (h[b]) atomicAdd(hist + b, h[b]);
+  // last arriver (agent-scope release / acquire around one counter; the histogram is atomics, read back with sc1 loads)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (atomicAdd(arrived, 1u) != gridDim.x - 1) return;
+  // the last workgroup to arrive: every histogram is in — the digit of the threshold
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const unsigned long long need = st->need;
+  unsigned long long before = 0, c = 0;
+  uint32_t b = 0;
+  for (; b < 256; ++b) {
+    c = __hip_atomic_load(hist + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (before + c >= need) break;
+    before += c;
+  }
+  if (b == 256) st->done = 1; // (unreachable: the tied groups hold at least `need`)
+  else {
+    st->prefix[w] |= (unsigned long long)b << shift;
+    st->mask[w] |= 255ull << shift;
+    st->need = need - before;
+    if (c == need - before) st->done = 1; // the whole bucket is taken: the threshold is final
+  }
+  for (uint32_t x = 0; x < 256; ++x) hist[x] = 0;
+  *arrived = 0;
+}
+
+// groups whose composite key, under the mask, is at most the threshold: exactly m of them
+__global__ __launch_bounds__(kOrderBlock) void order_select_kernel(const uint64_t *keys, uint64_t n, int n_words, const SelectState *st, uint32_t *cand,
+                                                                   uint32_t cap, unsigned int *count) {
+  __shared__ unsigned long long pre[kMaxWords + 1], msk[kMaxWords + 1];
+  for (int j = threadIdx.x; j <= n_words; j += blockDim.x) { pre[j] = st->prefix[j]; msk[j] = st->mask[j]; }
+  __syncthreads();
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    bool take = true;
+    for (int j = 0; j <= n_words; ++j) {
+      const uint64_t a = key_word(keys, n, n_words, j, i) & msk[j];
+      if (a != pre[j]) { take = a < pre[j]; break; }
+    }
+    if (take) {
+      const unsigned int at = atomicAdd(count, 1u);
+      if (at < cap) cand[at] = (uint32_t)i;
+    }
+  }
+}
+
+// output position of every survivor = survivors with a smaller composite key (keys are distinct: the position is the last word)
+constexpr uint32_t kRankTile = 128; // survivors per LDS tile (own keys 34 KiB + tile 17 KiB at the most words)
+__global__ __launch_bounds__(kOrderBlock) void order_rank_kernel(const uint64_t *keys, uint64_t n, int n_words, const uint32_t *cand, uint32_t m, uint32_t offset,
+                                                                 uint32_t *out_rows) {
+  __shared__ uint64_t own[(kMaxWords + 1) * kOrderBlock];
+  __shared__ uint64_t tile[(kMaxWords + 1) * kRankTile];
+  const uint32_t c = blockIdx.x * kOrderBlock + threadIdx.x;
+  const uint32_t mine = c < m ? cand[c] : 0;
+  for (int j = 0; j <= n_words; ++j) own[j * kOrderBlock + threadIdx.x] = key_word(keys, n, n_words, j, mine);
+  uint32_t rank = 0;
+  for (uint32_t t0 = 0; t0 < m; t0 += kRankTile) {
+    __syncthreads();
+    const uint32_t e = t0 + threadIdx.x;
+    if (threadIdx.x < kRankTile && e < m) {
+      const uint32_t other = cand[e];
+      for (int j = 0; j <= n_words; ++j) tile[j * kRankTile + threadIdx.x] = key_word(keys, n, n_words, j, other);
+    }
+    __syncthreads();
+    const uint32_t in_tile = m - t0 < kRankTile ? m - t0 : kRankTile;
+    for (uint32_t x = 0; x < in_tile; ++x) {
+      for (int j = 0; j <= n_words; ++j) {
+        const uint64_t a = tile[j * kRankTile + x], b = own[j * kOrderBlock + threadIdx.x];
+        if (a != b) { rank += a < b; break; }
+      }
+    }
+  }
+  if (c < m && rank >= offset && rank < m) out_rows[rank - offset] = mine;
+}
+
+__global__ __launch_bounds__(kOrderBlock) void order_gather_kernel(const uint64_t *lanes, const int64_t *kv, const uint8_t *kvalid, uint64_t n, int k, int n_keys,
+                                                                   const uint32_t *rows, uint32_t n_out, uint64_t *o_lanes, int64_t *o_kv, uint8_t *o_kvalid) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_out) return;
+  const uint64_t g = rows[r];
+  if (g >= n) return;
+  for (int j = 0; j < k; ++j) o_lanes[(uint64_t)r * k + j] = lanes[g * k + j];
+  for (int j = 0; j < n_keys; ++j) {
+    o_kv[(uint64_t)j * n_out + r] = kv[(uint64_t)j * n + g];
+    o_kvalid[(uint64_t)j * n_out + r] = kvalid[(uint64_t)j * n + g];
+  }
+}
+
+bool is_decimal_fin(AggFinal f) {
+  return f == AggFinal::SumDec || f == AggFinal::TotalDec || f == AggFinal::AvgDec || f == AggFinal::MinDec || f == AggFinal::MaxDec;
+}
+
+uint32_t grid_for(uint64_t n) {
+  const uint64_t want = (n + kOrderBlock - 1) / kOrderBlock;
+  const uint64_t cap = (uint64_t)g_ctx.cu_count * 8;
+  return (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
+}
+
+} // namespace
+
+bool group_order_device_ok(const GroupOrderSpec &o, const LazyGroups &lz, std::string *why) {
+  const uint64_t want = o.limit > UINT64_MAX - o.offset ? UINT64_MAX : o.offset + o.limit;
+  if (want > kGroupOrderDeviceRows) { *why = "offset + limit above " + std::to_string(kGroupOrderDeviceRows); return false; }
+  if (o.terms.size() > (size_t)kMaxTerms) { *why = "more than " + std::to_string(kMaxTerms) + " terms"; return false; }
+  if (lz.n >= (1ull << 32)) { *why = "2^32 groups or more"; return false; }
+  int words = 0, n_err = 0;
+  for (const AggOut &a : lz.plan->aggs) n_err += a.fin == AggFinal::SumI64 || a.fin == AggFinal::AvgI64;
+  if (n_err > kMaxErrAggs) { *why = "more than " + std::to_string(kMaxErrAggs) + " i64 SUM / AVG aggregates"; return false; }
+  for (const llkv_group_order_key &t : o.terms) {
+    if (t.kind == LLKV_GROUP_ORDER_KEY) {
+      const ColumnInfo *ci = lz.key_cols[t.index];
+      if (ci->dtype == LLKV_DT_UTF8 && ci->dictionary.size() > 256) { *why = "a Utf8 key with more than 256 dictionary entries"; return false; }
+      words += 2;
+      continue;
+    }
+    const AggOut &a = lz.plan->aggs[t.index];
+    if (a.digits_lane >= 0) { *why = "aggregate " + std::to_string(t.index) + ": a computed DECIMAL argument"; return false; }
+    words += is_decimal_fin(a.fin) ? 3 : 2;
+  }
+  if (words > kMaxWords) { *why = "more than " + std::to_string(kMaxWords) + " order-key words"; return false; }
+  return true;
+}
+
+int group_order_device(const GroupOrderSpec &o, const LazyGroups &lz, const uint64_t *d_lanes, const int64_t *d_kv, const uint8_t *d_kvalid,
+                       uint64_t n, hipStream_t s, void **h_lanes, size_t *cap_lanes, void **h_kv, size_t *cap_kv, void **h_kvalid, size_t *cap_kvalid,
+                       uint64_t *n_out) {
+  *n_out = 0;
+  if (n == 0) return LLKV_OK;
+  int rc;
+  const LoweredPlan &plan = *lz.plan;
+  const int K = lz.k;
+  const uint32_t n_keys = lz.n_keys;
+  OrderParams p;
+  std::memset(&p, 0, sizeof p);
+  p.lanes = d_lanes;
+  p.kv = d_kv;
+  p.kvalid = d_kvalid;
+  p.n = n;
+  p.k = K;
+  std::vector<int> err_agg;
+  for (size_t a = 0; a < plan.aggs.size(); ++a) {
+    const AggOut &ao = plan.aggs[a];
+    if (ao.fin != AggFinal::SumI64 && ao.fin != AggFinal::AvgI64) continue;
+    p.err_lane[err_agg.size()] = ao.lane;
+    p.err_count_lane[err_agg.size()] = ao.count_lane;
+    err_agg.push_back((int)a);
+  }
+  p.n_err = (int32_t)err_agg.size();
+  // Utf8 key terms: dictionary code → rank in byte order
+  std::vector<uint32_t> ranks((size_t)std::max<size_t>(1, o.terms.size()) * 256, 0);
+  int words = 0;
+  for (size_t j = 0; j < o.terms.size(); ++j) {
+    const llkv_group_order_key &k = o.terms[j];
+    OrderTerm &t = p.t[j];
+    t.word = words;
+    t.desc = k.descending != 0;
+    t.nulls_first = k.nulls_first != 0;
+    if (k.kind == LLKV_GROUP_ORDER_KEY) {
+      const ColumnInfo *ci = lz.key_cols[k.index];
+      t.key = (int32_t)k.index;
+      t.kind = ci->dtype == LLKV_DT_UTF8 ? kTermKeyUtf8 : kTermKeyInt;
+      if (t.kind == kTermKeyUtf8) {
+        std::vector<uint32_t> idx(ci->dictionary.size());
+        std::iota(idx.begin(), idx.end(), 0u);
+        std::sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return ci->dictionary[x] < ci->dictionary[y]; });
+        for (size_t r = 0; r < idx.size(); ++r) // equal strings share a rank
+          ranks[j * 256 + idx[r]] = r && ci->dictionary[idx[r]] == ci->dictionary[idx[r - 1]] ? ranks[j * 256 + idx[r - 1]] : (uint32_t)r;
+      }
+      words += 2;
+      continue;
+    }
+    const AggOut &a = plan.aggs[k.index];
+    t.kind = kTermAgg;
+    t.fin = (int32_t)a.fin;
+    t.lane = a.lane;
+    t.count_lane = a.count_lane;
+    t.typed_by_first_value = a.typed_by_first_value;
+    t.fast_sum = a.fast_sum;
+    t.wide = a.wide;
+    t.plain_minmax = a.plain_minmax;
+    t.null_without_values = a.null_without_values;
+    t.fixed_point = a.fixed_point;
+    t.fixed_exp = a.fixed_exp;
+    t.exact_levels = a.exact_levels;
+    t.wide_delta = a.wide_delta;
+    t.wide_base_hi = a.wide_base_hi;
+    t.wide_base_lo = a.wide_base_lo;
+    words += is_decimal_fin(a.fin) ? 3 : 2;
+  }
+  p.n_terms = (int32_t)o.terms.size();
+  p.n_words = words;
+  const uint64_t m = o.end(n);
+  const uint64_t rows_out = m > o.offset ? m - o.offset : 0;
+
+  // one upload: rank tables, the select state, the error records, the histogram and its arrival counter
+  SelectState st;
+  std::memset(&st, 0, sizeof st);
+  st.need = m;
+  if (m >= n) st.done = 1; // every group: mask 0 selects them all
+  for (int j = 0; j < words; ++j) st.mask[j] = 0;
+  for (size_t j = 0; j < o.terms.size(); ++j) st.mask[p.t[j].word] = ~0xFFull; // NULL words: only the low byte varies
+  {
+    uint32_t nb = 1;
+    while (nb < 8 && ((n - 1) >> (8 * nb)) != 0) ++nb;
+    st.mask[words] = nb == 8 ? 0 : ~0ull << (8 * nb);
+  }
+  const size_t ranks_bytes = ranks.size() * 4, st_off = (ranks_bytes + 15) & ~(size_t)15, bad_off = st_off + sizeof(SelectState),
+               hist_off = bad_off + (size_t)kMaxErrAggs * 8, total = hist_off + 257 * 4;
+  std::vector<uint8_t> blob(total, 0);
+  std::memcpy(blob.data(), ranks.data(), ranks_bytes);
+  std::memcpy(blob.data() + st_off, &st, sizeof st);
+  std::memset(blob.data() + bad_off, 0xFF, (size_t)kMaxErrAggs * 8);
+  Scratch meta, keys, cand, rows, count, o_lanes, o_kv, o_kvalid;
+  if ((rc = meta.alloc(total)) || (words && (rc = keys.alloc((size_t)words * n * 8)))) return rc;
+  HIP_TRY(hipMemcpyAsync(meta.p, blob.data(), total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s)); // `blob` is a local
+  uint8_t *mb = meta.as<uint8_t>();
+  SelectState *d_st = reinterpret_cast<SelectState *>(mb + st_off);
+  unsigned int *d_hist = reinterpret_cast<unsigned int *>(mb + hist_off), *d_arrived = d_hist + 256;
+  for (size_t j = 0; j < o.terms.size(); ++j) p.t[j].rank = reinterpret_cast<const uint32_t *>(mb) + j * 256;
+  p.keys = keys.as<uint64_t>();
+  p.first_bad = reinterpret_cast<unsigned long long *>(mb + bad_off);
+
+  if (words || p.n_err) {
+    hipLaunchKernelGGL(order_key_kernel, dim3(grid_for(n)), dim3(kOrderBlock), 0, s, p);
+    HIP_TRY(hipGetLastError());
+  }
+  if (p.n_err) { // the first failing group of the first aggregate that has one: the host's finalize words the error
+    uint64_t bad[kMaxErrAggs];
+    Readback rb;
+    if ((rc = rb.add(bad, p.first_bad, (size_t)p.n_err * 8, s)) || (rc = rb.wait())) return rc;
+    for (int e = 0; e < p.n_err; ++e) {
+      if (bad[e] == ~0ull) continue;
+      std::vector<uint64_t> g((size_t)K);
+      HIP_TRY(hipMemcpyAsync(g.data(), d_lanes + bad[e] * (uint64_t)K, (size_t)K * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      llkv_value v;
+      std::string err;
+      if ((rc = finalize_value(plan.aggs[(size_t)err_agg[(size_t)e]], g.data(), 2, &v, &err, false))) return set_error(rc, err);
+      return set_error(LLKV_INTERNAL, "device finalize check disagrees with the host's for aggregate " + std::to_string(err_agg[(size_t)e]));
+    }
+  }
+  if (rows_out == 0) return LLKV_OK;
+  const uint32_t grid = grid_for(n);
+  if (m < n) {
+    for (int w = 0; w <= words; ++w) {
+      for (int b = 7; b >= 0; --b) {
+        if ((st.mask[w] >> (8 * b)) & 0xFF) continue; // a byte known to be zero
+        hipLaunchKernelGGL(order_radix_pass, dim3(grid), dim3(kOrderBlock), 0, s, (const uint64_t *)p.keys, n, words, w, 8 * b, d_st, d_hist, d_arrived);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+  }
+  if ((rc = cand.alloc(m * 4)) || (rc = count.alloc(4)) || (rc = rows.alloc(rows_out * 4)) || (rc = o_lanes.alloc(rows_out * (size_t)K * 8)) ||
+      (rc = o_kv.alloc(rows_out * n_keys * 8 + 8)) || (rc = o_kvalid.alloc(rows_out * n_keys + 8)))
+    return rc;
+  HIP_TRY(hipMemsetAsync(count.p, 0, 4, s));
+  hipLaunchKernelGGL(order_select_kernel, dim3(grid), dim3(kOrderBlock), 0, s, (const uint64_t *)p.keys, n, words, (const SelectState *)d_st, cand.as<uint32_t>(),
+                     (uint32_t)m, count.as<unsigned int>());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(order_rank_kernel, dim3((uint32_t)((m + kOrderBlock - 1) / kOrderBlock)), dim3(kOrderBlock), 0, s, (const uint64_t *)p.keys, n, words,
+                     (const uint32_t *)cand.as<uint32_t>(), (uint32_t)m, (uint32_t)o.offset, rows.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(order_gather_kernel, dim3((uint32_t)((rows_out + kOrderBlock - 1) / kOrderBlock)), dim3(kOrderBlock), 0, s, d_lanes, d_kv, d_kvalid, n, K,
+                     (int)n_keys, (const uint32_t *)rows.as<uint32_t>(), (uint32_t)rows_out, o_lanes.as<uint64_t>(), o_kv.as<int64_t>(), o_kvalid.as<uint8_t>());
+  HIP_TRY(hipGetLastError());
+  if ((rc = pinned_reserve(h_lanes, cap_lanes, rows_out * (size_t)K * 8)) || (rc = pinned_reserve(h_kv, cap_kv, rows_out * n_keys * 8 + 8)) ||
+      (rc = pinned_reserve(h_kvalid, cap_kvalid, rows_out * n_keys + 8)))
+    return rc;
+  uint32_t selected = 0;
+  HIP_TRY(hipMemcpyAsync(*h_lanes, o_lanes.p, rows_out * (size_t)K * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(*h_kv, o_kv.p, rows_out * n_keys * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(*h_kvalid, o_kvalid.p, rows_out * n_keys, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&selected, count.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (selected != m) return set_error(LLKV_INTERNAL, "device top-k selected " + std::to_string(selected) + " groups, not " + std::to_string(m));
+  *n_out = rows_out;
+  return LLKV_OK;
+}
+
+// ---- host order ----------------------------------------------------------------------------------------------------------
+int group_order_host(const GroupOrderSpec &o, uint64_t n, const std::function<int(uint64_t, const llkv_group_order_key &, llkv_value *)> &cell,
+                     std::vector<uint64_t> *rows) {
+  rows->clear();
+  const uint64_t m = o.end(n);
+  const size_t T = o.terms.size(), W = 3 * T; // per term: NULL word, two value words
+  std::vector<uint64_t> img((size_t)n * W, 0);
+  std::vector<llkv_value> col((size_t)n);
+  for (size_t j = 0; j < T; ++j) {
+    const llkv_group_order_key &t = o.terms[j];
+    int rc;
+    for (uint64_t r = 0; r < n; ++r)
+      if ((rc = cell(r, t, &col[r]))) return rc;
+    std::vector<uint64_t> str_rank;
+    bool any_str = false;
+    for (uint64_t r = 0; r < n && !any_str; ++r) any_str = !col[r].is_null && col[r].dtype == LLKV_DT_UTF8;
+    if (any_str) { // strings by their bytes (str::cmp)
+      std::vector<uint64_t> idx;
+      for (uint64_t r = 0; r < n; ++r) if (!col[r].is_null) idx.push_back(r);
+      auto str = [&](uint64_t r) { return col[r].str ? col[r].str : ""; };
+      std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return std::strcmp(str(a), str(b)) < 0; });
+      str_rank.assign((size_t)n, 0);
+      for (size_t x = 1; x < idx.size(); ++x) str_rank[idx[x]] = str_rank[idx[x - 1]] + (std::strcmp(str(idx[x - 1]), str(idx[x])) != 0);
+    }
+    for (uint64_t r = 0; r < n; ++r) {
+      const llkv_value &v = col[r];
+      uint64_t *w = img.data() + (size_t)r * W + 3 * j;
+      const bool null = v.is_null != 0;
+      w[0] = null == (t.nulls_first != 0) ? 0 : 1;
+      if (null) continue;
+      switch (v.dtype) {
+      case LLKV_DT_FLOAT64: { uint64_t b; std::memcpy(&b, &v.f64, 8); w[1] = (b >> 63) ? ~b : (b | 0x8000000000000000ull); break; }
+      case LLKV_DT_DECIMAL128: w[1] = (uint64_t)v.i64_hi ^ 0x8000000000000000ull; w[2] = (uint64_t)v.i64; break;
+      case LLKV_DT_UTF8: w[1] = str_rank[r]; break;
+      default: w[1] = (uint64_t)v.i64 ^ 0x8000000000000000ull; break;
+      }
+      if (t.descending) { w[1] = ~w[1]; w[2] = ~w[2]; }
+    }
+  }
+  std::vector<uint64_t> idx((size_t)n);
+  std::iota(idx.begin(), idx.end(), 0ull);
+  auto before = [&](uint64_t a, uint64_t b) {
+    const uint64_t *x = img.data() + (size_t)a * W, *y = img.data() + (size_t)b * W;
+    for (size_t j = 0; j < W; ++j)
+      if (x[j] != y[j]) return x[j] < y[j];
+    return a < b; // ties: position in the unordered output
+  };
+  if (m < n) std::partial_sort(idx.begin(), idx.begin() + (ptrdiff_t)m, idx.end(), before);
+  else std::sort(idx.begin(), idx.end(), before);
+  if (m > o.offset) rows->assign(idx.begin() + (ptrdiff_t)o.offset, idx.begin() + (ptrdiff_t)m);
+  return LLKV_OK;
+}
+
+} // namespace llkv

@@ -53,7 +53,7 @@ struct PartGroupBy {
   hipStream_t copy_stream = nullptr;
   hipEvent_t range_done[kRanges] = {};
   uint32_t *h_counts = nullptr; // pinned: groups with rows per range, then the scatter's error word
-  int run(LazyGroups *out);
+  int run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done);
   ~PartGroupBy() {
     scratch_free(d_dict_num);
     scratch_free(d_lane_tables);
@@ -176,7 +176,7 @@ int part_groupby_prepare(const Table *table, const llkv_filter *filters, uint32_
   return LLKV_OK;
 }
 
-int PartGroupBy::run(LazyGroups *out) {
+int PartGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done) {
   *out = LazyGroups{};
   out->active = true;
   out->plan = &plan;
@@ -240,7 +240,8 @@ int PartGroupBy::run(LazyGroups *out) {
   // eight of 61: 3.72, against 2.77 one after the other)
   const uint32_t per_range = std::max<uint32_t>(g_ctx.cu_count, (np + kRanges - 1) / kRanges);
   const uint32_t n_ranges = (np + per_range - 1) / per_range;
-  const bool ranges = order_by_keys && ids_in_key_order && n_keys == 1 && n_ranges >= 2 && (uint64_t)ng * (k * 8 + 9) <= (256ull << 20) &&
+  const bool ordered = out_order && done && out_order->active(); // ORDER BY / LIMIT over the groups: no streamed key-order copy-out
+  const bool ranges = !ordered && order_by_keys && ids_in_key_order && n_keys == 1 && n_ranges >= 2 && (uint64_t)ng * (k * 8 + 9) <= (256ull << 20) &&
                       !std::getenv("LLKV_HIP_PART_NO_OVERLAP");
   if (ranges) {
     // ---- key order, one integer key: ascending group ids are the output order, so the groups of partitions [p0, p1) can leave
@@ -346,6 +347,22 @@ int PartGroupBy::run(LazyGroups *out) {
   HIP_TRY(hj_launch_emit_dense_groups(group_rows.as<uint64_t>(), k, ids.as<uint32_t>(), order, n_groups, kl_keys, lanes_d.as<uint64_t>(), kv_d.as<int64_t>(),
                                       kvalid_d.as<uint8_t>(), s));
   mark("emit groups");
+  if (ordered) {
+    done->total = n_groups;
+    if (group_order_device_ok(*out_order, *out, &done->why_host)) { // the device top-k copies out only the rows returned
+      uint64_t n_out = 0;
+      if ((rc = group_order_device(*out_order, *out, lanes_d.as<uint64_t>(), kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), n_groups, s, &h_lanes, &cap_lanes, &h_kv,
+                                   &cap_kv, &h_kvalid, &cap_kvalid, &n_out)))
+        return rc;
+      done->device = true;
+      out->n = n_out;
+      out->lanes = static_cast<const uint64_t *>(h_lanes);
+      out->key_vals = static_cast<const int64_t *>(h_kv);
+      out->key_valid = static_cast<const uint8_t *>(h_kvalid);
+      mark("order top-k");
+      return LLKV_OK;
+    }
+  }
   if ((rc = pinned_reserve(&h_lanes, &cap_lanes, (size_t)n_groups * k * 8)) || (rc = pinned_reserve(&h_kv, &cap_kv, (size_t)n_groups * n_keys * 8)) ||
       (rc = pinned_reserve(&h_kvalid, &cap_kvalid, (size_t)n_groups * n_keys)))
     return rc;
@@ -373,6 +390,6 @@ int PartGroupBy::run(LazyGroups *out) {
   return LLKV_OK;
 }
 
-int part_groupby_run(PartGroupBy *p, LazyGroups *out) { return p->run(out); }
+int part_groupby_run(PartGroupBy *p, LazyGroups *out, const GroupOrderSpec *order, GroupOrderDone *done) { return p->run(out, order, done); }
 
 } // namespace llkv

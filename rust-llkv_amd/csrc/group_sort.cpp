@@ -43,7 +43,7 @@ struct SortedGroupBy {
   // key set of the dimension rows that qualify (a bitmap the caller owns, alive as long as this object)
   bool has_key_set = false;
   KeySetView key_set{nullptr, 0, 0};
-  int run(LazyGroups *out);
+  int run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done);
   ~SortedGroupBy() {
     if (part) part_groupby_free(part);
     if (h_lanes) (void)hipHostFree(h_lanes);
@@ -233,8 +233,8 @@ int key_column_of(const Table *t, uint32_t field, JoinKeyColumn *kc, long long *
 }
 } // namespace
 
-int SortedGroupBy::run(LazyGroups *out) {
-  if (part) return part_groupby_run(part, out);
+int SortedGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done) {
+  if (part) return part_groupby_run(part, out, out_order, done);
   *out = LazyGroups{};
   out->active = true;
   out->plan = &red_plan;
@@ -472,6 +472,26 @@ int SortedGroupBy::run(LazyGroups *out) {
   if ((rc = jit_launch_raw(narrow ? red_kernel.fn2 : red_kernel.fn, (uint32_t)((n_groups + groups_per_block - 1) / groups_per_block), &p, sizeof p, s))) return rc;
   HIP_TRY(hj_launch_group_keys(ks, sel.d_dev, perm, seg.as<uint64_t>(), order, n_groups, kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), s));
   mark("group reduce");
+  if (done) done->total = n_groups;
+  if (out_order && done && out_order->active()) { // ORDER BY / LIMIT: the device top-k copies out only the rows returned
+    if (group_order_device_ok(*out_order, *out, &done->why_host)) {
+      uint32_t errflag = 0;
+      Readback rb;
+      if ((rc = rb.add(&errflag, err_d.p, 4, s)) || (rc = rb.wait())) return rc;
+      if (errflag) return set_error(LLKV_INTERNAL, arith_error_message(errflag));
+      uint64_t n_out = 0;
+      if ((rc = group_order_device(*out_order, *out, lanes_d.as<uint64_t>(), kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), n_groups, s, &h_lanes, &cap_lanes, &h_kv,
+                                   &cap_kv, &h_kvalid, &cap_kvalid, &n_out)))
+        return rc;
+      done->device = true;
+      out->n = n_out;
+      out->lanes = static_cast<const uint64_t *>(h_lanes);
+      out->key_vals = static_cast<const int64_t *>(h_kv);
+      out->key_valid = static_cast<const uint8_t *>(h_kvalid);
+      mark("order top-k");
+      return LLKV_OK;
+    }
+  }
 
   if ((rc = pinned_reserve(&h_lanes, &cap_lanes, n_groups * (size_t)K * 8)) || (rc = pinned_reserve(&h_kv, &cap_kv, n_groups * n_keys * 8)) ||
       (rc = pinned_reserve(&h_kvalid, &cap_kvalid, n_groups * n_keys)))
@@ -504,6 +524,6 @@ int SortedGroupBy::run(LazyGroups *out) {
   return LLKV_OK;
 }
 
-int sorted_groupby_run(SortedGroupBy *s, LazyGroups *out) { return s->run(out); }
+int sorted_groupby_run(SortedGroupBy *s, LazyGroups *out, const GroupOrderSpec *order, GroupOrderDone *done) { return s->run(out, order, done); }
 
 } // namespace llkv

@@ -10,7 +10,7 @@ xGMI) on GPUs, "gloo" in the CPU tests.
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 
@@ -102,15 +102,23 @@ def join_groupby_topk(dist, rt, join_agg, rank: int, world: int, limit: int, all
     return merged, sum(p[1] for p in parts)
 
 
-def sorted_groupby(dist, prepared, world: int):
+def sorted_groupby(dist, prepared, world: int, order: Sequence = (), offset: int = 0, limit: Optional[int] = None):
     """GROUP BY of any cardinality over a sharded table (the sort-based route): this rank's shard is reduced on its
     GPU, the partial groups of all ranks are all-gathered and merged in rank order on every rank
-    (llkv_hip_query_partial_groups / llkv_hip_query_merge_groups).  Returns the table-wide rows."""
+    (llkv_hip_query_partial_groups / llkv_hip_query_merge_groups).  ``order`` / ``offset`` / ``limit`` (abi.GroupOrder
+    terms) apply to the merged groups: a group can straddle ranks.  Returns the table-wide rows."""
+    ordered = bool(order) or offset != 0 or limit is not None
+    if ordered and world == 1:
+        prepared.set_group_order(order, offset, limit)
+    elif ordered:  # the ranks' partial groups leave unordered
+        prepared.set_group_order()
     prepared.launch(0)
     prepared.finish_only()
     if world > 1:
         gathered = [None] * world
         dist.all_gather_object(gathered, prepared.partial_groups())
+        if ordered:
+            prepared.set_group_order(order, offset, limit)
         prepared.merge_groups(gathered)
     return prepared.rows()
 

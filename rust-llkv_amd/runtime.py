@@ -55,6 +55,9 @@ def lib():
         getattr(L, name).argtypes = [C.c_void_p]
     L.llkv_hip_free.argtypes = [C.c_void_p]
     L.llkv_hip_free.restype = None
+    L.llkv_hip_query_set_group_order.argtypes = [C.c_void_p, C.POINTER(abi.CGroupOrderKey), C.c_uint32, C.c_uint64, C.c_uint64]
+    L.llkv_hip_query_total_groups.restype = C.c_uint64
+    L.llkv_hip_query_total_groups.argtypes = [C.c_void_p]
     L.llkv_plan_last_error.restype = C.c_char_p
     _lib = L
     return L
@@ -676,6 +679,18 @@ class PreparedQuery:
         return (np.ctypeslib.as_array(kv, shape=(nk.value, n.value)).copy(), np.ctypeslib.as_array(kva, shape=(nk.value, n.value)).copy(),
                 np.ctypeslib.as_array(ln, shape=(n.value, k.value)).copy())
 
+    def set_group_order(self, order: Sequence["abi.GroupOrder"] = (), offset: int = 0, limit: Optional[int] = None):
+        """ORDER BY output columns, then OFFSET / LIMIT, over the groups (llkv_hip_query_set_group_order): from the next
+        finish / collect / merge_groups on.  No terms, offset 0 and no limit clear it."""
+        terms = (abi.CGroupOrderKey * max(1, len(order)))(*[t.to_c() for t in order])
+        lim = (1 << 64) - 1 if limit is None else int(limit)
+        check(lib().llkv_hip_query_set_group_order(self._h, terms, C.c_uint32(len(order)), C.c_uint64(int(offset)), C.c_uint64(lim)))
+
+    @property
+    def total_groups(self) -> int:
+        """Groups of the last finish before OFFSET / LIMIT."""
+        return int(lib().llkv_hip_query_total_groups(self._h))
+
     def merge_groups(self, parts):
         """Installs the table-wide groups from every rank's partial_groups() (in rank order); rows() then reads them."""
         world = len(parts)
@@ -716,10 +731,14 @@ def aggregate(table: HipTable, predicate, aggs: Sequence[AggregateSpec]) -> List
         q.close()
 
 
-def groupby(table: HipTable, predicate, keys: Sequence[int], aggs: Sequence[AggregateSpec], order_by_keys: bool = False) -> List[GroupRow]:
-    """execute_group_by_single_table (llkv-executor/src/lib.rs:4405)."""
+def groupby(table: HipTable, predicate, keys: Sequence[int], aggs: Sequence[AggregateSpec], order_by_keys: bool = False,
+            order: Sequence["abi.GroupOrder"] = (), offset: int = 0, limit: Optional[int] = None) -> List[GroupRow]:
+    """execute_group_by_single_table (llkv-executor/src/lib.rs:4405); ``order`` / ``offset`` / ``limit``: ORDER BY output
+    columns then OFFSET / LIMIT over the groups (sort_record_batch_with_order :13762)."""
     q = PreparedQuery(table, predicate, aggs, keys, order_by_keys)
     try:
+        if order or offset or limit is not None:
+            q.set_group_order(order, offset, limit)
         return q.run()
     finally:
         q.close()

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """GROUP BY at SF10 on one GPU beyond the per-thread accumulators: l_orderkey (≈15 M groups: sort-based route), l_partkey
 (2 M groups: partitioned route), l_shipdate (≈2500 groups: shared-image kernel) and the wide-state Q1 shape with every
-aggregate doubled — inputs resident in HBM."""
+aggregate doubled — inputs resident in HBM.  The *_top10 cases add ORDER BY sum(l_quantity) DESC LIMIT 10
+(llkv_hip_query_set_group_order) and print the route note, which says where the order ran."""
 import importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -30,12 +31,16 @@ out = {}
 only = sys.argv[2] if len(sys.argv) > 2 else ""  # "image_only": just the shared-image cases (counter runs)
 for name, keys, aggs in (("by_orderkey", [S["l_orderkey"][0]], narrow), ("by_partkey", [S["l_partkey"][0]], narrow), ("by_shipdate", [S["l_shipdate"][0]], narrow),
                          ("by_shipdate_count_only", [S["l_shipdate"][0]], narrow[:1]), ("by_shipdate_4aggs", [S["l_shipdate"][0]], mid), ("by_flag_status_shipdate", [S["l_returnflag"][0], S["l_linestatus"][0], S["l_shipdate"][0]], narrow[:2]),
-                         ("q1_wide_state", [S["l_returnflag"][0], S["l_linestatus"][0]], wide)):
+                         ("q1_wide_state", [S["l_returnflag"][0], S["l_linestatus"][0]], wide),
+                         ("by_orderkey_top10", [S["l_orderkey"][0]], narrow), ("by_partkey_top10", [S["l_partkey"][0]], narrow)):
     if only == "image_only" and name not in ("by_shipdate", "by_shipdate_count_only"):
         continue
     if only and only != "image_only" and name not in only.split(","):
         continue
     q = rt.PreparedQuery(t, None, aggs, keys, True)
+    top10 = name.endswith("_top10")
+    if top10:  # ORDER BY sum(l_quantity) DESC LIMIT 10
+        q.set_group_order([abi.GroupOrder.agg(1, descending=True)], 0, 10)
     image = q.kernel_signature.endswith(",2>")
     ts = []
     q.set_profiling(True)
@@ -47,6 +52,8 @@ for name, keys, aggs in (("by_orderkey", [S["l_orderkey"][0]], narrow), ("by_par
     kms, kn, _ = q.kernel_time()
     best = min(ts)
     out[name] = {"route": q.route_note.split(" (")[0], "groups": int(ng), "seconds_best": best, "rows_per_s": rows / best}
+    if top10:
+        out[name].update({"total_groups": q.total_groups, "route_note": q.route_note})
     if q.algorithmic_bytes:
         out[name].update({"alg_bytes": q.algorithmic_bytes, "gbs_end_to_end": q.algorithmic_bytes / best / 1e9})
         if kn:
