@@ -299,6 +299,23 @@ llkv_status llkv_hip_table_append_utf8_column(llkv_hip_table *table, uint32_t fi
                                               const uint8_t *const *chunk_data,
                                               uint32_t n_chunks,
                                               const char *const *dictionary, uint32_t dict_size);
+/* The same with `flags`; 0 behaves exactly as llkv_hip_table_append_utf8_column.
+ * LLKV_UTF8_WIDE_CODES: more than 256 distinct values may be staged, in the WIDE
+ * form — 4-byte codes, code c = the position of its string in the dictionary
+ * sorted by bytes (str::cmp).  With ≤ 256 distinct values the column is staged
+ * exactly as without the flag.  A supplied dictionary of more than 256 entries is
+ * checked for duplicates and then sorted: its order does not fix the codes.
+ * Views of a wide column carry its u32 codes (llkv_column_view.precision = 4).
+ * An append (llkv_hip_table_append_chunks) to a wide column may bring strings
+ * it already holds; a new string is refused (LLKV_UNSUPPORTED, re-stage the
+ * column), as is a 1-byte column growing past 256 strings.                   */
+#define LLKV_UTF8_WIDE_CODES 1u
+llkv_status llkv_hip_table_append_utf8_column_ex(llkv_hip_table *table, uint32_t field_id,
+                                                 const int32_t *const *chunk_offsets,
+                                                 const uint8_t *const *chunk_data,
+                                                 uint32_t n_chunks,
+                                                 const char *const *dictionary, uint32_t dict_size,
+                                                 uint32_t flags);
 /* --- llkv-column-map chunk format ------------------------- */
 /* `ARR0` blob header, llkv-column-map/src/serialization.rs:41-140: 24 bytes
  * (magic, layout, type code, len, extra_a, extra_b) then the payload; no null
@@ -632,6 +649,9 @@ typedef struct llkv_column_view {
   const uint8_t *validity; /* Arrow validity bitmap or NULL (all valid)       */
   const char *const *dictionary; /* Utf8: code → string, else NULL            */
   int32_t precision, scale;      /* Decimal128: 16-byte little-endian values  */
+  /* Utf8: precision 0 = `values` are 1-byte codes; precision 4 = `values` are
+   * uint32_t codes of a wide column (LLKV_UTF8_WIDE_CODES), whose dictionary is
+   * sorted by bytes.                                                          */
 } llkv_column_view;
 
 typedef struct llkv_batch_view {
@@ -1096,7 +1116,9 @@ typedef struct llkv_column_desc {
   uint64_t rows;      /* global table rows                                   */
   int32_t has_stats;  /* integer min/max known                               */
   int64_t min_i, max_i;
-  uint32_t dict_size; /* LLKV_DT_UTF8                                        */
+  uint32_t dict_size; /* LLKV_DT_UTF8; more than 256 entries describe a wide
+                       * column, whose dictionary must be sorted by bytes
+                       * (else LLKV_INVALID_ARGUMENT)                          */
   const char *const *dictionary;
   int32_t nullable;   /* the column has NULL cells                           */
   int32_t precision, scale; /* LLKV_DT_DECIMAL128                            */
@@ -1117,6 +1139,9 @@ llkv_status llkv_plan_lower(const llkv_column_desc *cols, uint32_t n_cols,
                             int32_t grouped, char *type_string_out, uint64_t type_string_cap,
                             uint32_t *lanes_out, uint64_t *bytes_per_row_out);
 const char *llkv_plan_last_error(void);
+/* The integer literal bank and the CodeBits bitmaps (wide Utf8 leaves, back to back) of the plan the calling thread lowered
+ * last with llkv_plan_lower: up to the caps are copied, the full counts are returned.  Host only.                    */
+llkv_status llkv_plan_last_banks(int64_t *lit_i, uint32_t lit_cap, uint32_t *n_lit, uint64_t *code_bits, uint64_t bits_cap, uint64_t *n_bits);
 /* The number a Utf8 value counts as under the reference's SQLite-style coercion of aggregate inputs
  * (`s.trim().parse::<f64>().unwrap_or(0.0)`, llkv-aggregate/src/lib.rs:426-434) — what SUM / AVG / TOTAL / MIN / MAX over
  * a dictionary-coded Utf8 column accumulate on the GPU path.  Host only.                                            */

@@ -118,6 +118,12 @@ def scan_options(include_nulls=False, include_row_ids=False, order=None) -> "CSc
     return o
 
 
+# llkv_hip_table_append_utf8_column_ex: more than 256 distinct strings may be staged, as u32 codes in byte order of the strings;
+# views of such a column carry precision 4 (values are uint32 codes)
+UTF8_WIDE_CODES = 1
+UTF8_WIDE_VIEW_PRECISION = 4
+
+
 class CColumnView(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("values", C.c_void_p), ("validity", C.POINTER(C.c_uint8)),
                 ("dictionary", C.POINTER(C.c_char_p)), ("precision", C.c_int32), ("scale", C.c_int32)]

@@ -116,7 +116,27 @@ void export_column(const llkv_column_view &c, uint64_t n, const std::string &nam
     oa->buffer_ptrs = {validity, bits};
     break;
   }
-  case LLKV_DT_UTF8: { // dictionary codes → offsets + data
+  case LLKV_DT_UTF8: // dictionary codes → offsets + data
+    if (c.precision == 4) { // u32 codes of a wide column (llkv_column_view)
+      format = "u";
+      const uint32_t *codes = static_cast<const uint32_t *>(c.values);
+      int32_t *off = static_cast<int32_t *>(oa->take((size_t)(n + 1) * 4));
+      uint64_t total = 0;
+      for (uint64_t i = 0; i < n; ++i) { // (the data pass copies the lengths found here)
+        off[i] = (int32_t)total;
+        const bool valid = !c.validity || ((c.validity[i >> 3] >> (i & 7)) & 1u);
+        total += valid && c.dictionary && c.dictionary[codes[i]] ? std::strlen(c.dictionary[codes[i]]) : 0;
+      }
+      off[n] = (int32_t)total;
+      char *data = static_cast<char *>(oa->take((size_t)total));
+      for (uint64_t i = 0; i < n; ++i) {
+        const size_t len = (size_t)(off[i + 1] - off[i]);
+        if (len) std::memcpy(data + off[i], c.dictionary[codes[i]], len);
+      }
+      oa->buffer_ptrs = {validity, off, data};
+      break;
+    }
+    {
     format = "u";
     const uint8_t *codes = static_cast<const uint8_t *>(c.values);
     size_t lens[256];
@@ -138,7 +158,7 @@ void export_column(const llkv_column_view &c, uint64_t n, const std::string &nam
     }
     oa->buffer_ptrs = {validity, off, data};
     break;
-  }
+    }
   default: format = "n"; arr->null_count = (int64_t)n; oa->buffer_ptrs = {}; break; // Null type
   }
   arr->n_buffers = (int64_t)oa->buffer_ptrs.size();

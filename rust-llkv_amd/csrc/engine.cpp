@@ -60,6 +60,7 @@ Query::~Query() {
   }
   scratch_free(d_tile_partials);
   scratch_free(d_dict_num);
+  scratch_free(d_code_bits);
   if (d_exchange && !host_mapped) scratch_free(d_exchange);
   scratch_free(d_lane_ops);
   scratch_free(d_empty_image);
@@ -252,6 +253,13 @@ int prepare_query(const Table *table, const llkv_filter *filters, uint32_t n_fil
     HIP_TRY(hipMemcpyAsync(q->d_dict_num, image.data(), image.size() * 8, hipMemcpyHostToDevice, g_ctx.stream));
     HIP_TRY(hipStreamSynchronize(g_ctx.stream)); // `image` is pageable and goes out of scope
     q->params.dict_num = q->d_dict_num;
+  }
+  if (!p.code_bits.empty()) { // bitmaps of the CodeBits leaves (the plan outlives the query's launches)
+    q->d_code_bits = (uint64_t *)scratch_alloc(p.code_bits.size() * 8);
+    if (!q->d_code_bits) return set_error(LLKV_INTERNAL, "device allocation failed");
+    HIP_TRY(hipMemcpyAsync(q->d_code_bits, p.code_bits.data(), p.code_bits.size() * 8, hipMemcpyHostToDevice, g_ctx.stream));
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    q->params.code_bits = q->d_code_bits;
   }
   for (size_t i = 0; i < p.lit_i.size(); ++i) q->params.lit_i[i] = p.lit_i[i];
   for (size_t i = 0; i < p.lit_f.size(); ++i) q->params.lit_f[i] = p.lit_f[i];
@@ -927,7 +935,7 @@ int Query::finish_from_exchange(const uint64_t *exchange) {
       rank[k].assign(card, 0);
       std::vector<uint32_t> by_value(n_codes);
       for (uint32_t c = 0; c < n_codes; ++c) by_value[c] = c;
-      if (!p.key_is_int[k]) {
+      if (!p.key_is_int[k] && !utf8_wide(table->cols.at(p.key_fields[k]).info)) { // (a wide key's codes are in byte order already)
         const auto &dict = table->cols.at(p.key_fields[k]).info.dictionary;
         auto word = [&](uint32_t c) -> const std::string & { static const std::string none; return c < dict.size() ? dict[c] : none; };
         std::stable_sort(by_value.begin(), by_value.end(), [&](uint32_t x, uint32_t y) { return word(x) < word(y); });

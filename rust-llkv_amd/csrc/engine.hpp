@@ -279,6 +279,7 @@ struct Query {
   const TileSet *tiles = nullptr;
   ScanParams params;
   double *d_dict_num = nullptr; // ScanParams::dict_num of plans that read dictionary codes as numbers
+  uint64_t *d_code_bits = nullptr; // ScanParams::code_bits of plans with CodeBits leaves (wide Utf8 columns)
   // ring of exchange images so that up to `depth` executions are in flight: the host
   // finalizes execution i while the GPU already runs i+1
   static constexpr uint32_t kMaxDepth = 8;

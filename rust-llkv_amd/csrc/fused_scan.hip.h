@@ -504,6 +504,22 @@ template <class E, class M0, class M1, class M2, class M3> struct InMask {
     return (m >> (code & 63)) & 1u;
   }
 };
+// Predicates over a wide Utf8 column (more than 256 strings, 4-byte codes = positions in the byte-ordered dictionary).
+// CodeRange: the codes in [LO, HI) — equality, ordering, BETWEEN and case-sensitive prefixes (one unsigned compare).
+template <class E, class LO, class HI> struct CodeRange {
+  static __device__ __forceinline__ bool eval(Ctx &c, int j) {
+    const uint32_t lo = (uint32_t)LO::eval(c, j);
+    return (uint32_t)E::eval(c, j) - lo < (uint32_t)HI::eval(c, j) - lo;
+  }
+};
+// CodeBits: bit `code` of the host-evaluated bitmap at word S of ScanParams::code_bits (patterns, long IN lists).  The
+// bitmap (dict_size bits, 187 KB at 1.5 M codes) is read through the caches: the codes of a scan touch it at random.
+template <class E, int S> struct CodeBits {
+  static __device__ __forceinline__ bool eval(Ctx &c, int j) {
+    const uint32_t code = (uint32_t)E::eval(c, j);
+    return (c.p.code_bits[S + (code >> 6)] >> (code & 63)) & 1u;
+  }
+};
 template <class E, class... Vs> struct In {
   static __device__ __forceinline__ bool eval(Ctx &c, int j) {
     const auto v = E::eval(c, j);
@@ -612,6 +628,10 @@ template <int S> struct Valid {
 // --------------------------------------------------------------------------
 template <int S> struct KeyCode {
   static __device__ __forceinline__ uint32_t code(Ctx &c, int j) { return c.get<U8>(S, j); }
+};
+// Wide Utf8 key: the 4-byte code is the dense id (codes run over the byte-ordered dictionary).
+template <int S> struct KeyCode32 {
+  static __device__ __forceinline__ uint32_t code(Ctx &c, int j) { return c.get<U32>(S, j); }
 };
 // Integer key with a small statistics-bounded range: code = value − column minimum.
 template <int S, class Ty, class Base> struct KeyInt {

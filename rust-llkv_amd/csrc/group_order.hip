@@ -382,7 +382,6 @@ bool group_order_device_ok(const GroupOrderSpec &o, const LazyGroups &lz, std::s
   for (const llkv_group_order_key &t : o.terms) {
     if (t.kind == LLKV_GROUP_ORDER_KEY) {
       const ColumnInfo *ci = lz.key_cols[t.index];
-      if (ci->dtype == LLKV_DT_UTF8 && ci->dictionary.size() > 256) { *why = "a Utf8 key with more than 256 dictionary entries"; return false; }
       words += 2;
       continue;
     }
@@ -431,7 +430,7 @@ int group_order_device(const GroupOrderSpec &o, const LazyGroups &lz, const uint
     if (k.kind == LLKV_GROUP_ORDER_KEY) {
       const ColumnInfo *ci = lz.key_cols[k.index];
       t.key = (int32_t)k.index;
-      t.kind = ci->dtype == LLKV_DT_UTF8 ? kTermKeyUtf8 : kTermKeyInt;
+      t.kind = ci->dtype == LLKV_DT_UTF8 && !utf8_wide(*ci) ? kTermKeyUtf8 : kTermKeyInt; // (a wide key's code is in byte order: its integer image)
       if (t.kind == kTermKeyUtf8) {
         std::vector<uint32_t> idx(ci->dictionary.size());
         std::iota(idx.begin(), idx.end(), 0u);

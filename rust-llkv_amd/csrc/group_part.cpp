@@ -44,6 +44,7 @@ struct PartGroupBy {
   bool ids_in_key_order = false;       // integer keys without NULL cells: ascending group ids are ascending keys
   uint32_t *d_code_rank = nullptr;     // [key][256] dictionary code → position in string order (Utf8 keys, ORDER BY the keys)
   double *d_dict_num = nullptr;
+  uint64_t *d_code_bits = nullptr; // ScanParams::code_bits (CodeBits leaves over wide Utf8 columns)
   uint8_t *d_lane_tables = nullptr; // [kl] ops of the kernel lanes, [k] source lane, [k] transform
   void *h_lanes = nullptr, *h_kv = nullptr, *h_kvalid = nullptr;
   size_t cap_lanes = 0, cap_kv = 0, cap_kvalid = 0;
@@ -56,6 +57,7 @@ struct PartGroupBy {
   int run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done);
   ~PartGroupBy() {
     scratch_free(d_dict_num);
+    scratch_free(d_code_bits);
     scratch_free(d_lane_tables);
     scratch_free(d_code_rank);
     if (h_lanes) (void)hipHostFree(h_lanes);
@@ -135,6 +137,12 @@ int part_groupby_prepare(const Table *table, const llkv_filter *filters, uint32_
     HIP_TRY(hipMemcpyAsync(g->d_dict_num, image.data(), image.size() * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s)); // `image` is a local
   }
+  if (!p.code_bits.empty()) {
+    g->d_code_bits = (uint64_t *)scratch_alloc(p.code_bits.size() * 8);
+    if (!g->d_code_bits) return set_error(LLKV_INTERNAL, "device allocation failed");
+    HIP_TRY(hipMemcpyAsync(g->d_code_bits, p.code_bits.data(), p.code_bits.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
   // lane tables: ops of the kernel lanes (exchange lane j comes from kernel lane image_src[j], so that lane's op is
   // exchange lane j's), then source and transform per exchange lane
   const uint32_t k = (uint32_t)p.k;
@@ -153,7 +161,7 @@ int part_groupby_prepare(const Table *table, const llkv_filter *filters, uint32_
     std::vector<uint32_t> ranks((size_t)n_keys * 256, 0);
     for (uint32_t j = 0; j < n_keys; ++j) {
       const ColumnInfo &ci = table->cols.at(key_fields[j]).info;
-      if (ci.dtype != LLKV_DT_UTF8) continue;
+      if (ci.dtype != LLKV_DT_UTF8 || utf8_wide(ci)) continue; // (a wide key's code is its rank: no table, kl_keys.code_rank stays NULL)
       std::vector<uint32_t> idx(std::min<size_t>(ci.dictionary.size(), 256));
       for (size_t i = 0; i < idx.size(); ++i) idx[i] = (uint32_t)i;
       std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return ci.dictionary[a] < ci.dictionary[b]; });
@@ -215,6 +223,7 @@ int PartGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrde
   for (size_t i = 0; i < p.lit_f.size(); ++i) sp.lit_f[i] = p.lit_f[i];
   for (size_t i = 0; i < p.key_strides.size(); ++i) sp.key_stride[i] = p.key_strides[i];
   sp.dict_num = d_dict_num;
+  sp.code_bits = d_code_bits;
   sp.tiles = ts->d_tiles.get<TileDesc>();
   sp.n_tiles = n_tiles;
   sp.part_hist = cell_table.as<uint32_t>();
@@ -232,7 +241,8 @@ int PartGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrde
     kl_keys.card[j] = p.key_cards[j];
     kl_keys.nullable[j] = p.key_nullable[j];
     kl_keys.base[j] = p.key_bases[j];
-    kl_keys.code_rank[j] = d_code_rank && !p.key_is_int[j] ? d_code_rank + (size_t)j * 256 : nullptr;
+    const bool wide_key = utf8_wide(table->cols.at(p.key_fields[j]).info); // (its code is its rank: no table)
+    kl_keys.code_rank[j] = d_code_rank && !p.key_is_int[j] && !wide_key ? d_code_rank + (size_t)j * 256 : nullptr;
   }
   uint32_t n_groups = 0;
   Scratch lanes_d, kv_d, kvalid_d;

@@ -222,6 +222,11 @@ int key_column_of(const Table *t, uint32_t field, JoinKeyColumn *kc, long long *
   case LLKV_DT_UINT32: kc->width = 4; kc->is_signed = 0; *base = 0; *bits = 32; break;
   default: kc->width = 1; kc->is_signed = 0; *base = 0; *bits = 8; break; // dictionary codes
   }
+  if (utf8_wide(c.info)) { // 4-byte codes of a wide Utf8 column: the bits of the largest code
+    kc->width = 4;
+    *bits = 1;
+    while (*bits < 32 && ((c.info.dictionary.size() - 1) >> *bits)) ++*bits;
+  }
   if (c.info.has_stats && kc->is_signed) { // only the bits the value range needs are sorted
     *base = c.info.min_i;
     const unsigned __int128 range = (unsigned __int128)((__int128)c.info.max_i - (__int128)c.info.min_i);
@@ -347,7 +352,7 @@ int SortedGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOr
     if ((rc = key_column_of(table, key_fields[k], &ks.k[k], &base, &bits))) return rc;
     const uint8_t *code_rank = nullptr;
     const ColumnInfo &ci = table->cols.at(key_fields[k]).info;
-    if (order_by_keys && ci.dtype == LLKV_DT_UTF8) { // ORDER BY the key: codes sort as their strings do
+    if (order_by_keys && ci.dtype == LLKV_DT_UTF8 && !utf8_wide(ci)) { // ORDER BY the key: codes sort as their strings do (a wide code already does)
       std::vector<uint32_t> idx(ci.dictionary.size());
       std::iota(idx.begin(), idx.end(), 0u);
       std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return ci.dictionary[a] < ci.dictionary[b]; });

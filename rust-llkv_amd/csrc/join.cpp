@@ -29,6 +29,8 @@ int key_part(const Table *t, uint32_t field, const DeviceColumn **col, JoinKeyPa
   if (it == t->cols.end()) return set_error(LLKV_NOT_FOUND, "join key field " + std::to_string(field) + " not found");
   const DeviceColumn &c = it->second;
   if (c.info.wide128) return set_error(LLKV_UNSUPPORTED, "join key over Decimal128 values beyond 64 bits (field " + std::to_string(field) + ")");
+  if (utf8_wide(c.info))
+    return set_error(LLKV_UNSUPPORTED, "join key over the wide Utf8 column " + std::to_string(field) + " (" + std::to_string(c.info.dictionary.size()) + " distinct values, 4-byte codes) is not on the GPU path");
   *col = &c;
   std::memset(out, 0, sizeof *out);
   out->values = c.d_values.get();
@@ -511,6 +513,9 @@ struct SideOut {
       std::string err;
       int rc = lower_projection(resolve, pr, gn, &lp, &err, pad);
       if (rc) return set_error(rc, err);
+      for (uint32_t i = 0; i < gn; ++i)
+        if (lp.out_wide[i])
+          return set_error(LLKV_UNSUPPORTED, "joined batches with the wide Utf8 column " + std::to_string(fields[g0 + i]) + " (4-byte codes) are not on the GPU path");
       JitKernel k;
       if ((rc = jit_compile(JitKind::Project, lp.type_string, &k, &err))) return set_error(rc, err);
       for (uint32_t i = 0; i < gn; ++i) {

@@ -228,6 +228,7 @@ struct Lowering {
   bool whole_table_image = false; // partitioned route: one LDS image may receive every row of the table
   uint64_t table_rows = 0; // rows of the table the plan scans (the N of the exact sums)
   bool allow_dict_num = true; // the kernels of this plan see ScanParams::dict_num (not the sort route's reduce kernel)
+  bool allow_code_bits = false; // the launches of this plan bind ScanParams::code_bits (selections and fused / partitioned scans)
   bool allow_sorted_distinct = false; // reduce plans: DISTINCT aggregates over ONE Int64 / Float64 column (it sorts last)
   // shared-image plans: exchange lane j of a lane group = xf(kernel lane src) (LoweredPlan::image_src / image_xf); empty = as is
   std::vector<std::vector<std::pair<uint8_t, uint8_t>>> group_expand = {};
@@ -378,18 +379,21 @@ struct Lowering {
 
   int fail(int code, const std::string &m) { return set_err(err, code, m); }
 
-  int slot_of(uint32_t field, const ColumnInfo **ci_out, int *slot) {
+  // `wide_codes`: the caller reads a wide Utf8 column's 4-byte codes as such (string predicates, passthrough projections, GROUP BY keys)
+  int slot_of(uint32_t field, const ColumnInfo **ci_out, int *slot, bool wide_codes = false) {
     const ColumnInfo *ci = resolve(field);
     if (!ci) return fail(LLKV_NOT_FOUND, "field " + std::to_string(field) + " not found");
     *ci_out = ci;
     // every reader of a column's values comes through here: a wide Decimal128 column has no 8 B/row value image
     if (ci->wide128)
       return fail(LLKV_UNSUPPORTED, "Decimal128 values beyond 64 bits in field " + std::to_string(field) + ": only SUM / TOTAL / AVG / COUNT over the bare column are on the GPU path");
+    // … and the codes of a wide Utf8 column are no 1-byte codes: readers that do not know the form refuse
+    if (utf8_wide(*ci) && !wide_codes) return fail(LLKV_UNSUPPORTED, wide_utf8_refusal(*ci, "this operation"));
     for (size_t i = 0; i < p.slot_fields.size(); ++i)
       if (p.slot_fields[i] == field && !p.slot_is_valid[i]) { *slot = (int)i; return LLKV_OK; }
     if ((int)p.slot_fields.size() >= kMaxColsHost) return fail(LLKV_UNSUPPORTED, "plan touches more than 16 column buffers");
     p.slot_fields.push_back(field);
-    p.slot_dtypes.push_back(ci->dtype);
+    p.slot_dtypes.push_back(storage_dtype(*ci));
     p.slot_is_valid.push_back(0);
     *slot = (int)p.slot_fields.size() - 1;
     return LLKV_OK;
@@ -532,6 +536,116 @@ struct Lowering {
     return LLKV_OK;
   }
 
+  static std::string wide_utf8_refusal(const ColumnInfo &ci, const std::string &what) {
+    return what + " over the wide Utf8 column " + std::to_string(ci.field_id) + " (" + std::to_string(ci.dictionary.size()) +
+           " distinct values, 4-byte codes) is not on the GPU path";
+  }
+
+  // A leaf over a wide Utf8 column: its codes are positions in the byte-ordered dictionary, so
+  // =, <, <=, >, >=, BETWEEN and case-sensitive StartsWith select one code interval [lo, hi) (CodeRange, found by binary search);
+  // IN selects its codes (In up to kWideInCodes of them, else a bitmap); EndsWith, Contains and every case-insensitive pattern are
+  // evaluated once per dictionary string, with the rules of the 1-byte form, into a bitmap of dict_size bits (CodeBits).
+  static constexpr size_t kWideInCodes = 8;
+  int wide_code_leaf(const llkv_filter &f, const ColumnInfo *ci, std::string *out) {
+    const std::vector<std::string> &d = ci->dictionary;
+    const uint64_t n = d.size();
+    auto lit_str = [&](const llkv_literal &l, std::string *s) -> int {
+      if (l.tag != LLKV_LIT_STRING || !l.str) return fail(LLKV_PREDICATE_BUILD, std::string("literal cast error: expected string, got ") + lit_kind(l));
+      *s = l.str;
+      return LLKV_OK;
+    };
+    auto first_ge = [&](const std::string &s) { return (uint64_t)(std::lower_bound(d.begin(), d.end(), s) - d.begin()); };
+    auto first_gt = [&](const std::string &s) { return (uint64_t)(std::upper_bound(d.begin(), d.end(), s) - d.begin()); };
+    auto ascii = [](const std::string &x) { for (unsigned char ch : x) if (ch >= 0x80) return false; return true; };
+    auto lower = [](std::string x) { for (char &ch : x) if (ch >= 'A' && ch <= 'Z') ch = (char)(ch + 32); return x; };
+    int rc, slot;
+    std::vector<uint64_t> bits; // a bitmap leaf: bit c = code c qualifies
+    uint64_t lo = 0, hi = n;
+    std::string a, b;
+    const bool pattern_op = f.op == LLKV_OP_STARTS_WITH || f.op == LLKV_OP_ENDS_WITH || f.op == LLKV_OP_CONTAINS;
+    if (f.op == LLKV_OP_IN) {
+      std::vector<uint64_t> codes;
+      for (uint32_t i = 0; i < f.in_len; ++i) {
+        if ((rc = lit_str(f.in_list[i], &a))) return rc;
+        const uint64_t c = first_ge(a);
+        if (c < n && d[c] == a) codes.push_back(c);
+      }
+      std::sort(codes.begin(), codes.end());
+      codes.erase(std::unique(codes.begin(), codes.end()), codes.end());
+      if (codes.empty()) { *out = "False"; return LLKV_OK; }
+      if (codes.size() <= kWideInCodes || !allow_code_bits) {
+        std::string lits;
+        for (uint64_t c : codes) {
+          std::string lit;
+          if ((rc = lit_i((int64_t)c, &lit, "LitU"))) return rc;
+          lits += "," + lit;
+        }
+        if ((rc = slot_of(f.field_id, &ci, &slot, true))) return rc;
+        *out = "In<" + col_node(slot, storage_dtype(*ci)) + lits + ">";
+        return LLKV_OK;
+      }
+      bits.assign((n + 63) / 64, 0);
+      for (uint64_t c : codes) bits[c >> 6] |= 1ull << (c & 63);
+    } else if (pattern_op) { // Operator::{StartsWith, EndsWith, Contains} (typed_predicate.rs:186-210)
+      std::string pat;
+      if ((rc = lit_str(f.value, &pat))) return rc;
+      if (!f.case_sensitive) {
+        if (!ascii(pat)) return fail(LLKV_UNSUPPORTED, "case-insensitive pattern with non-ASCII characters (Unicode to_lowercase)");
+        pat = lower(pat);
+      }
+      if (f.op == LLKV_OP_STARTS_WITH && f.case_sensitive) { // the strings with this prefix follow each other in byte order
+        lo = first_ge(pat);
+        hi = (uint64_t)(std::partition_point(d.begin() + lo, d.end(), [&](const std::string &v) { return v.compare(0, pat.size(), pat) == 0; }) - d.begin());
+      } else {
+        bits.assign((n + 63) / 64, 0);
+        for (uint64_t c = 0; c < n; ++c) {
+          const std::string &v = d[c];
+          if (!f.case_sensitive && !ascii(v)) return fail(LLKV_UNSUPPORTED, "case-insensitive pattern over non-ASCII strings (Unicode to_lowercase)");
+          const std::string x = f.case_sensitive ? v : lower(v);
+          bool ok;
+          if (f.op == LLKV_OP_STARTS_WITH) ok = x.size() >= pat.size() && x.compare(0, pat.size(), pat) == 0;
+          else if (f.op == LLKV_OP_ENDS_WITH) ok = x.size() >= pat.size() && x.compare(x.size() - pat.size(), pat.size(), pat) == 0;
+          else ok = x.find(pat) != std::string::npos;
+          if (ok) bits[c >> 6] |= 1ull << (c & 63);
+        }
+      }
+    } else {
+      switch (f.op) {
+      case LLKV_OP_EQUALS: if ((rc = lit_str(f.value, &a))) return rc; lo = first_ge(a); hi = lo < n && d[lo] == a ? lo + 1 : lo; break;
+      case LLKV_OP_GT: if ((rc = lit_str(f.value, &a))) return rc; lo = first_gt(a); break;
+      case LLKV_OP_GE: if ((rc = lit_str(f.value, &a))) return rc; lo = first_ge(a); break;
+      case LLKV_OP_LT: if ((rc = lit_str(f.value, &a))) return rc; hi = first_ge(a); break;
+      case LLKV_OP_LE: if ((rc = lit_str(f.value, &a))) return rc; hi = first_gt(a); break;
+      case LLKV_OP_RANGE:
+        if (f.lower_kind != LLKV_BOUND_UNBOUNDED && (rc = lit_str(f.lower, &a))) return rc;
+        if (f.upper_kind != LLKV_BOUND_UNBOUNDED && (rc = lit_str(f.upper, &b))) return rc;
+        if (f.lower_kind == LLKV_BOUND_INCLUDED) lo = first_ge(a);
+        if (f.lower_kind == LLKV_BOUND_EXCLUDED) lo = first_gt(a);
+        if (f.upper_kind == LLKV_BOUND_INCLUDED) hi = first_gt(b);
+        if (f.upper_kind == LLKV_BOUND_EXCLUDED) hi = first_ge(b);
+        break;
+      default: return fail(LLKV_PREDICATE_BUILD, "unsupported operator for typed predicate: operator lacks string literal support");
+      }
+    }
+    if (bits.empty()) { // an interval
+      if (lo >= hi) { *out = "False"; return LLKV_OK; }
+      if (lo == 0 && hi == n) { *out = "True"; return LLKV_OK; } // every code (the leaf's NULL domain is added by the caller)
+      std::string l, h;
+      if ((rc = slot_of(f.field_id, &ci, &slot, true)) || (rc = lit_i((int64_t)lo, &l, "LitU")) || (rc = lit_i((int64_t)hi, &h, "LitU"))) return rc;
+      *out = "CodeRange<" + col_node(slot, storage_dtype(*ci)) + "," + l + "," + h + ">";
+      return LLKV_OK;
+    }
+    bool any = false;
+    for (uint64_t w : bits) any |= w != 0;
+    if (!any) { *out = "False"; return LLKV_OK; }
+    if (!allow_code_bits) return fail(LLKV_UNSUPPORTED, wide_utf8_refusal(*ci, "a pattern or long IN list predicate on this route"));
+    if ((rc = slot_of(f.field_id, &ci, &slot, true))) return rc;
+    const size_t at = p.code_bits.size();
+    p.code_bits.insert(p.code_bits.end(), bits.begin(), bits.end());
+    *out = "CodeBits<" + col_node(slot, storage_dtype(*ci)) + "," + std::to_string(at) + ">";
+    return LLKV_OK;
+  }
+
   // The value test of a leaf filter, NULL cells aside (llkv-table/src/table.rs:1117-1171).
   int leaf_values(const llkv_filter &f, std::string *out) {
     const ColumnInfo *ci = resolve(f.field_id);
@@ -559,6 +673,7 @@ struct Lowering {
     if (f.op == LLKV_OP_RANGE && f.lower_kind == LLKV_BOUND_UNBOUNDED && f.upper_kind == LLKV_BOUND_UNBOUNDED) { *out = "True"; return LLKV_OK; }
     int slot;
     int rc;
+    if (utf8_wide(*ci)) return wide_code_leaf(f, ci, out);
     if (ci->dtype == LLKV_DT_UTF8) { // dictionary codes: equality only
       auto code_of = [&](const llkv_literal &l, int *code) -> int {
         if (l.tag != LLKV_LIT_STRING || !l.str) return fail(LLKV_PREDICATE_BUILD, std::string("literal cast error: expected string, got ") + lit_kind(l));
@@ -1484,6 +1599,7 @@ static int lower_aggregates(Lowering &L, const ColumnResolver &resolve, const ll
       if (p.distinct_proj) return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates over more than one argument in a GROUP BY");
       const ColumnInfo *dci = resolve(s.expr[0].field_id);
       if (!dci) return L.fail(LLKV_INVALID_ARGUMENT, "unknown column '" + std::to_string(s.expr[0].field_id) + "' in aggregate");
+      if (utf8_wide(*dci)) return L.fail(LLKV_UNSUPPORTED, L.wide_utf8_refusal(*dci, "a DISTINCT aggregate"));
       // DistinctKey::from_array (llkv-aggregate/src/lib.rs:261-331): Int by value, Float by bits, Str by its string (here: its
       // dictionary code — the staged dictionary holds every string once), Bool, Date by its day number; what SUM / TOTAL / AVG
       // add for the last three is their numeric image in the Float64 accumulators (:400-449,889-924,1035-1066,1200-1232)
@@ -1595,6 +1711,7 @@ static int lower_aggregates(Lowering &L, const ColumnResolver &resolve, const ll
         return L.fail(LLKV_INVALID_ARGUMENT, std::string(fn) + " aggregate not supported for column type " + dtype_name(dt));
       const ColumnInfo *ci;
       int slot;
+      if (dt == LLKV_DT_UTF8 && utf8_wide(*resolve(s.expr[0].field_id))) return L.fail(LLKV_UNSUPPORTED, L.wide_utf8_refusal(*resolve(s.expr[0].field_id), fn));
       if ((rc = L.slot_of(s.expr[0].field_id, &ci, &slot))) return rc;
       if (dt == LLKV_DT_UTF8) {
         if (!L.allow_dict_num) return L.fail(LLKV_UNSUPPORTED, std::string(fn) + " over a Utf8 column is not on this route");
@@ -1839,6 +1956,7 @@ int lower_plan(const ColumnResolver &resolve, const llkv_filter *filters, uint32
   *out = LoweredPlan{};
   LoweredPlan &p = *out;
   Lowering L{resolve, p, err, grouped};
+  L.allow_code_bits = true; // (engine.cpp and group_part.cpp bind the bitmaps)
   p.grouped = grouped;
   if (image && !grouped) return L.fail(LLKV_INVALID_ARGUMENT, "the shared-image kernel serves GROUP BY plans");
   if (partitioned && !image) return L.fail(LLKV_INVALID_ARGUMENT, "the partitioned route uses the shared-image lowering");
@@ -1879,7 +1997,9 @@ int lower_plan(const ColumnResolver &resolve, const llkv_filter *filters, uint32
         const unsigned __int128 range = (unsigned __int128)((__int128)probe->max_i - (__int128)probe->min_i) + 1;
         if (range > (image ? max_groups : 256u)) return L.fail(LLKV_UNSUPPORTED, "integer GROUP BY key spans more than " + std::to_string(image ? max_groups : 256u) + " values (sort-based route)");
       }
-      if ((rc = L.slot_of(key_fields[k], &ci, &slot))) return rc;
+      // a wide Utf8 key: its code is its dense id (4-byte codes in string order), for the shared-image and partitioned routes
+      if (utf8_wide(*probe) && !image) return L.fail(LLKV_UNSUPPORTED, L.wide_utf8_refusal(*probe, "a GROUP BY key on this route"));
+      if ((rc = L.slot_of(key_fields[k], &ci, &slot, true))) return rc;
       L.table_rows = std::max(L.table_rows, ci->rows);
       uint32_t card;
       std::string node;
@@ -1890,7 +2010,7 @@ int lower_plan(const ColumnResolver &resolve, const llkv_filter *filters, uint32
         node = "KeyInt<" + std::to_string(slot) + "," + dtype_tag(ci->dtype) + "," + base + ">";
       } else {
         card = (uint32_t)(ci->dictionary.empty() ? 1 : ci->dictionary.size());
-        node = "KeyCode<" + std::to_string(slot) + ">";
+        node = (utf8_wide(*ci) ? "KeyCode32<" : "KeyCode<") + std::to_string(slot) + ">";
       }
       // GroupKeyValue::Null is a group of its own (llkv-executor/src/lib.rs:99-106,9362-9456): one more code
       std::string kv;
@@ -2041,6 +2161,7 @@ int lower_selection(const ColumnResolver &resolve, const llkv_filter *filters, u
                     LoweredPlan *out, std::string *err) {
   *out = LoweredPlan{};
   Lowering L{resolve, *out, err, false};
+  L.allow_code_bits = true; // (run_selection_lowered binds the bitmaps)
   std::string pred;
   int rc = L.predicate(filters, n_filters, ops, n_ops, &pred);
   if (rc) return rc;
@@ -2199,12 +2320,13 @@ int lower_projection(const ColumnResolver &resolve, const llkv_projection *proje
       int slot;
       if ((rc = wide_column(pr.field_id, &node, &ci)) > 0) return rc;
       if (rc < 0) {
-        if ((rc = L.slot_of(pr.field_id, &ci, &slot))) return rc;
+        if ((rc = L.slot_of(pr.field_id, &ci, &slot, true))) return rc;
         if (dtype_width(ci->dtype) == 0) return L.fail(LLKV_UNSUPPORTED, std::string("projection of ") + dtype_name(ci->dtype));
-        node = L.col_node(slot, ci->dtype);
+        node = L.col_node(slot, storage_dtype(*ci));
         if (ci->dtype == LLKV_DT_DECIMAL128) node = "Widen128<" + node + ">"; // back to arrow's 16-byte raw values
       }
       out->out_dtypes.push_back(ci->dtype);
+      out->out_wide.push_back(utf8_wide(*ci) ? 1 : 0);
       out->out_fields.push_back((int32_t)pr.field_id);
       std::string v;
       if ((rc = L.valid_of_field(pr.field_id, &v))) return rc;
@@ -2220,11 +2342,12 @@ int lower_projection(const ColumnResolver &resolve, const llkv_projection *proje
         int slot;
         if ((rc = wide_column(pr.expr[0].field_id, &node, &ci)) > 0) return rc;
         if (rc < 0) {
-          if ((rc = L.slot_of(pr.expr[0].field_id, &ci, &slot))) return rc;
-          node = L.col_node(slot, ci->dtype);
+          if ((rc = L.slot_of(pr.expr[0].field_id, &ci, &slot, true))) return rc;
+          node = L.col_node(slot, storage_dtype(*ci));
           if (ci->dtype == LLKV_DT_DECIMAL128) node = "Widen128<" + node + ">";
         }
         out->out_dtypes.push_back(ci->dtype);
+        out->out_wide.push_back(utf8_wide(*ci) ? 1 : 0);
         out->out_fields.push_back((int32_t)pr.expr[0].field_id);
       } else {
         L.exact_nan = true; // the consumer sees the bits of a projected value
@@ -2233,6 +2356,7 @@ int lower_projection(const ColumnResolver &resolve, const llkv_projection *proje
         if (rc) return rc;
         if (L.last_fast_32) node = std::string("Narrow32<") + node + (L.last_fast_32 == 1 ? ",I32>" : ",U32>");
         out->out_dtypes.push_back(is_f64 ? LLKV_DT_FLOAT64 : L.last_fast_32 == 1 ? LLKV_DT_INT32 : L.last_fast_32 == 2 ? LLKV_DT_UINT32 : LLKV_DT_INT64);
+        out->out_wide.push_back(0);
         out->out_fields.push_back(-1);
       }
       std::string v;

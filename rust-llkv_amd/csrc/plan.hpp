@@ -43,6 +43,14 @@ struct ColumnInfo {
   uint64_t wide_min_hi = 0, wide_min_lo = 0, wide_max_hi = 0, wide_max_lo = 0; // i128 smallest / largest value of a wide128 column (every cell, NULL ones too)
 };
 
+// A Utf8 column of more than kNarrowDictMax distinct strings is staged in the wide form: 4-byte codes, code c = the position of
+// its string in the dictionary sorted by bytes (str::cmp).  At most kNarrowDictMax strings: 1-byte codes in first-appearance
+// order.  The width follows from the dictionary alone; every "is this column wide" question asks utf8_wide.
+constexpr size_t kNarrowDictMax = 256;
+inline bool utf8_wide(const ColumnInfo &ci) { return ci.dtype == LLKV_DT_UTF8 && ci.dictionary.size() > kNarrowDictMax; }
+// what the device image of a column holds per row, as a dtype (a wide Utf8 column: UInt32 codes)
+inline int32_t storage_dtype(const ColumnInfo &ci) { return utf8_wide(ci) ? LLKV_DT_UINT32 : ci.dtype; }
+
 using ColumnResolver = std::function<const ColumnInfo *(uint32_t field_id)>;
 
 enum class AggFinal : int {
@@ -88,7 +96,7 @@ struct LoweredPlan {
   std::string type_string;            // "Plan<Cols<...>,<pred>,Keys<...>,Aggs<...>,U>"
   std::vector<uint32_t> slot_fields;  // slot → field id
   bool late_columns = false;          // register-state plan whose argument-only columns are read for the passing rows (Plan::EARLY)
-  std::vector<int32_t> slot_dtypes;   // slot → llkv_dtype (UTF8 = 1-byte codes)
+  std::vector<int32_t> slot_dtypes;   // slot → storage dtype (UTF8 = 1-byte codes, UINT32 for the codes of a wide Utf8 column)
   std::vector<uint8_t> slot_is_valid; // what of the field the slot reads: 0 its values, 1 its validity mask (1 B/row), 2 the high halves of a wide Decimal128 column
   std::vector<int64_t> lit_i;
   std::vector<double> lit_f;
@@ -127,11 +135,14 @@ struct LoweredPlan {
   uint64_t bytes_per_row = 0;    // algorithmic bytes (value buffers, once)
   bool always_false = false;     // predicate folded to FALSE on the host
   bool always_true = false;      // selection plans: predicate folded to TRUE
-  std::vector<int32_t> out_dtypes; // projection plans: storage dtype of each output
+  std::vector<int32_t> out_dtypes; // projection plans: dtype of each output (a wide Utf8 passthrough: UTF8, 4-byte codes — out_wide)
+  std::vector<uint8_t> out_wide;   // projection plans: the output is a wide Utf8 column's u32 codes
   std::vector<int32_t> out_fields; // projection plans: source field of a passthrough column, else -1
   std::vector<uint8_t> out_nullable; // projection plans: the output carries a validity bitmap
   // slots whose dictionary codes some aggregate reads as numbers (DictNum<slot>): slot → 256 values (code → f64)
   std::vector<std::pair<int, std::vector<double>>> dict_num;
+  // bitmaps of the CodeBits leaves over wide Utf8 columns (ScanParams::code_bits): leaf at word offset S, bit c = code c qualifies
+  std::vector<uint64_t> code_bits;
 };
 
 // `str.trim().parse::<f64>().unwrap_or(0.0)` of the reference's numeric coercion (llkv-aggregate/src/lib.rs:426-434):

@@ -7,6 +7,8 @@
 
 namespace {
 thread_local std::string g_plan_err;
+thread_local std::vector<int64_t> g_last_lit_i;     // banks of the plan this thread lowered last (llkv_plan_last_banks)
+thread_local std::vector<uint64_t> g_last_code_bits;
 }
 
 extern "C" {
@@ -38,6 +40,13 @@ llkv_status llkv_plan_lower(const llkv_column_desc *cols, uint32_t n_cols, const
     infos[i].f_all_finite = cols[i].f_all_finite != 0;
     for (uint32_t d = 0; d < cols[i].dict_size; ++d)
       infos[i].dictionary.push_back(cols[i].dictionary && cols[i].dictionary[d] ? cols[i].dictionary[d] : "");
+    // a wide Utf8 column's codes are positions in its byte-ordered dictionary: the descriptor must list it so
+    if (llkv::utf8_wide(infos[i]))
+      for (size_t d = 1; d < infos[i].dictionary.size(); ++d)
+        if (!(infos[i].dictionary[d - 1] < infos[i].dictionary[d])) {
+          g_plan_err = "the dictionary of wide Utf8 field " + std::to_string(infos[i].field_id) + " is not sorted by bytes without duplicates (entry " + std::to_string(d) + ")";
+          return LLKV_INVALID_ARGUMENT;
+        }
   }
   auto resolve = [&](uint32_t fid) -> const llkv::ColumnInfo * {
     for (auto &c : infos) if (c.field_id == fid) return &c;
@@ -47,12 +56,22 @@ llkv_status llkv_plan_lower(const llkv_column_desc *cols, uint32_t n_cols, const
   g_plan_err.clear();
   int rc = llkv::lower_plan(resolve, filters, n_filters, ops, n_ops, key_fields, n_keys, aggs, n_aggs, (grouped & 1) != 0, (grouped & 2) == 0, &plan, &g_plan_err, (grouped & 4) != 0, (grouped & 8) != 0);
   if (rc) return (llkv_status)rc;
+  g_last_lit_i = plan.lit_i;
+  g_last_code_bits = plan.code_bits;
   if (type_string_out && type_string_cap) {
     if (plan.type_string.size() + 1 > type_string_cap) { g_plan_err = "type string buffer too small"; return LLKV_INVALID_ARGUMENT; }
     std::memcpy(type_string_out, plan.type_string.c_str(), plan.type_string.size() + 1);
   }
   if (lanes_out) *lanes_out = (uint32_t)plan.lanes;
   if (bytes_per_row_out) *bytes_per_row_out = plan.bytes_per_row;
+  return LLKV_OK;
+}
+
+llkv_status llkv_plan_last_banks(int64_t *lit_i, uint32_t lit_cap, uint32_t *n_lit, uint64_t *code_bits, uint64_t bits_cap, uint64_t *n_bits) {
+  if (n_lit) *n_lit = (uint32_t)g_last_lit_i.size();
+  if (n_bits) *n_bits = g_last_code_bits.size();
+  for (size_t i = 0; lit_i && i < g_last_lit_i.size() && i < lit_cap; ++i) lit_i[i] = g_last_lit_i[i];
+  for (size_t i = 0; code_bits && i < g_last_code_bits.size() && i < bits_cap; ++i) code_bits[i] = g_last_code_bits[i];
   return LLKV_OK;
 }
 

@@ -135,6 +135,8 @@ struct ScanParams {
   uint32_t rk_shift, rk_chunks;
   uint32_t *rk_prefix, *rk_base, *rk_state;
   uint32_t rk_help_first, rk_helpers;
+  // CodeBits leaves over wide Utf8 columns (fused_scan.hip.h): the plan's bitmaps back to back (LoweredPlan::code_bits)
+  const uint64_t *code_bits;
 };
 
 constexpr int kMaxOuts = 8;

@@ -54,6 +54,13 @@ int run_selection_lowered(const Table *t, const LoweredPlan &plan, Selection *se
   for (size_t s = 0; s < plan.slot_fields.size(); ++s) p.col[s] = slot_buffer(t->cols, plan, s);
   for (size_t i = 0; i < plan.lit_i.size(); ++i) p.lit_i[i] = plan.lit_i[i];
   for (size_t i = 0; i < plan.lit_f.size(); ++i) p.lit_f[i] = plan.lit_f[i];
+  DeviceBuf code_bits; // bitmaps of CodeBits leaves (wide Utf8 columns)
+  if (!plan.code_bits.empty()) {
+    if ((rc = code_bits.alloc(plan.code_bits.size() * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(code_bits.p, plan.code_bits.data(), plan.code_bits.size() * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream)); // (the source is pageable)
+    p.code_bits = code_bits.as<uint64_t>();
+  }
   p.tiles = ts->d_tiles.get<TileDesc>();
   p.n_tiles = ts->n_tiles;
   p.sub_rows = kSelectTileRows / (kBlock / 64);
@@ -162,6 +169,7 @@ static int sort_selection(const Table *t, const llkv_scan_options *o, Selection 
   const uint8_t *code_rank = nullptr;
   if (c.info.dtype == LLKV_DT_INT64) { kc.width = 8; kc.is_signed = 1; base = INT64_MIN; }
   else if (c.info.dtype == LLKV_DT_INT32) { kc.width = 4; kc.is_signed = 1; base = INT32_MIN; }
+  else if (utf8_wide(c.info)) { kc.width = 4; kc.is_signed = 0; } // wide codes are positions in the byte-ordered dictionary: the code is the key
   else { // dictionary codes sort as their strings do (str::cmp)
     kc.width = 1;
     std::vector<uint32_t> idx(c.info.dictionary.size());
@@ -288,6 +296,7 @@ llkv_status llkv_hip_scan_stream(const llkv_hip_table *table, const llkv_project
 
   hipStream_t stream = g_ctx.stream;
   const uint32_t n_out = (uint32_t)proj.out_dtypes.size();
+  auto out_width = [&](uint32_t o) -> size_t { return proj.out_wide[o] ? 4 : dtype_out_width(proj.out_dtypes[o]); }; // (wide Utf8: u32 codes)
   const bool with_ids = options && options->include_row_ids;
   // Two buffers of up to kSuper reference windows each: one gather launch and one copy per output fill a buffer
   // (65 536-row launches and 512 KB copies leave the PCIe link half idle), the host then hands out its windows
@@ -311,7 +320,7 @@ llkv_status llkv_hip_scan_stream(const llkv_hip_table *table, const llkv_project
   for (auto &w : win) {
     if ((rc = w.d_err.alloc(kSuper * 4)) || (rc = w.h_err.alloc(kSuper * 4))) return (llkv_status)rc;
     for (uint32_t o = 0; o < n_out; ++o) {
-      const size_t bytes = (size_t)buf_rows * dtype_out_width(proj.out_dtypes[o]);
+      const size_t bytes = (size_t)buf_rows * out_width(o);
       if ((rc = w.d[o].alloc(bytes)) || (rc = w.h[o].alloc(bytes))) return (llkv_status)rc;
       if (proj.out_nullable[o] && ((rc = w.d_valid[o].alloc(buf_rows / 8)) || (rc = w.h_valid[o].alloc(buf_rows / 8)))) return (llkv_status)rc;
     }
@@ -337,7 +346,7 @@ llkv_status llkv_hip_scan_stream(const llkv_hip_table *table, const llkv_project
     if (r) return r;
     for (uint32_t o = 0; o < n_out; ++o)
     {
-      HIP_TRY(hipMemcpyAsync(w.h[o].p, w.d[o].p, (size_t)w.n * dtype_out_width(proj.out_dtypes[o]), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(w.h[o].p, w.d[o].p, (size_t)w.n * out_width(o), hipMemcpyDeviceToHost, stream));
       if (proj.out_nullable[o]) HIP_TRY(hipMemcpyAsync(w.h_valid[o].p, w.d_valid[o].p, (size_t)((w.n + 63) / 64) * 8, hipMemcpyDeviceToHost, stream));
     }
     if (with_ids) HIP_TRY(hipMemcpyAsync(w.h_ids.p, sel.d_ids + w0, (size_t)w.n * 8, hipMemcpyDeviceToHost, stream));
@@ -366,10 +375,11 @@ llkv_status llkv_hip_scan_stream(const llkv_hip_table *table, const llkv_project
       llkv_column_view cols[kMaxOuts];
       for (uint32_t o = 0; o < n_out; ++o) {
         cols[o].dtype = proj.out_dtypes[o];
-        cols[o].values = (const char *)w.h[o].p + r0 * dtype_out_width(proj.out_dtypes[o]);
+        cols[o].values = (const char *)w.h[o].p + r0 * out_width(o);
         cols[o].validity = proj.out_nullable[o] ? (const uint8_t *)w.h_valid[o].p + r0 / 8 : nullptr;
         cols[o].dictionary = dicts[o].empty() ? nullptr : dicts[o].data();
         cols[o].precision = cols[o].scale = 0;
+        if (proj.out_wide[o]) cols[o].precision = 4; // u32 codes of a wide Utf8 column
         if (proj.out_dtypes[o] == LLKV_DT_DECIMAL128 && proj.out_fields[o] >= 0) {
           const ColumnInfo &ci = t->cols.at((uint32_t)proj.out_fields[o]).info;
           cols[o].precision = ci.precision;

@@ -10,7 +10,10 @@
 #include <chrono>
 #include <cstring>
 #include <map>
+#include <string_view>
 #include <thread>
+#include <unordered_map>
+#include <unordered_set>
 
 namespace llkv {
 
@@ -378,6 +381,65 @@ static int encode_utf8(const ChunkRun &run, const int32_t *const *offsets, const
   });
 }
 
+// The distinct strings of a run in order of first appearance (each chunk's own list in parallel, merged in chunk order): what
+// decides the form of a column staged with LLKV_UTF8_WIDE_CODES, and its dictionary.  Hash sets: a std::map of millions of
+// strings is too slow here.
+static int collect_utf8_words(const ChunkRun &run, const int32_t *const *offsets, const uint8_t *const *data, std::vector<std::string> *words) {
+  for (uint32_t i = 0; i < run.n; ++i)
+    if (run.rows[i] && (!offsets[i] || !data[i])) return set_error(LLKV_INVALID_ARGUMENT, "chunk pointer is NULL");
+  std::vector<std::vector<std::string_view>> seen(run.n);
+  int rc = for_each_chunk_parallel(run.n, [&](uint32_t i) -> int {
+    const int32_t *off = offsets[i];
+    std::unordered_set<std::string_view> local;
+    for (uint64_t r = 0; r < run.rows[i]; ++r) {
+      if (off[r + 1] < off[r]) return set_error(LLKV_INVALID_ARGUMENT, "Utf8 offsets must not descend");
+      const std::string_view s((const char *)data[i] + off[r], (size_t)(off[r + 1] - off[r]));
+      if (local.insert(s).second) seen[i].push_back(s);
+    }
+    return LLKV_OK;
+  });
+  if (rc) return rc;
+  std::unordered_set<std::string_view> all;
+  for (auto &chunk : seen)
+    for (std::string_view s : chunk)
+      if (all.insert(s).second) words->emplace_back(s);
+  return LLKV_OK;
+}
+
+// Utf8 → 4 B/row codes of the wide form (more than kNarrowDictMax distinct strings) in `codes`, image_rows() + 16 words,
+// padding rows and the tail zero.  Code c = the position of its string in `dict`, which is sorted by bytes; a string outside it
+// is refused with `miss_status` and `miss` (+ the string).  Chunk-parallel, through a hash map.
+static int encode_utf8_wide(const ChunkRun &run, const int32_t *const *offsets, const uint8_t *const *data, const std::vector<std::string> &dict,
+                            int miss_status, const std::string &miss, uint32_t *codes) {
+  for (uint32_t i = 0; i < run.n; ++i) {
+    if (run.rows[i] && (!offsets[i] || !data[i])) return set_error(LLKV_INVALID_ARGUMENT, "chunk pointer is NULL");
+    const uint64_t end = run.dst[i] + run.rows[i];
+    std::memset(codes + end, 0, (run.dst[i + 1] - end) * 4);
+  }
+  std::memset(codes + run.image_rows(), 0, 16 * 4);
+  const auto descending = [] { return set_error(LLKV_INVALID_ARGUMENT, "Utf8 offsets must not descend"); };
+  auto str_at = [&](uint32_t i, uint64_t r) { return std::string_view((const char *)data[i] + offsets[i][r], (size_t)(offsets[i][r + 1] - offsets[i][r])); };
+  std::unordered_map<std::string_view, uint32_t> code_of;
+  code_of.reserve(dict.size());
+  for (size_t c = 0; c < dict.size(); ++c) code_of.emplace(dict[c], (uint32_t)c);
+  return for_each_chunk_parallel(run.n, [&](uint32_t i) -> int {
+    const int32_t *off = offsets[i];
+    uint32_t *dst = codes + run.dst[i];
+    int64_t lut[256]; // 1-byte strings (flags): one lookup per byte value
+    std::fill(std::begin(lut), std::end(lut), (int64_t)-1);
+    for (uint64_t r = 0; r < run.rows[i]; ++r) {
+      if (off[r + 1] < off[r]) return descending();
+      const std::string_view s = str_at(i, r);
+      if (s.size() == 1 && lut[(uint8_t)s[0]] >= 0) { dst[r] = (uint32_t)lut[(uint8_t)s[0]]; continue; }
+      auto it = code_of.find(s);
+      if (it == code_of.end()) return set_error(miss_status, miss + " '" + std::string(s) + "'");
+      dst[r] = it->second;
+      if (s.size() == 1) lut[(uint8_t)s[0]] = it->second;
+    }
+    return LLKV_OK;
+  });
+}
+
 // Decimal128 (lo, hi) pairs → the 8 B/row image of the low halves in `lo` (image_rows() + 16, padding rows zero); *wide: some
 // value needs more than 64 bits.  Given `hi`, a wide run also gets the image of its high halves there and the values'
 // min / max / max|v| in `info`.
@@ -562,17 +624,66 @@ llkv_status llkv_hip_table_append_column(llkv_hip_table *table, uint32_t field_i
 llkv_status llkv_hip_table_append_utf8_column(llkv_hip_table *table, uint32_t field_id,
                                               const int32_t *const *chunk_offsets, const uint8_t *const *chunk_data,
                                               uint32_t n_chunks, const char *const *dictionary, uint32_t dict_size) {
+  return llkv_hip_table_append_utf8_column_ex(table, field_id, chunk_offsets, chunk_data, n_chunks, dictionary, dict_size, 0);
+}
+
+// The wide form (LLKV_UTF8_WIDE_CODES, more than kNarrowDictMax distinct strings): u32 codes in byte order of the strings.
+// `dictionary` (sorted here), or NULL: the run's strings.
+// `words`: the supplied dictionary, or the column's strings (collect_utf8_words); sorted here.
+static int stage_utf8_wide(Table *t, DeviceColumn &c, const int32_t *const *chunk_offsets, const uint8_t *const *chunk_data,
+                           std::vector<std::string> words) {
+  const bool trace = std::getenv("LLKV_HIP_TRACE") != nullptr;
+  auto t_last = std::chrono::steady_clock::now();
+  auto mark = [&](const char *what) {
+    if (!trace) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[llkv utf8 staging] %-18s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+    t_last = now;
+  };
+  c.info.dictionary = std::move(words);
+  std::sort(c.info.dictionary.begin(), c.info.dictionary.end());
+  for (size_t d = 1; d < c.info.dictionary.size(); ++d)
+    if (c.info.dictionary[d] == c.info.dictionary[d - 1]) return set_error(LLKV_INVALID_ARGUMENT, "duplicate dictionary entry '" + c.info.dictionary[d] + "'");
+  PinnedBuf codes;
+  int rc;
+  if ((rc = codes.alloc(((size_t)t->dev_rows + 16) * 4))) return rc;
+  if ((rc = encode_utf8_wide(local_run(*t), chunk_offsets, chunk_data, c.info.dictionary, LLKV_INVALID_ARGUMENT,
+                             "value is not in the supplied dictionary:", static_cast<uint32_t *>(codes.p))))
+    return rc;
+  mark("wide codes");
+  if ((rc = alloc_column(*t, 4, c.d_values))) return rc;
+  if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) return set_error(LLKV_INTERNAL, "staging copy failed");
+  if ((rc = stage_from_pinned(c.d_values.get(), codes.p, (size_t)t->dev_rows * 4))) return rc;
+  mark("copy");
+  return LLKV_OK;
+}
+
+llkv_status llkv_hip_table_append_utf8_column_ex(llkv_hip_table *table, uint32_t field_id,
+                                                 const int32_t *const *chunk_offsets, const uint8_t *const *chunk_data,
+                                                 uint32_t n_chunks, const char *const *dictionary, uint32_t dict_size, uint32_t flags) {
   Table *t = reinterpret_cast<Table *>(table);
   int rc = check_new_column(t, field_id, n_chunks);
   if (rc) return (llkv_status)rc;
+  if (flags & ~LLKV_UTF8_WIDE_CODES) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "unknown Utf8 staging flags");
+  const bool wide_ok = (flags & LLKV_UTF8_WIDE_CODES) != 0;
   if (!dictionary && t->world > 1)
     return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "sharded Utf8 columns need a table-wide dictionary (ranks must agree on the codes)");
-  if (dict_size > 256) return (llkv_status)set_error(LLKV_UNSUPPORTED, "Utf8 column has more than 256 distinct values");
+  if (dict_size > kNarrowDictMax && !wide_ok) return (llkv_status)set_error(LLKV_UNSUPPORTED, "Utf8 column has more than 256 distinct values");
   if ((rc = ensure_device())) return (llkv_status)rc;
   DeviceColumn c;
   c.info.field_id = field_id;
   c.info.dtype = LLKV_DT_UTF8;
   c.info.rows = t->total_rows;
+  // the dictionary: the supplied one, or — opted in, none supplied — the column's strings in order of first appearance (one pass
+  // decides the form: the 1-byte coder then codes them exactly as it would have found them)
+  std::vector<std::string> given;
+  if (dictionary) for (uint32_t d = 0; d < dict_size; ++d) given.emplace_back(dictionary[d] ? dictionary[d] : "");
+  else if (wide_ok && (rc = collect_utf8_words(local_run(*t), chunk_offsets, chunk_data, &given))) return (llkv_status)rc;
+  if (given.size() > kNarrowDictMax) {
+    if ((rc = stage_utf8_wide(t, c, chunk_offsets, chunk_data, std::move(given)))) return (llkv_status)rc;
+    t->cols.emplace(field_id, std::move(c));
+    return LLKV_OK;
+  }
   const bool trace = std::getenv("LLKV_HIP_TRACE") != nullptr;
   auto t_last = std::chrono::steady_clock::now();
   auto mark = [&](const char *what) {
@@ -586,9 +697,9 @@ llkv_status llkv_hip_table_append_utf8_column(llkv_hip_table *table, uint32_t fi
   PinnedBuf codes;
   if (codes.alloc((size_t)t->dev_rows + 16)) return (llkv_status)set_error(LLKV_INTERNAL, "no pinned host memory for the dictionary codes");
   std::map<std::string, uint8_t> dict;
-  const bool fixed = dictionary != nullptr;
-  for (uint32_t d = 0; d < dict_size && fixed; ++d) {
-    std::string s = dictionary[d] ? dictionary[d] : "";
+  const bool fixed = dictionary != nullptr || wide_ok;
+  for (uint32_t d = 0; d < given.size(); ++d) {
+    const std::string &s = given[d];
     if (!dict.emplace(s, (uint8_t)d).second) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "duplicate dictionary entry '" + s + "'");
     c.info.dictionary.push_back(s);
   }
@@ -875,8 +986,15 @@ static int append_chunks_impl(Table *t, const uint64_t *chunk_rows, uint32_t n_n
     const llkv_column_chunks &in = *by_field[kv.first];
     Prepared &p = prep[kv.first];
     if (c.info.wide128) return set_error(LLKV_UNSUPPORTED, "append to a Decimal128 column with values beyond 64 bits: re-stage it");
-    const uint32_t w = dtype_width(c.info.dtype);
-    if (c.info.dtype == LLKV_DT_UTF8) {
+    const uint32_t w = dtype_width(storage_dtype(c.info));
+    if (utf8_wide(c.info)) { // the wide form: the new rows' strings must be in the dictionary already (a new one would move codes)
+      if (!in.offsets || !in.data) return set_error(LLKV_INVALID_ARGUMENT, "Utf8 field " + std::to_string(kv.first) + " needs offsets and data");
+      if ((rc = p.codes.alloc((span + 16) * 4)) ||
+          (rc = encode_utf8_wide(run, in.offsets, in.data, c.info.dictionary, LLKV_UNSUPPORTED,
+                                 "the append brings a new string into the wide Utf8 field " + std::to_string(kv.first) + " (re-stage the column):",
+                                 static_cast<uint32_t *>(p.codes.p))))
+        return rc;
+    } else if (c.info.dtype == LLKV_DT_UTF8) {
       if (!in.offsets || !in.data) return set_error(LLKV_INVALID_ARGUMENT, "Utf8 field " + std::to_string(kv.first) + " needs offsets and data");
       std::map<std::string, uint8_t> dict;
       for (size_t d = 0; d < c.info.dictionary.size(); ++d) dict.emplace(c.info.dictionary[d], (uint8_t)d);
@@ -931,7 +1049,7 @@ static int append_chunks_impl(Table *t, const uint64_t *chunk_rows, uint32_t n_n
   };
   for (auto &kv : t->cols) {
     DeviceColumn &c = kv.second;
-    if ((rc = want_room(c.d_values, dtype_width(c.info.dtype), 0))) return rc;
+    if ((rc = want_room(c.d_values, dtype_width(storage_dtype(c.info)), 0))) return rc;
     if (!prep[kv.first].mask.empty() && (rc = want_room(c.d_valid, 1, 1))) return rc;
   }
   if (want_id_image && (rc = want_room(t->d_row_ids, 8, 0))) return rc;
@@ -948,10 +1066,10 @@ static int append_chunks_impl(Table *t, const uint64_t *chunk_rows, uint32_t n_n
   for (auto &kv : t->cols) {
     DeviceColumn &c = kv.second;
     Prepared &p = prep[kv.first];
-    const uint32_t w = dtype_width(c.info.dtype);
+    const uint32_t w = dtype_width(storage_dtype(c.info));
     char *image = c.d_values.get<char>() + old_dev_rows * w; // (the new chunks' rows)
     if (c.info.dtype == LLKV_DT_UTF8) {
-      if ((rc = stage_from_pinned(image, p.codes.p, (size_t)span))) return rc;
+      if ((rc = stage_from_pinned(image, p.codes.p, (size_t)span * w))) return rc;
       for (std::string &wd : p.new_words) c.info.dictionary.push_back(wd);
     } else if (c.info.dtype == LLKV_DT_DECIMAL128) {
       if ((rc = stage_to_device({{image, p.narrow.data(), (size_t)span * 8}}))) return rc;

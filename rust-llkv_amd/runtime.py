@@ -371,10 +371,13 @@ class HipTable:
         ptrs = (C.c_void_p * max(1, len(bitmaps)))(*[b.ctypes.data for b in bitmaps])
         check(lib().llkv_hip_table_set_column_validity(self._h, C.c_uint32(field_id), ptrs, C.c_uint32(len(bitmaps))))
 
-    def append_utf8_column(self, field_id: int, strings: Union[np.ndarray, Sequence], dictionary: Optional[Sequence[str]] = None, valid=None):
+    def append_utf8_column(self, field_id: int, strings: Union[np.ndarray, Sequence], dictionary: Optional[Sequence[str]] = None, valid=None,
+                           wide: bool = False):
         """Stage a Utf8 column.  ``strings`` is either a uint8 array of 1-byte strings (Arrow
         offsets are then 0..n) or a sequence of Python strings.  ``dictionary`` fixes the codes
-        (required for sharded tables: every rank must pass the same table-wide dictionary)."""
+        (required for sharded tables: every rank must pass the same table-wide dictionary).
+        ``wide``: more than 256 distinct strings may be staged, as 4-byte codes in byte order of
+        the strings (abi.UTF8_WIDE_CODES); with at most 256 the column is staged as without it."""
         chunks_off, chunks_data = [], []
         if isinstance(strings, np.ndarray) and strings.dtype == np.uint8:
             ramp = np.arange(max(self.local_chunk_rows, default=0) + 1, dtype=np.int32)  # offsets 0..n of any chunk
@@ -402,7 +405,8 @@ class HipTable:
         else:
             enc = [d.encode() for d in dictionary]
             dptr, dn = (C.c_char_p * max(1, len(enc)))(*enc), len(enc)
-        check(lib().llkv_hip_table_append_utf8_column(self._h, C.c_uint32(field_id), poff, pdat, C.c_uint32(len(chunks_off)), dptr, C.c_uint32(dn)))
+        check(lib().llkv_hip_table_append_utf8_column_ex(self._h, C.c_uint32(field_id), poff, pdat, C.c_uint32(len(chunks_off)), dptr, C.c_uint32(dn),
+                                                         C.c_uint32(abi.UTF8_WIDE_CODES if wide else 0)))
         self._utf8_fields.add(field_id)
         if valid is not None:
             self.set_column_validity(field_id, valid)
@@ -814,8 +818,9 @@ def decode_view_column(c, n: int) -> list:
     if c.dtype == abi.DT_DECIMAL128:
         raw = np.frombuffer(C.string_at(c.values, n * 16), dtype=np.uint64).reshape(n, 2)
         vals = [abi.i128_from_words(int(lo), int(np.int64(hi))) for lo, hi in raw]
-    elif c.dtype == abi.DT_UTF8:
-        codes = np.frombuffer(C.string_at(c.values, n), dtype=np.uint8)
+    elif c.dtype == abi.DT_UTF8:  # 1-byte codes, or u32 codes of a wide column (precision 4)
+        wide = c.precision == abi.UTF8_WIDE_VIEW_PRECISION
+        codes = np.frombuffer(C.string_at(c.values, n * (4 if wide else 1)), dtype=np.uint32 if wide else np.uint8)
         vals = [c.dictionary[int(k)].decode() for k in codes] if not c.validity else None
         if vals is None:  # a NULL cell's code may be any byte
             bits = np.unpackbits(np.frombuffer(C.string_at(c.validity, (n + 7) // 8), dtype=np.uint8), bitorder="little")[:n]
