@@ -443,22 +443,11 @@ int Query::launch(hipStream_t stream) {
   return LLKV_OK;
 }
 
-static inline uint64_t host_identity(int op) { return op == 2 ? 0x7FFFFFFFFFFFFFFFull : op == 3 ? 0x8000000000000000ull : 0ull; }
-static inline uint64_t host_combine(int op, uint64_t a, uint64_t b) {
-  switch (op) {
-  case 0: { double x, y; std::memcpy(&x, &a, 8); std::memcpy(&y, &b, 8); double z = x + y; uint64_t r; std::memcpy(&r, &z, 8); return r; }
-  case 1: return a + b;
-  case 2: return (int64_t)b < (int64_t)a ? b : a;
-  case 3: return (int64_t)b > (int64_t)a ? b : a;
-  default: return b > a ? b : a;
-  }
-}
-
 // Fold the 8 octant partials in octant order (same association for every GPU count).
 void fold_exchange_host(const uint64_t *exchange, const uint8_t *lane_ops, uint32_t lanes, uint64_t *state) {
   for (uint32_t l = 0; l < lanes; ++l) {
-    uint64_t v = host_identity(lane_ops[l]);
-    for (int o = 0; o < kOctantsHost; ++o) v = host_combine(lane_ops[l], v, exchange[(size_t)o * lanes + l]);
+    uint64_t v = host_lane_identity(lane_ops[l]);
+    for (int o = 0; o < kOctantsHost; ++o) v = host_lane_combine(lane_ops[l], v, exchange[(size_t)o * lanes + l]);
     state[l] = v;
   }
 }
@@ -933,14 +922,9 @@ int Query::finish_from_exchange(const uint64_t *exchange) {
     for (size_t k = 0; k < p.key_fields.size(); ++k) {
       const uint32_t card = p.key_cards[k], n_codes = p.key_nullable[k] ? card - 1 : card;
       rank[k].assign(card, 0);
-      std::vector<uint32_t> by_value(n_codes);
-      for (uint32_t c = 0; c < n_codes; ++c) by_value[c] = c;
-      if (!p.key_is_int[k] && !utf8_wide(table->cols.at(p.key_fields[k]).info)) { // (a wide key's codes are in byte order already)
-        const auto &dict = table->cols.at(p.key_fields[k]).info.dictionary;
-        auto word = [&](uint32_t c) -> const std::string & { static const std::string none; return c < dict.size() ? dict[c] : none; };
-        std::stable_sort(by_value.begin(), by_value.end(), [&](uint32_t x, uint32_t y) { return word(x) < word(y); });
-      }
-      for (uint32_t r = 0; r < n_codes; ++r) rank[k][by_value[r]] = r + 1; // 0 is the NULL group's
+      // (a code the dictionary does not hold never occurs — the one code of an empty dictionary: it ranks after the strings)
+      const std::vector<uint32_t> by_string = dictionary_ranks(table->cols.at(p.key_fields[k]).info);
+      for (uint32_t c = 0; c < n_codes; ++c) rank[k][c] = (c < by_string.size() ? by_string[c] : c) + 1; // 0 is the NULL group's
     }
   for (uint32_t g = 0; g < p.ng; ++g) {
     const uint64_t *gl = &state[(size_t)g * p.k];

@@ -4,10 +4,13 @@
 #include <hip/hip_runtime.h>
 
 #include "catalog.hpp"
+#include "join.hpp"
 #include "llkv_hip.h"
 #include "plan.hpp"
 #include "scan_params.h"
 
+#include <climits>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <memory>
@@ -87,6 +90,52 @@ struct DeviceColumn {
   DeviceBuffer d_valid; // uint8_t: 1 B/row validity mask (info.nullable), same row layout as d_values
   DeviceBuffer d_hi;    // Decimal128 values beyond 64 bits (info.wide128): d_values holds the low halves, this the high halves
 };
+
+// The key kernels' view of a staged column (join.hip: load_key, key_cell): width and sign by storage dtype — 1-byte codes for a
+// narrow Utf8 column, 4-byte unsigned ones for a wide one.  It refuses nothing: every caller admits the dtypes it takes itself.
+inline JoinKeyColumn key_view(const DeviceColumn &c) {
+  JoinKeyColumn k{};
+  k.values = c.d_values.get();
+  k.valid = c.info.nullable ? c.d_valid.get<uint8_t>() : nullptr;
+  switch (storage_dtype(c.info)) {
+  case LLKV_DT_INT64: k.width = 8; k.is_signed = 1; break;
+  case LLKV_DT_UINT64: k.width = 8; break;
+  case LLKV_DT_INT32: case LLKV_DT_DATE32: k.width = 4; k.is_signed = 1; break;
+  case LLKV_DT_UINT32: k.width = 4; break;
+  default: k.width = 1; break; // dictionary codes
+  }
+  return k;
+}
+
+// The radix sorts' image of a key_view cell is (cell − base) in its low `bits` bits (hj_launch_gather_sort_keys): the type's
+// minimum and width, a wide Utf8 column's largest code.  `by_stats`: a signed column with staging statistics narrows both to
+// its value range.
+struct RadixRange {
+  long long base;
+  uint32_t bits;
+};
+inline RadixRange radix_range(const ColumnInfo &ci, bool by_stats = false) {
+  RadixRange r{0, 64};
+  bool is_signed = true;
+  switch (storage_dtype(ci)) {
+  case LLKV_DT_INT64: r.base = INT64_MIN; break;
+  case LLKV_DT_INT32: case LLKV_DT_DATE32: r = {INT32_MIN, 32}; break;
+  case LLKV_DT_UINT64: is_signed = false; break;
+  case LLKV_DT_UINT32: r.bits = 32; is_signed = false; break;
+  default: r.bits = 8; is_signed = false; break; // dictionary codes
+  }
+  if (utf8_wide(ci)) { // 4-byte codes: the bits of the largest
+    r.bits = 1;
+    while (r.bits < 32 && ((ci.dictionary.size() - 1) >> r.bits)) ++r.bits;
+  }
+  if (by_stats && is_signed && ci.has_stats) { // only the bits the value range needs
+    r.base = ci.min_i;
+    const unsigned __int128 range = (unsigned __int128)((__int128)ci.max_i - (__int128)ci.min_i);
+    r.bits = 1;
+    while (r.bits < 64 && (range >> r.bits) != 0) ++r.bits;
+  }
+  return r;
+}
 
 // Device buffer read by slot `s` of a lowered plan: the field's values, its validity mask, or the high halves of a wide
 // Decimal128 column.
@@ -509,6 +558,17 @@ int run_join_batches(const Table *left, const Table *right, const llkv_join_key 
                      const llkv_join_options *options, const llkv_join_output *output, llkv_on_join_record_batch on_batch, void *user);
 int join_output_names_c(const llkv_join_output *output, int32_t join_type, int32_t key_rules, char **names, uint32_t *n_names);
 
+// The lane ops of the kernels (fused_scan.hip.h: lane_identity, lane_combine) on the host.
+inline uint64_t host_lane_identity(int op) { return op == OP_MIN_I64 ? 0x7FFFFFFFFFFFFFFFull : op == OP_MAX_I64 ? 0x8000000000000000ull : 0ull; }
+inline uint64_t host_lane_combine(int op, uint64_t a, uint64_t b) {
+  switch (op) {
+  case OP_ADD_F64: { double x, y; std::memcpy(&x, &a, 8); std::memcpy(&y, &b, 8); const double z = x + y; uint64_t r; std::memcpy(&r, &z, 8); return r; }
+  case OP_ADD_I64: return a + b;
+  case OP_MIN_I64: return (int64_t)b < (int64_t)a ? b : a;
+  case OP_MAX_I64: return (int64_t)b > (int64_t)a ? b : a;
+  default: return b > a ? b : a;
+  }
+}
 void fold_exchange_host(const uint64_t *exchange, const uint8_t *lane_ops, uint32_t lanes, uint64_t *state);
 int finalize_value(const AggOut &a, const uint64_t *group_lanes, int base, llkv_value *out, std::string *err, bool prefixes_checked);
 

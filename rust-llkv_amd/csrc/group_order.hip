@@ -29,8 +29,6 @@
 
 namespace llkv {
 
-int finalize_value(const AggOut &a, const uint64_t *g, int base, llkv_value *out, std::string *err, bool prefixes_checked);
-
 namespace {
 
 typedef __int128 i128;
@@ -431,13 +429,8 @@ int group_order_device(const GroupOrderSpec &o, const LazyGroups &lz, const uint
       const ColumnInfo *ci = lz.key_cols[k.index];
       t.key = (int32_t)k.index;
       t.kind = ci->dtype == LLKV_DT_UTF8 && !utf8_wide(*ci) ? kTermKeyUtf8 : kTermKeyInt; // (a wide key's code is in byte order: its integer image)
-      if (t.kind == kTermKeyUtf8) {
-        std::vector<uint32_t> idx(ci->dictionary.size());
-        std::iota(idx.begin(), idx.end(), 0u);
-        std::sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return ci->dictionary[x] < ci->dictionary[y]; });
-        for (size_t r = 0; r < idx.size(); ++r) // equal strings share a rank
-          ranks[j * 256 + idx[r]] = r && ci->dictionary[idx[r]] == ci->dictionary[idx[r - 1]] ? ranks[j * 256 + idx[r - 1]] : (uint32_t)r;
-      }
+      const std::vector<uint32_t> by_string = dictionary_ranks(*ci);
+      std::copy(by_string.begin(), by_string.end(), ranks.begin() + j * 256);
       words += 2;
       continue;
     }

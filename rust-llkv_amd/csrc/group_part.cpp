@@ -27,8 +27,6 @@
 
 namespace llkv {
 
-int finalize_value(const AggOut &a, const uint64_t *g, int base, llkv_value *out, std::string *err, bool prefixes_checked);
-
 constexpr uint32_t kPartTileRowsHost = 32768; // fused_scan.hip.h: kPartTileRows
 constexpr uint32_t kMaxPartsHost = 4096;      // fused_scan.hip.h: kMaxParts
 constexpr size_t kPartImageBytes = 128u << 10; // LDS image of one partition, at most
@@ -159,13 +157,9 @@ int part_groupby_prepare(const Table *table, const llkv_filter *filters, uint32_
   HIP_TRY(hipStreamSynchronize(s));
   if (order_by_keys && !g->ids_in_key_order) {
     std::vector<uint32_t> ranks((size_t)n_keys * 256, 0);
-    for (uint32_t j = 0; j < n_keys; ++j) {
-      const ColumnInfo &ci = table->cols.at(key_fields[j]).info;
-      if (ci.dtype != LLKV_DT_UTF8 || utf8_wide(ci)) continue; // (a wide key's code is its rank: no table, kl_keys.code_rank stays NULL)
-      std::vector<uint32_t> idx(std::min<size_t>(ci.dictionary.size(), 256));
-      for (size_t i = 0; i < idx.size(); ++i) idx[i] = (uint32_t)i;
-      std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return ci.dictionary[a] < ci.dictionary[b]; });
-      for (size_t r = 0; r < idx.size(); ++r) ranks[(size_t)j * 256 + idx[r]] = (uint32_t)r;
+    for (uint32_t j = 0; j < n_keys; ++j) { // (a wide key's code is its rank: no table, kl_keys.code_rank stays NULL)
+      const std::vector<uint32_t> r = dictionary_ranks(table->cols.at(key_fields[j]).info);
+      std::copy(r.begin(), r.end(), ranks.begin() + (size_t)j * 256);
     }
     g->d_code_rank = (uint32_t *)scratch_alloc(ranks.size() * 4);
     if (!g->d_code_rank) return set_error(LLKV_INTERNAL, "device allocation failed");

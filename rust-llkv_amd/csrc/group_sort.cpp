@@ -23,8 +23,6 @@
 
 namespace llkv {
 
-int finalize_value(const AggOut &a, const uint64_t *g, int base, llkv_value *out, std::string *err, bool prefixes_checked);
-
 struct SortedGroupBy {
   const Table *table = nullptr;
   LoweredPlan sel_plan, red_plan;
@@ -62,15 +60,6 @@ bool sorted_groupby_partitioned(const SortedGroupBy *s) { return s && s->part; }
 // sums are those of the table — and the groups are put into the order one device would have produced: by key (NULLS
 // first, strings by dictionary order) or by first appearance.
 namespace {
-inline uint64_t combine_lane(int op, uint64_t a, uint64_t b) { // fused_scan.hip.h lane ops
-  switch (op) {
-  case 0: { double x, y; std::memcpy(&x, &a, 8); std::memcpy(&y, &b, 8); const double z = x + y; uint64_t r; std::memcpy(&r, &z, 8); return r; }
-  case 1: return a + b;
-  case 2: return (int64_t)b < (int64_t)a ? b : a;
-  case 3: return (int64_t)b > (int64_t)a ? b : a;
-  default: return b > a ? b : a;
-  }
-}
 struct KeyTupleHost {
   int64_t v[4];
   uint8_t valid[4];
@@ -112,7 +101,7 @@ int sorted_groupby_merge(SortedGroupBy *s, uint32_t world, const uint64_t *rank_
         state.insert(state.end(), src, src + K);
       } else {
         uint64_t *dst = state.data() + (size_t)it->second * K;
-        for (int l = 0; l < K; ++l) dst[l] = combine_lane(ops[(size_t)l], dst[l], src[l]);
+        for (int l = 0; l < K; ++l) dst[l] = host_lane_combine(ops[(size_t)l], dst[l], src[l]);
       }
     }
   }
@@ -121,15 +110,7 @@ int sorted_groupby_merge(SortedGroupBy *s, uint32_t world, const uint64_t *rank_
   std::iota(order.begin(), order.end(), 0ull);
   if (s->order_by_keys) {
     std::vector<std::vector<uint32_t>> rank_of(n_keys); // Utf8: dictionary code → position in string order
-    for (uint32_t k = 0; k < n_keys; ++k) {
-      const ColumnInfo &ci = s->table->cols.at(s->key_fields[k]).info;
-      if (ci.dtype != LLKV_DT_UTF8) continue;
-      std::vector<uint32_t> idx(ci.dictionary.size());
-      std::iota(idx.begin(), idx.end(), 0u);
-      std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return ci.dictionary[a] < ci.dictionary[b]; });
-      rank_of[k].resize(idx.size());
-      for (size_t i = 0; i < idx.size(); ++i) rank_of[k][idx[i]] = (uint32_t)i;
-    }
+    for (uint32_t k = 0; k < n_keys; ++k) rank_of[k] = dictionary_ranks(s->table->cols.at(s->key_fields[k]).info);
     std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
       for (uint32_t k = 0; k < n_keys; ++k) {
         const KeyTupleHost &x = keys[a], &y = keys[b];
@@ -207,36 +188,6 @@ int sorted_groupby_prepare(const Table *table, const llkv_filter *filters, uint3
   *out = s.release();
   return LLKV_OK;
 }
-
-namespace {
-int key_column_of(const Table *t, uint32_t field, JoinKeyColumn *kc, long long *base, uint32_t *bits) {
-  const DeviceColumn &c = t->cols.at(field);
-  std::memset(kc, 0, sizeof *kc);
-  kc->values = c.d_values.get();
-  kc->valid = c.info.nullable ? c.d_valid.get<uint8_t>() : nullptr;
-  *bits = 64;
-  switch (c.info.dtype) {
-  case LLKV_DT_INT64: kc->width = 8; kc->is_signed = 1; *base = INT64_MIN; break;
-  case LLKV_DT_UINT64: kc->width = 8; kc->is_signed = 0; *base = 0; break;
-  case LLKV_DT_INT32: case LLKV_DT_DATE32: kc->width = 4; kc->is_signed = 1; *base = INT32_MIN; *bits = 32; break;
-  case LLKV_DT_UINT32: kc->width = 4; kc->is_signed = 0; *base = 0; *bits = 32; break;
-  default: kc->width = 1; kc->is_signed = 0; *base = 0; *bits = 8; break; // dictionary codes
-  }
-  if (utf8_wide(c.info)) { // 4-byte codes of a wide Utf8 column: the bits of the largest code
-    kc->width = 4;
-    *bits = 1;
-    while (*bits < 32 && ((c.info.dictionary.size() - 1) >> *bits)) ++*bits;
-  }
-  if (c.info.has_stats && kc->is_signed) { // only the bits the value range needs are sorted
-    *base = c.info.min_i;
-    const unsigned __int128 range = (unsigned __int128)((__int128)c.info.max_i - (__int128)c.info.min_i);
-    uint32_t b = 1;
-    while (b < 64 && (range >> b) != 0) ++b;
-    *bits = b;
-  }
-  return LLKV_OK;
-}
-} // namespace
 
 int SortedGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done) {
   if (part) return part_groupby_run(part, out, out_order, done);
@@ -347,23 +298,20 @@ int SortedGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOr
     HIP_TRY(hipStreamSynchronize(s)); // tmp is reallocated by the next pass
   }
   for (int k = (int)n_keys - 1; k >= 0; --k) {
-    long long base;
-    uint32_t bits;
-    if ((rc = key_column_of(table, key_fields[k], &ks.k[k], &base, &bits))) return rc;
+    const DeviceColumn &col = table->cols.at(key_fields[k]);
+    ks.k[k] = key_view(col);
+    const RadixRange range = radix_range(col.info, /*by_stats=*/true);
     const uint8_t *code_rank = nullptr;
-    const ColumnInfo &ci = table->cols.at(key_fields[k]).info;
-    if (order_by_keys && ci.dtype == LLKV_DT_UTF8 && !utf8_wide(ci)) { // ORDER BY the key: codes sort as their strings do (a wide code already does)
-      std::vector<uint32_t> idx(ci.dictionary.size());
-      std::iota(idx.begin(), idx.end(), 0u);
-      std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return ci.dictionary[a] < ci.dictionary[b]; });
+    const std::vector<uint32_t> by_string = order_by_keys ? dictionary_ranks(col.info) : std::vector<uint32_t>();
+    if (!by_string.empty()) { // ORDER BY the key: codes sort as their strings do (a wide code already does)
       uint8_t rank[256] = {0};
-      for (size_t r = 0; r < idx.size(); ++r) rank[idx[r]] = (uint8_t)r;
+      for (size_t c = 0; c < by_string.size(); ++c) rank[c] = (uint8_t)by_string[c];
       if ((rc = rank_d.alloc(256))) return rc;
       HIP_TRY(hipMemcpyAsync(rank_d.p, rank, 256, hipMemcpyHostToDevice, s));
       HIP_TRY(hipStreamSynchronize(s)); // `rank` is a stack array
       code_rank = rank_d.as<uint8_t>();
     }
-    HIP_TRY(hj_launch_gather_sort_keys(ks.k[k], base, code_rank, sel.d_dev, perm, n, keys_a.as<uint64_t>(), s));
+    HIP_TRY(hj_launch_gather_sort_keys(ks.k[k], range.base, code_rank, sel.d_dev, perm, n, keys_a.as<uint64_t>(), s));
     if (n_keys == 1 && !ks.k[k].valid && !has_distinct) {
       // GROUP BY the column the table is clustered by (a primary-key order): the selection already is in key order —
       // no sort, and the reduction then streams the argument columns instead of gathering them
@@ -380,9 +328,9 @@ int SortedGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOr
       }
     }
     size_t tb = 0;
-    HIP_TRY(hj_sort_u64_u32_bits(nullptr, &tb, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), perm, perm_other, n, bits, s));
+    HIP_TRY(hj_sort_u64_u32_bits(nullptr, &tb, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), perm, perm_other, n, range.bits, s));
     if ((rc = tmp.alloc(tb ? tb : 8))) return rc;
-    HIP_TRY(hj_sort_u64_u32_bits(tmp.p, &tb, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), perm, perm_other, n, bits, s));
+    HIP_TRY(hj_sort_u64_u32_bits(tmp.p, &tb, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), perm, perm_other, n, range.bits, s));
     std::swap(perm, perm_other);
     if (ks.k[k].valid) { // NULL cells (key image 0) are told apart — and put first — by one more 1-bit pass
       if (!vkeys_a.p && ((rc = vkeys_a.alloc(n * 4)) || (rc = vkeys_b.alloc(n * 4)))) return rc;

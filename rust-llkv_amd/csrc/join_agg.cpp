@@ -34,11 +34,8 @@ int int_key_column(const Table *t, uint32_t field, JoinKeyColumn *out) {
   auto it = t->cols.find(field);
   if (it == t->cols.end()) return set_error(LLKV_NOT_FOUND, "field " + std::to_string(field) + " not found");
   if (it->second.info.nullable) return set_error(LLKV_UNSUPPORTED, "key column with NULL cells in the join-aggregate pipeline");
-  out->values = it->second.d_values.get();
   switch (it->second.info.dtype) {
-  case LLKV_DT_INT64: case LLKV_DT_UINT64: out->width = 8; out->is_signed = 1; return LLKV_OK;
-  case LLKV_DT_INT32: case LLKV_DT_DATE32: out->width = 4; out->is_signed = 1; return LLKV_OK;
-  case LLKV_DT_UINT32: out->width = 4; out->is_signed = 0; return LLKV_OK;
+  case LLKV_DT_INT64: case LLKV_DT_UINT64: case LLKV_DT_INT32: case LLKV_DT_DATE32: case LLKV_DT_UINT32: *out = key_view(it->second); return LLKV_OK;
   default: return set_error(LLKV_UNSUPPORTED, std::string("integer column expected, got ") + dtype_name(it->second.info.dtype));
   }
 }

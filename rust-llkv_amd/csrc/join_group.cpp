@@ -26,8 +26,6 @@
 
 namespace llkv {
 
-int finalize_value(const AggOut &a, const uint64_t *g, int base, llkv_value *out, std::string *err, bool prefixes_checked);
-
 namespace {
 constexpr uint64_t kMaxSetSpan = 1ull << 32; // 512 MiB of bitmap at most
 
@@ -36,13 +34,8 @@ int key_col_of(const Table *t, uint32_t field, JoinKeyColumn *out, const ColumnI
   if (it == t->cols.end()) return set_error(LLKV_NOT_FOUND, "field " + std::to_string(field) + " not found");
   const ColumnInfo &ci = it->second.info;
   if (ci.nullable && !allow_null) return set_error(LLKV_UNSUPPORTED, "join key column with NULL cells in the join → GROUP BY pipeline");
-  std::memset(out, 0, sizeof *out);
-  out->values = it->second.d_values.get();
-  out->valid = ci.nullable ? it->second.d_valid.get<uint8_t>() : nullptr;
   switch (ci.dtype) {
-  case LLKV_DT_INT64: out->width = 8; out->is_signed = 1; break;
-  case LLKV_DT_INT32: case LLKV_DT_DATE32: out->width = 4; out->is_signed = 1; break;
-  case LLKV_DT_UINT32: out->width = 4; out->is_signed = 0; break;
+  case LLKV_DT_INT64: case LLKV_DT_INT32: case LLKV_DT_DATE32: case LLKV_DT_UINT32: *out = key_view(it->second); break;
   default: return set_error(LLKV_UNSUPPORTED, std::string("integer column expected in the join → GROUP BY pipeline, got ") + dtype_name(ci.dtype));
   }
   if (info) *info = &ci;

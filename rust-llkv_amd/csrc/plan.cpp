@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <numeric>
 
 namespace llkv {
 
@@ -148,6 +149,16 @@ int cast_literal_for_column(const llkv_literal &lit, int32_t dtype, NativeLit *o
   default:
     return set_err(err, LLKV_INTERNAL, std::string("Filtering on type ") + dtype_name(dtype) + " is not supported");
   }
+}
+
+std::vector<uint32_t> dictionary_ranks(const ColumnInfo &ci) {
+  if (ci.dtype != LLKV_DT_UTF8 || utf8_wide(ci)) return {};
+  const std::vector<std::string> &dict = ci.dictionary;
+  std::vector<uint32_t> by_string(dict.size()), rank(dict.size());
+  std::iota(by_string.begin(), by_string.end(), 0u);
+  std::sort(by_string.begin(), by_string.end(), [&](uint32_t a, uint32_t b) { return dict[a] < dict[b]; }); // (no duplicates: table.cpp refuses them)
+  for (size_t r = 0; r < by_string.size(); ++r) rank[by_string[r]] = (uint32_t)r;
+  return rank;
 }
 
 namespace {

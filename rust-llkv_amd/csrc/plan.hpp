@@ -50,6 +50,9 @@ constexpr size_t kNarrowDictMax = 256;
 inline bool utf8_wide(const ColumnInfo &ci) { return ci.dtype == LLKV_DT_UTF8 && ci.dictionary.size() > kNarrowDictMax; }
 // what the device image of a column holds per row, as a dtype (a wide Utf8 column: UInt32 codes)
 inline int32_t storage_dtype(const ColumnInfo &ci) { return utf8_wide(ci) ? LLKV_DT_UINT32 : ci.dtype; }
+// A Utf8 column of 1-byte codes: code → position of its string in byte order (str::cmp), so that codes sort as their strings
+// do; one entry per dictionary string.  Empty for every other column (a wide column's codes are in byte order already).
+std::vector<uint32_t> dictionary_ranks(const ColumnInfo &ci);
 
 using ColumnResolver = std::function<const ColumnInfo *(uint32_t field_id)>;
 

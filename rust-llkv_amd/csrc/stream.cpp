@@ -160,23 +160,14 @@ static int sort_selection(const Table *t, const llkv_scan_options *o, Selection 
   if (n < 2) return LLKV_OK;
   if (n >= (1ull << 32)) return set_error(LLKV_UNSUPPORTED, "more than 2^32 selected rows in an ordered scan");
   hipStream_t s = g_ctx.stream;
-  JoinKeyColumn kc;
-  std::memset(&kc, 0, sizeof kc);
-  kc.values = c.d_values.get();
-  kc.valid = c.info.nullable ? c.d_valid.get<uint8_t>() : nullptr;
-  long long base = 0;
+  const JoinKeyColumn kc = key_view(c);
+  const long long base = radix_range(c.info).base;
   Scratch rank_d;
   const uint8_t *code_rank = nullptr;
-  if (c.info.dtype == LLKV_DT_INT64) { kc.width = 8; kc.is_signed = 1; base = INT64_MIN; }
-  else if (c.info.dtype == LLKV_DT_INT32) { kc.width = 4; kc.is_signed = 1; base = INT32_MIN; }
-  else if (utf8_wide(c.info)) { kc.width = 4; kc.is_signed = 0; } // wide codes are positions in the byte-ordered dictionary: the code is the key
-  else { // dictionary codes sort as their strings do (str::cmp)
-    kc.width = 1;
-    std::vector<uint32_t> idx(c.info.dictionary.size());
-    for (size_t i = 0; i < idx.size(); ++i) idx[i] = (uint32_t)i;
-    std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return c.info.dictionary[a] < c.info.dictionary[b]; });
+  const std::vector<uint32_t> by_string = dictionary_ranks(c.info);
+  if (!by_string.empty()) { // dictionary codes sort as their strings do (str::cmp; a wide code already does)
     uint8_t rank[256] = {0};
-    for (size_t r = 0; r < idx.size(); ++r) rank[idx[r]] = (uint8_t)r;
+    for (size_t code = 0; code < by_string.size(); ++code) rank[code] = (uint8_t)by_string[code];
     int rc = rank_d.alloc(256);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(rank_d.p, rank, 256, hipMemcpyHostToDevice, s));

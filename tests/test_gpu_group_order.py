@@ -76,6 +76,30 @@ def same_rows(got, want, ctx=""):
         assert [bits(v) for v in g.values] == [bits(v) for v in w.values], (ctx, i, g, w)
 
 
+def same_cells(got, want, ctx=""):
+    """Against the oracle: key cells by value (its NULL key cell types differently), aggregate cells bit for bit."""
+    assert len(got) == len(want), (ctx, len(got), len(want))
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert [(k.is_null, k.value) for k in g.keys] == [(k.is_null, k.value) for k in w.keys], (ctx, i, g, w)
+        assert [bits(v) for v in g.values] == [bits(v) for v in w.values], (ctx, i, g, w)
+
+
+WORDS = ["b", "B", "a", "ab", "", "é", "Z", "aa"]  # first appearance is not byte order: upper case first, a multi-byte character last
+
+
+def utf8_key_columns(orc, abi, rng, n, days):
+    """A 1-byte-code Utf8 key (NULL cells), a Date32 key over `days` values and an Int64 argument, and their oracle table."""
+    w = [WORDS[i] for i in rng.integers(0, len(WORDS), size=n)]
+    wvalid = rng.random(n) > 0.05
+    date = (rng.integers(0, days, size=n) + 9000).astype(np.int32)
+    q = rng.integers(-50, 50, size=n).astype(np.int64)
+    first = list(dict.fromkeys(w))
+    assert first != sorted(first, key=str.encode)  # the codes do not sort as the strings do
+    ot = orc.OracleTable(n)
+    ot.add(1, abi.DT_UTF8, [x if ok else None for x, ok in zip(w, wvalid)]).add(2, abi.DT_DATE32, date).add(3, abi.DT_INT64, q)
+    return w, wvalid, date, q, ot
+
+
 def grid_f64(rng, n):
     return rng.integers(-8000, 8000, size=n).astype(np.float64) / 8.0  # dyadic: exact sums
 
@@ -186,6 +210,26 @@ def test_date32_and_utf8_keys(rt, abi, route, monkeypatch):
         for offset, limit in ((0, 10), (7, 25), (0, None)) if oi == 0 or route == "image" else ((0, 10), (7, 25)):
             got, note, _ = ordered_run(rt, t, None, [1, 2], aggs, order, offset, limit)
             same_rows(got, host_order(plain, order, offset, limit), f"{route} {order} {offset}")
+
+
+@pytest.mark.parametrize("route", DEVICE_ROUTES)
+def test_utf8_key_terms_of_the_device_top_k_equal_the_oracle(rt, orc, abi, route, monkeypatch):
+    """A Utf8 key whose dictionary codes do not sort as its strings, as an ORDER BY term of the device top-k: rows and cells
+    equal orc.groupby(...) sorted and sliced the same way."""
+    set_env(monkeypatch, route)
+    w, wvalid, date, q, ot = utf8_key_columns(orc, abi, np.random.default_rng(61), N, 20_000)
+    t = rt.HipTable(1, CHUNKS)
+    t.append_utf8_column(1, w, valid=wvalid)
+    t.append_column(2, abi.DT_DATE32, date)
+    t.append_column(3, abi.DT_INT64, q)
+    A, G = abi.AggregateSpec, abi.GroupOrder
+    aggs = [A.count_star(), A.sum(3)]
+    want = orc.groupby(ot, None, [1, 2], aggs)
+    for order in ([G.key(0), G.key(1)], [G.key(0, True, False), G.agg(1, True)], [G.agg(0, True), G.key(0, False, True)]):
+        got, note, total = ordered_run(rt, t, None, [1, 2], aggs, order, 3, 20)
+        assert note.startswith(ROUTES[route][2]) and note.endswith("; order: device top-k"), note
+        assert total == len(want)
+        same_cells(got, host_order(want, order, 3, 20), f"{route} {order}")
 
 
 @pytest.mark.parametrize("route", ["lds", "partitioned", "sort"])
@@ -368,6 +412,42 @@ def test_sharded_merge_orders_the_merged_groups(rt, abi, order_by_keys, monkeypa
             same_rows(last.rows(), want, f"world {world} {order}")
             for pq in pqs:
                 pq.close()
+
+
+@pytest.mark.parametrize("world", [2, 4])
+def test_sharded_merge_orders_utf8_keys_by_their_strings(rt, orc, abi, world, monkeypatch):
+    """ORDER BY the keys over the merged partial groups of 2 / 4 ranks, the first key a Utf8 column whose table-wide dictionary
+    is in first-appearance order (its codes do not sort as its strings): rows and cells equal the oracle."""
+    monkeypatch.setenv("LLKV_HIP_GROUP_NO_IMAGE", "1")  # (the partial-groups exchange belongs to the sort-based route)
+    chunks = [6000, 9000, 300, 20_000, 4096, 123, 8000]
+    n = sum(chunks)
+    w, wvalid, date, q, ot = utf8_key_columns(orc, abi, np.random.default_rng(67), n, 3000)
+    dictionary = list(dict.fromkeys(w))
+    A = abi.AggregateSpec
+    aggs = [A.count_star(), A.sum(3), A.min(3)]
+
+    def shard(rank):
+        t = rt.HipTable(1, chunks, rank, world)
+        lo = sum(chunks[:t.first_chunk])
+        hi = lo + t.local_rows
+        t.append_utf8_column(1, w[lo:hi], dictionary, valid=wvalid[lo:hi])
+        t.append_column(2, abi.DT_DATE32, date[lo:hi])
+        t.append_column(3, abi.DT_INT64, q[lo:hi])
+        t.set_column_stats(2, 9000, 11_999)
+        t.set_column_stats(3, -50, 49)
+        return t
+
+    pqs = [rt.PreparedQuery(shard(r), None, aggs, [1, 2], True) for r in range(world)]
+    assert pqs[0].route_note.startswith("sort-based"), pqs[0].route_note
+    parts = []
+    for pq in pqs:
+        pq.launch(0)
+        pq.finish_only()
+        parts.append(pq.partial_groups())
+    pqs[-1].merge_groups(parts)
+    same_cells(pqs[-1].rows(), orc.groupby(ot, None, [1, 2], aggs, True), f"world {world}")
+    for pq in pqs:
+        pq.close()
 
 
 def test_prepared_ordered_query_relaunches_and_goes_stale(rt, abi):
