@@ -477,10 +477,9 @@ int finalize_value(const AggOut &a, const uint64_t *g /*group lanes*/, int base,
       const i128 steps = ((i128)(int64_t)l[1] << 32) + (i128)(int64_t)l[0];
       return std::ldexp((double)steps, a.fixed_exp); // (the conversion rounds to nearest even; the scaling is exact)
     }
-    if (a.exact_levels <= 1) return as_f64(l[0]);
-    double v = as_f64(l[a.exact_levels - 1]);
+    double v = as_f64(l[a.exact_levels <= 1 ? 0 : a.exact_levels - 1]);
     for (int j = a.exact_levels - 2; j >= 0; --j) v += as_f64(l[j]);
-    return v;
+    return a.nan_default && std::isnan(v) ? as_f64(0xFFF8000000000000ull) : v; // (AggOut::nan_default: ∞ − ∞ in row order)
   };
   auto exact_sum = [&](int64_t *sum, const char *overflow_msg) -> int {
     const i128 total = ((i128)(int64_t)l[1] << 32) + (i128)(u128)l[0];

@@ -87,6 +87,7 @@ struct DeviceColumn {
   double local_f_absmax = 0.0, local_f_absmin_nz = 0.0;
   bool local_f_all_finite = false; // … and none of this rank's values is NaN / ±∞
   bool local_f_no_neg_zero = false; // … nor −0.0
+  bool local_f_no_nan = false; // … nor NaN
   DeviceBuffer d_valid; // uint8_t: 1 B/row validity mask (info.nullable), same row layout as d_values
   DeviceBuffer d_hi;    // Decimal128 values beyond 64 bits (info.wide128): d_values holds the low halves, this the high halves
 };

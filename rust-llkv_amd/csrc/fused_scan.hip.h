@@ -269,8 +269,10 @@ constexpr uint32_t kErrOverflow = 1u, kErrDivZero = 2u;
 // operand's sign, invalid operations give +NaN), and arrow compares floats by totalOrder — where −NaN is below and
 // +NaN above everything — so the sign of a computed NaN decides `Expr::Compare` and IN-list results.
 // (Only where the bits of a NaN can be observed — template flag EXACT_NAN of Bin / Div, set by the lowering for compare /
-// IN-list sides, projected and emitted values; aggregate arguments skip it: no accumulator looks at a NaN's sign, and
-// the fix-up costs the Q1 kernel 5 %.)
+// IN-list sides, projected and emitted values; aggregate arguments skip it, and the fix-up costs the Q1 kernel 5 %.  No
+// accumulator's state depends on a NaN's sign, but ORDER BY over a finalized f64 SUM / AVG / TOTAL / MIN / MAX does: a NaN
+// computed inside an aggregate argument keeps CDNA's sign there — a known divergence (DESIGN a10).  The accumulators' own
+// ∞ − ∞ is corrected at finalize for a bare Float64 column without NaN cells: AggOut::nan_default.)
 __device__ __forceinline__ double f64_result_as_sse2(double r, double a, double b) {
   if (r == r) return r;
   const long long quiet = 0x0008000000000000ll;

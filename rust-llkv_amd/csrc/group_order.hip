@@ -47,7 +47,7 @@ struct OrderTerm {
   int32_t lane, count_lane; // relative to the group's aggregate lanes (after rows and first row id)
   int32_t word;             // first key word of the term
   int32_t desc, nulls_first;
-  int32_t typed_by_first_value, fast_sum, wide, plain_minmax, null_without_values, fixed_point, fixed_exp, exact_levels, wide_delta;
+  int32_t typed_by_first_value, fast_sum, wide, plain_minmax, null_without_values, fixed_point, fixed_exp, exact_levels, wide_delta, nan_default;
   uint64_t wide_base_hi, wide_base_lo;
   const uint32_t *rank; // Utf8 keys: dictionary code → position in byte order
 };
@@ -134,10 +134,9 @@ __device__ void agg_image(const OrderTerm &t, const uint64_t *g, bool *null, uin
   }
   auto f64_sum = [&]() -> double {
     if (t.fixed_point) return ldexp(i128_to_f64(exact_total(l)), t.fixed_exp);
-    if (t.exact_levels <= 1) return as_f64(l[0]);
-    double v = as_f64(l[t.exact_levels - 1]);
+    double v = as_f64(l[t.exact_levels <= 1 ? 0 : t.exact_levels - 1]);
     for (int j = t.exact_levels - 2; j >= 0; --j) v = host_add(v, as_f64(l[j]));
-    return v;
+    return t.nan_default && __builtin_isnan(v) ? as_f64(0xFFF8000000000000ull) : v; // (AggOut::nan_default)
   };
   auto dec = [&](i128 v) {
     *w0 = (uint64_t)(v >> 64) ^ 0x8000000000000000ull;
@@ -448,6 +447,7 @@ int group_order_device(const GroupOrderSpec &o, const LazyGroups &lz, const uint
     t.fixed_exp = a.fixed_exp;
     t.exact_levels = a.exact_levels;
     t.wide_delta = a.wide_delta;
+    t.nan_default = a.nan_default;
     t.wide_base_hi = a.wide_base_hi;
     t.wide_base_lo = a.wide_base_lo;
     words += is_decimal_fin(a.fin) ? 3 : 2;

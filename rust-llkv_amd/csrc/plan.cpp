@@ -225,7 +225,8 @@ struct Lowering {
   bool grouped;
   // f64 nodes that must return a computed NaN exactly as the reference's host does (sign included): set where the
   // NaN's bits are observable — totalOrder compares, IN lists, projected / emitted values — and left off for aggregate
-  // arguments, where no accumulator looks at them (fused_scan.hip.h: f64_result_as_sse2; it costs Q1 5 %)
+  // arguments, where no accumulator's state depends on them (fused_scan.hip.h: f64_result_as_sse2; it costs Q1 5 %; the
+  // sign of such a NaN in a finalized cell is a known divergence, DESIGN a10)
   bool exact_nan = false;
   int last_fast_32 = 0; // expr_fast: the expression's root type is Int32 (1) / UInt32 (2): the nodes are wrapped in Fit32
   std::string nan_flag(bool is_float) const { return exact_nan && is_float ? ",1" : ""; }
@@ -1645,6 +1646,7 @@ static int lower_aggregates(Lowering &L, const ColumnResolver &resolve, const ll
         p.aggs.push_back(o);
         continue;
       }
+      o.nan_default = dci->dtype == LLKV_DT_FLOAT64 && dci->f_no_nan; // (AggOut::nan_default: the distinct values' ∞ − ∞)
       if (s.kind == LLKV_AGG_TOTAL) { o.fin = AggFinal::TotalF64; o.lane = add_group(f ? "DistinctSumF64" : "DistinctTotalI64", {ADD_F64}); }
       else if (f) { o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumF64 : AggFinal::AvgF64; o.lane = add_group("DistinctSumF64", {ADD_F64}); }
       else { o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumI64Fast : AggFinal::AvgI64Fast; o.lane = add_group("DistinctSumI64", {ADD_I64}); }
@@ -1891,6 +1893,8 @@ static int lower_aggregates(Lowering &L, const ColumnResolver &resolve, const ll
     // statistics say "no NaN / ±∞, no −0.0" has neither case: one order-key lane (a third of the DS instructions)
     const bool plain_f64 = simple && simple_ci->dtype == LLKV_DT_FLOAT64 && simple_ci->has_fstats && simple_ci->f_all_finite && simple_ci->f_no_neg_zero &&
                            !std::getenv("LLKV_HIP_MINMAX_ROW_ORDER");
+    // a NaN sum of a bare Float64 column without NaN cells is the reference's default NaN (AggOut::nan_default)
+    o.nan_default = simple && simple_ci->dtype == LLKV_DT_FLOAT64 && simple_ci->f_no_nan && (s.kind == LLKV_AGG_SUM || s.kind == LLKV_AGG_TOTAL || s.kind == LLKV_AGG_AVG);
     switch (s.kind) {
     case LLKV_AGG_SUM:
       if (is_f64) { o.fin = AggFinal::SumF64; auto g = sum_f64(node); add_agg(g.first, g.second); }
@@ -2150,6 +2154,8 @@ int lower_reduce(const ColumnResolver &resolve, const llkv_aggregate_spec *aggs,
   Lowering L{resolve, p, err, true};
   L.allow_dict_num = false;
   L.allow_sorted_distinct = true;
+  L.strict_exact = plan_exact_f64_sums(); // (the exact-sum option holds on this route too: SumF64Q2 / SumF64X, or UNSUPPORTED)
+  L.exact_f64 = L.strict_exact;
   p.grouped = true;
   p.track_first = true;
   std::vector<std::string> groups;

@@ -32,6 +32,7 @@ struct ColumnInfo {
   bool nullable = false;                // some cell is NULL (row id absent from the column): a 1 B/row validity mask is staged
   bool f_all_finite = false;            // … and no NaN / ±∞ among the values (unsharded tables; agreed by share_metadata)
   bool f_no_neg_zero = false;           // … and no −0.0: with both, MIN / MAX over the bare column need no row-order lanes (one order-key lane)
+  bool f_no_nan = false;                // … and no NaN cell (unsharded tables): a NaN sum of the bare column is the default NaN (AggOut::nan_default)
   bool has_fstats = false;              // Float64 / Float32 columns, over the finite values (staging statistics):
   double f_absmax = 0.0;                //   largest |v|
   double f_absmin_nz = 0.0;             //   smallest non-zero |v| (0: none / unknown)
@@ -93,6 +94,10 @@ struct AggOut {
   int exact_levels = 0; // f64 sum kept as exact grid-level lanes (SumF64X, 2 or 3 of them): value = smallest level first, summed
   bool fixed_point = false; // f64 sum kept as an integer count of grid steps 2^fixed_exp (SumF64Q): lanes = low 32 bits, high part
   int fixed_exp = 0;
+  // f64 SUM / AVG / TOTAL over a bare Float64 column without a NaN cell: a NaN result can only come from +∞ + −∞, which the
+  // reference's row-order sum (x86 SSE2) turns into the default NaN, sign bit set — and a NaN operand keeps its sign after that.
+  // The device lanes give +NaN for it: the finalize returns 0xFFF8000000000000 for any NaN.
+  bool nan_default = false;
 };
 
 struct LoweredPlan {

@@ -215,7 +215,12 @@ static int column_stats_device(Table &t, DeviceColumn &c) {
     if (!std::isfinite(c.local_f_absmin_nz)) c.local_f_absmin_nz = 0.0; // no non-zero value
     c.local_f_all_finite = (bits[2] & 1u) == 0;
     c.local_f_no_neg_zero = (bits[2] & 2u) == 0;
-    if (t.world == 1) { c.info.has_fstats = true; c.info.f_absmax = c.local_f_absmax; c.info.f_absmin_nz = c.local_f_absmin_nz; c.info.f_all_finite = c.local_f_all_finite; c.info.f_no_neg_zero = c.local_f_no_neg_zero; }
+    c.local_f_no_nan = (bits[2] & 4u) == 0;
+    if (t.world == 1) {
+      c.info.has_fstats = true; c.info.f_absmax = c.local_f_absmax; c.info.f_absmin_nz = c.local_f_absmin_nz; c.info.f_all_finite = c.local_f_all_finite;
+      c.info.f_no_neg_zero = c.local_f_no_neg_zero;
+      c.info.f_no_nan = c.info.dtype == LLKV_DT_FLOAT64 && c.local_f_no_nan; // (sharded tables: not shared, stays false)
+    }
     return LLKV_OK;
   }
   if (c.info.dtype != LLKV_DT_INT64 && c.info.dtype != LLKV_DT_INT32 && c.info.dtype != LLKV_DT_DATE32 && c.info.dtype != LLKV_DT_DECIMAL128) return LLKV_OK;
