@@ -158,7 +158,7 @@ int prepare_query(const Table *table, const llkv_filter *filters, uint32_t n_fil
   };
   std::unique_ptr<Query> q(new Query());
   q->table = table;
-  q->table_generation = table->generation;
+  q->epochs.add(table, "");
   q->order_by_keys = order_by_keys;
   q->n_user_aggs = n_aggs;
   q->n_user_keys = grouped ? n_keys : 0;
@@ -343,9 +343,16 @@ int Query::flush_pending() {
   return LLKV_OK;
 }
 
+int TableEpochs::check() const {
+  for (uint32_t i = 0; i < n; ++i)
+    if (e[i].t->generation != e[i].generation)
+      return set_error(LLKV_INVALID_ARGUMENT, std::string("the ") + e[i].role + "table (id " + std::to_string(e[i].t->table_id) +
+                                                  ") was appended to after this handle was prepared (its buffers, statistics and tile lists have changed): prepare it again");
+  return LLKV_OK;
+}
+
 int Query::launch(hipStream_t stream) {
-  if (table && table->generation != table_generation)
-    return set_error(LLKV_INVALID_ARGUMENT, "the table was appended to after this query was prepared (its buffers, statistics and tile lists have changed): prepare it again");
+  if (int stale = epochs.check()) return stale;
   if (sorted) { // the sort-based route runs to completion here; submit / collect only hand the result over
     if (n_launched != n_collected) return set_error(LLKV_INVALID_ARGUMENT, "a sort-based GROUP BY keeps one execution in flight");
     // (a sharded table orders the merged groups: llkv_hip_query_merge_groups / finish_sharded)

@@ -317,9 +317,24 @@ void sorted_groupby_free(SortedGroupBy *s);
 int sorted_groupby_merge(SortedGroupBy *s, uint32_t world, const uint64_t *rank_groups, const int64_t *const *key_values,
                          const uint8_t *const *key_valid, const uint64_t *const *lanes, LazyGroups *out);
 
+// The tables a prepared handle (Query, join → GROUP BY, JoinAgg) was lowered over, each with the generation (Table::generation) it
+// had then.  A handle keeps device pointers, statistics and tile lists of that generation; llkv_hip_table_append_chunks makes a new
+// one and frees what moved: every entry point of a handle that reads a table asks check() first — on the host, before any launch.
+struct TableEpochs {
+  struct Entry {
+    const Table *t;
+    uint64_t generation;
+    const char *role; // "", "fact ", "dimension ", "second dimension ": names the table in the refusal
+  };
+  Entry e[3];
+  uint32_t n = 0;
+  void add(const Table *t, const char *role) { if (t && n < 3) e[n++] = {t, t->generation, role}; }
+  int check() const; // LLKV_OK, or LLKV_INVALID_ARGUMENT "the … table was appended to after this handle was prepared …: prepare it again"
+};
+
 struct Query {
   const Table *table = nullptr;
-  uint64_t table_generation = 0; // the table's generation this query was lowered over (Table::generation)
+  TableEpochs epochs; // the table (join → GROUP BY: fact, dim, dim2) and the generations this query was lowered over
   LazyGroups lazy;
   SortedGroupBy *sorted = nullptr; // set when the dense GROUP BY kernel cannot hold the groups: executions run synchronously in launch()
   struct JoinGroupState *join_state = nullptr; // join → GROUP BY (join_group.cpp): the dimension side's key set and sorted rows

@@ -134,6 +134,7 @@ bool row_before(const llkv_join_group_row &a, const llkv_join_group_row &b, uint
 
 struct JoinAgg {
   const Table *tf = nullptr, *td = nullptr;
+  TableEpochs epochs;                // fact, dim, dim2 as prepare() met them: every later entry point refuses once one of them grew
   uint32_t n_payload = 0;
   CandidateCols cc{};
   Selection seld;                    // qualifying dim rows before the dim2 semi join
@@ -264,6 +265,9 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
   if (td->world != 1 || (t2 && t2->world != 1))
     return set_error(LLKV_INVALID_ARGUMENT, "dimension tables are replicated: stage them whole (world = 1) on every rank; only the fact table is sharded");
   n_payload = n_payload_;
+  epochs.add(tf, "fact ");
+  epochs.add(td, "dimension ");
+  epochs.add(t2, "second dimension ");
   hipStream_t s = g_ctx.stream;
 
   // ---- dim rows: filter [⋉ dim2] ------------------------------------------------------
@@ -515,7 +519,7 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
     cc.rank_chunks = rank_chunks;
     cc.rank_words = dt.n_words;
     cc.rank_kmin = dt.kmin;
-    cc.rank_rows = td->local_rows;
+    cc.rank_rows = td->dev_rows; // the owner row is searched for in the DEVICE image (padding rows behind a ragged chunk repeat its last key: still ascending)
   } else if (direct) { // launches only; the duplicate flag is read with the pair count below
     if ((rc = dt.build(kd_info, kd, d_dim_rows, n_dim, true, s, dt_bits_done && d_dim_rows == seld.d_dev))) return rc;
   } else {
@@ -677,6 +681,7 @@ int JoinAgg::compact_pairs(bool run_sums) {
 int JoinAgg::settle(bool delivered) {
   if (!pending) return LLKV_OK;
   int rc;
+  if ((rc = epochs.check())) return rc;
   if (!delivered && (rc = rb.wait())) return rc;
   pending = false;
   hipStream_t s = g_ctx.stream;
@@ -718,6 +723,7 @@ int JoinAgg::settle(bool delivered) {
 
 // After the all-reduce of gcnts: this rank's raw pairs of the groups that other ranks hold rows of too.
 int JoinAgg::straddlers() {
+  if (int stale = epochs.check()) return stale;
   st_groups.clear();
   st_vals.clear();
   have_straddlers = true;
@@ -751,9 +757,10 @@ int JoinAgg::candidates(const uint32_t *f_groups, const double *f_sums, const ui
                         uint32_t rank, uint32_t limit, llkv_join_group_row *out_rows, uint32_t *out_n, uint64_t *out_groups) {
   *out_n = 0;
   if (out_groups) *out_groups = 0;
+  int rc;
+  if ((rc = epochs.check())) return rc;
   if (n_dim == 0) return LLKV_OK;
   hipStream_t s = g_ctx.stream;
-  int rc;
   // groups this rank reports: the ones it alone holds … (one rank holds every group alone: its counts are the report)
   const bool alone = (tf->world == 1 || range_form) && n_folded == 0;
   const bool by_selection = !std::getenv("LLKV_HIP_TOPK_SORT") && limit <= kTopkSlices;
@@ -900,6 +907,7 @@ int JoinAgg::candidates(const uint32_t *f_groups, const double *f_sums, const ui
 int JoinAgg::boundary() {
   if (!range_form) return set_error(LLKV_INVALID_ARGUMENT, "not a ranged handle: take counts_buffer / straddlers / candidates");
   int rc;
+  if ((rc = epochs.check())) return rc;
   if (pending && (rc = settle())) return rc;
   boundary_block.assign(8 + 2 * kBoundaryCap, 0);
   boundary_block[0] = (multi_run || desc_run) ? 1 : 0;
@@ -917,6 +925,7 @@ int JoinAgg::boundary() {
 int JoinAgg::finish_ranged(const uint64_t *blocks, const uint64_t *offsets, uint32_t world, uint32_t rank, uint32_t limit, llkv_join_group_row *out_rows,
                            uint32_t *out_n, uint64_t *out_groups) {
   if (!range_form) return set_error(LLKV_INVALID_ARGUMENT, "not a ranged handle");
+  if (int stale = epochs.check()) return stale;
   if (boundary_block.empty()) return set_error(LLKV_INVALID_ARGUMENT, "finish_ranged before boundary");
   const uint64_t words = 8 + 2 * kBoundaryCap;
   // every rank sees the same blocks and takes the same decisions
@@ -1034,6 +1043,7 @@ llkv_status llkv_hip_join_agg_counts_buffer(llkv_hip_join_agg *h, void **device_
   auto *j = reinterpret_cast<JoinAgg *>(h);
   if (!j || !device_ptr || !len_i64) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "NULL argument");
   if (j->range_form) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "a ranged handle exchanges boundary runs, not counts: boundary / finish_ranged");
+  if (int stale = j->epochs.check()) return (llkv_status)stale; // (the counts are of the generation the handle was prepared over)
   *device_ptr = j->gcnts.p;
   *len_i64 = j->n_dim;
   return LLKV_OK;
@@ -1111,6 +1121,7 @@ llkv_status llkv_hip_join_agg_finish_sharded(llkv_hip_join_agg *h, uint32_t limi
                                              uint64_t *out_total_groups) {
   auto *j = reinterpret_cast<JoinAgg *>(h);
   if (!j || !out_rows || !out_n) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "NULL argument");
+  if (int stale = j->epochs.check()) return (llkv_status)stale;
   if (!comm_ready()) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "no communicator: call llkv_hip_comm_init first");
   const uint32_t world = comm_world(), rank = comm_rank();
   if (j->tf->world != world || j->tf->rank != rank) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "the fact table's (rank, world) is not the communicator's");

@@ -164,7 +164,9 @@ static int join_groupby_prepare(const llkv_join_side *fact, const llkv_join_side
   if ((rc = key_col_of(tf, fact->key_field, &kf, nullptr, false))) return rc;
   std::unique_ptr<Query> q(new Query());
   q->table = tf;
-  q->table_generation = tf->generation;
+  q->epochs.add(tf, "fact ");
+  q->epochs.add(td, "dimension "); // the key set and the sorted dimension rows are the dimension side's of THIS generation
+  q->epochs.add(t2, "second dimension ");
   q->order_by_keys = true; // ascending keys: the same order on every rank count (the caller's ORDER BY is applied by _rows)
   q->n_user_aggs = n_aggs;
   q->n_user_keys = 1;
@@ -211,6 +213,7 @@ static int join_groupby_rows(Query *q, const uint32_t *payload_fields, uint32_t 
   if (rc) return rc;
   if (!q || !q->join_state || !q->sorted || !out) return set_error(LLKV_INVALID_ARGUMENT, "not a join → GROUP BY query");
   if (!q->lazy.active) return set_error(LLKV_INVALID_ARGUMENT, "the query has not finished an execution yet");
+  if ((rc = q->epochs.check())) return rc; // (the payload gather reads the dimension's columns through the rows kept at prepare)
   if (n_payload > 4) return set_error(LLKV_UNSUPPORTED, "more than 4 payload columns");
   const JoinGroupState &st = *q->join_state;
   const LazyGroups &lz = q->lazy;
