@@ -1,5 +1,6 @@
 // plan.cpp — see plan.hpp.
 #include "plan.hpp"
+#include "scan_params.h" // kMaxCols, kMaxLits, kMaxKeys and the lane algebra (LaneOp) the kernels are built with
 
 #include <algorithm>
 #include <atomic>
@@ -15,10 +16,6 @@ namespace llkv {
 typedef __int128 i128;
 typedef unsigned __int128 u128;
 
-static constexpr int kMaxColsHost = 16;
-static constexpr int kMaxLitsHost = 48; // = kMaxLits (scan_params.h)
-static constexpr int kMaxKeysHost = 4;
-bool plan_exact_f64_sums();
 static constexpr uint32_t kMaxDenseGroups = 64; // bounded further by the LDS image (lanes · 2 KiB ≤ 160 KiB)
 // shared-image route: one image [lane][group] of 8-byte slots per workgroup; 150 KiB of the CU's 160 KiB of LDS
 static constexpr uint32_t kMaxImageGroups = 1u << 16;
@@ -161,9 +158,6 @@ std::vector<uint32_t> dictionary_ranks(const ColumnInfo &ci) {
   return rank;
 }
 
-namespace {
-
-} // namespace
 double parse_numeric_or_zero(const std::string &text) {
   // str::trim(): Unicode White_Space — the ASCII ones and the multi-byte ones a UTF-8 string can start / end with
   auto ws_at = [&](size_t i, bool backwards) -> size_t { // length of the white-space character at i (ending at i), 0 if none
@@ -213,10 +207,60 @@ double parse_numeric_or_zero(const std::string &text) {
   if (k != t.size()) return 0.0;
   return std::strtod(t.c_str(), nullptr); // a decimal literal of that grammar: both sides round it correctly
 }
-static std::string cols_string(const LoweredPlan &p, uint64_t *bytes);
+static std::string cols_string(const LoweredPlan &p, uint64_t *bytes) { // "Cols<…>" of the slots, and the algorithmic bytes per row
+  std::string cols = "Cols<";
+  uint64_t b = 0;
+  for (size_t i = 0; i < p.slot_dtypes.size(); ++i) {
+    cols += (i ? "," : "") + std::string(dtype_tag(p.slot_dtypes[i]));
+    b += dtype_width(p.slot_dtypes[i]);
+  }
+  if (bytes) *bytes = b;
+  return cols + ">";
+}
 namespace {
 
-struct PlanValueInfo { bool is_decimal = false; int scale = 0; i128 lo = 0, hi = 0; bool bounded = false; };
+// [lo, hi] with the arithmetic of bounds: over double for f64 arguments, over i128 for the 64-bit images of integers and decimals
+static double abs_of(double v) { return std::fabs(v); }
+static i128 abs_of(i128 v) { return v < 0 ? -v : v; }
+template <class T> struct Interval {
+  T lo = 0, hi = 0;
+  Interval operator+(const Interval &r) const { return {lo + r.lo, hi + r.hi}; }
+  Interval operator-(const Interval &r) const { return {lo - r.hi, hi - r.lo}; }
+  Interval operator*(const Interval &r) const {
+    const T c[4] = {lo * r.lo, lo * r.hi, hi * r.lo, hi * r.hi};
+    return {std::min(std::min(c[0], c[1]), std::min(c[2], c[3])), std::max(std::max(c[0], c[1]), std::max(c[2], c[3]))};
+  }
+  T mag() const { return std::max(abs_of(lo), abs_of(hi)); } // largest |v|
+};
+static bool fits_i64(i128 v) { return v >= (i128)INT64_MIN && v <= (i128)INT64_MAX; }
+static bool fits_i64(const Interval<i128> &v) { return fits_i64(v.lo) && fits_i64(v.hi); }
+static u128 stats_mag(const ColumnInfo &ci) { return (u128)Interval<i128>{ci.min_i, ci.max_i}.mag(); } // largest |v| the integer statistics allow
+
+struct PlanValueInfo { bool is_decimal = false; int scale = 0; Interval<i128> iv = {}; bool bounded = false; };
+
+// What lowering an expression finds: its node, its class — Float64, or an integer whose ROOT type is Int32 (fit32 = 1) / UInt32 (2),
+// the nodes wrapped in Fit32 (expr_fast) — and, for GROUP BY arguments (expr_planvalue), class, scale and bounds as a PlanValue
+struct Lowered {
+  std::string node;
+  bool is_f64 = false;
+  int fit32 = 0;
+  PlanValueInfo pv = {};
+};
+
+// the conversions of a numeric literal the reference's constant paths apply (literal_to_array: `*v as i64`)
+static int64_t lit_as_i64(const llkv_literal &l) { return (int64_t)lit_i128(l); }
+static double lit_as_f64(const llkv_literal &l) { return l.tag == LLKV_LIT_FLOAT64 ? l.f64 : (double)lit_as_i64(l); }
+static bool numeric_or_null(const llkv_literal &l) { return l.tag == LLKV_LIT_INT128 || l.tag == LLKV_LIT_FLOAT64 || l.tag == LLKV_LIT_NULL; }
+// one numeric or NULL literal: what `simplify` folds literal arithmetic to
+static bool one_literal(const std::vector<llkv_expr_token> &v) { return v.size() == 1 && v[0].kind == LLKV_TOK_LITERAL && numeric_or_null(v[0].literal); }
+
+// ASCII lower case of `v` into `*x` (which may be `v` itself); false when `v` holds a non-ASCII byte: Unicode to_lowercase is not restated
+static bool ascii_lower(const std::string &v, std::string *x) {
+  for (unsigned char ch : v) if (ch >= 0x80) return false;
+  if (x != &v) x->assign(v);
+  for (char &ch : *x) if (ch >= 'A' && ch <= 'Z') ch = (char)(ch + 32);
+  return true;
+}
 
 struct Lowering {
   const ColumnResolver &resolve;
@@ -226,9 +270,9 @@ struct Lowering {
   // f64 nodes that must return a computed NaN exactly as the reference's host does (sign included): set where the
   // NaN's bits are observable — totalOrder compares, IN lists, projected / emitted values — and left off for aggregate
   // arguments, where no accumulator's state depends on them (fused_scan.hip.h: f64_result_as_sse2; it costs Q1 5 %; the
-  // sign of such a NaN in a finalized cell is a known divergence, DESIGN a10)
+  // sign of such a NaN in a finalized cell is a known divergence, DESIGN a10).  Set for a scope, through ExactNan only.
   bool exact_nan = false;
-  int last_fast_32 = 0; // expr_fast: the expression's root type is Int32 (1) / UInt32 (2): the nodes are wrapped in Fit32
+  struct ExactNan { bool &f, was; explicit ExactNan(Lowering &l) : f(l.exact_nan), was(l.exact_nan) { f = true; } ~ExactNan() { f = was; } };
   std::string nan_flag(bool is_float) const { return exact_nan && is_float ? ",1" : ""; }
   // shared-image plans: f64 sums as exact two-level pairs (SumF64X), which need a bound on |argument|
   bool exact_f64 = false;
@@ -238,85 +282,95 @@ struct Lowering {
   bool strict_exact = false;
   bool image_plan = false;
   bool whole_table_image = false; // partitioned route: one LDS image may receive every row of the table
-  uint64_t table_rows = 0; // rows of the table the plan scans (the N of the exact sums)
+  // rows of the table the plan scans (the N of the exact sums): the largest row count among the key columns and the columns of
+  // every expression bounded SO FAR (expr_bounds) — an aggregate's constants depend on what was lowered before it
+  uint64_t table_rows = 0;
   bool allow_dict_num = true; // the kernels of this plan see ScanParams::dict_num (not the sort route's reduce kernel)
   bool allow_code_bits = false; // the launches of this plan bind ScanParams::code_bits (selections and fused / partitioned scans)
   bool allow_sorted_distinct = false; // reduce plans: DISTINCT aggregates over ONE Int64 / Float64 column (it sorts last)
-  // shared-image plans: exchange lane j of a lane group = xf(kernel lane src) (LoweredPlan::image_src / image_xf); empty = as is
-  std::vector<std::vector<std::pair<uint8_t, uint8_t>>> group_expand = {};
-  std::vector<std::pair<uint8_t, uint8_t>> next_expand = {};
-  bool bounds_all_finite = true; // (expr_bounds) no column of the expression holds NaN / ±∞
-  // shared-image plans: the largest |contribution| a row makes to any lane of a lane group (counts: 1; SumI64Fast: max |v| of
-  // its column) when every lane of the group is a plain integer add; −1: the group needs 8-byte cells.  Set before add_group.
-  double next_narrow = -1.0;
-  std::vector<double> group_narrow = {};
 
   // What the column statistics say about an aggregate argument: an interval [lo, hi] (integer min / max, largest
   // finite |v| of float columns) and `nz`, a lower bound on |value| wherever the value is not zero (smallest non-zero
   // finite |v| of float columns, 1 for integers; 0 = unknown).  Literals and + − × only: a division has no useful
   // bound, and a sum of terms of either sign may cancel to anything (nz unknown unless the interval excludes zero).
-  bool expr_bounds(const llkv_expr_token *e, uint32_t n, double *absmax, double *nzmin) {
-    struct I { double lo, hi, nz; };
+  struct Bounds {
+    bool ok = false;         // the statistics bound the argument: |v| ≤ absmax, |v| ≥ nzmin where v ≠ 0
+    double absmax = 0.0, nzmin = 0.0;
+    bool all_finite = true;  // no column of the expression holds NaN / ±∞
+  };
+  Bounds expr_bounds(const llkv_expr_token *e, uint32_t n) {
+    struct I { Interval<double> v; double nz; };
     std::vector<I> st;
-    bounds_all_finite = true;
+    Bounds out;
     for (uint32_t i = 0; i < n; ++i) {
       if (e[i].kind == LLKV_TOK_COLUMN) {
         const ColumnInfo *ci = resolve(e[i].field_id);
-        if (!ci) return false;
+        if (!ci) return out;
         table_rows = std::max(table_rows, ci->rows);
         if ((ci->dtype == LLKV_DT_FLOAT64 || ci->dtype == LLKV_DT_FLOAT32) && ci->has_fstats) {
-          st.push_back({-ci->f_absmax, ci->f_absmax, ci->f_absmin_nz});
-          bounds_all_finite &= ci->f_all_finite;
+          st.push_back({{-ci->f_absmax, ci->f_absmax}, ci->f_absmin_nz});
+          out.all_finite &= ci->f_all_finite;
         }
-        else if (ci->dtype == LLKV_DT_BOOLEAN) st.push_back({0.0, 1.0, 1.0});
+        else if (ci->dtype == LLKV_DT_BOOLEAN) st.push_back({{0.0, 1.0}, 1.0});
         else if (ci->dtype == LLKV_DT_UTF8) { // numeric image of the dictionary
-          I b{0.0, 0.0, 0.0};
+          I b{{0.0, 0.0}, 0.0};
           for (const std::string &w : ci->dictionary) {
             const double v = parse_numeric_or_zero(w);
-            if (!std::isfinite(v)) return false;
-            b.lo = std::min(b.lo, v); b.hi = std::max(b.hi, v);
+            if (!std::isfinite(v)) return out;
+            b.v.lo = std::min(b.v.lo, v); b.v.hi = std::max(b.v.hi, v);
             if (v != 0.0) b.nz = b.nz == 0.0 ? std::fabs(v) : std::min(b.nz, std::fabs(v));
           }
           if (b.nz == 0.0) b.nz = 1.0; // every string counts as 0
           st.push_back(b);
         }
-        else if (is_int_class(ci->dtype) && ci->has_stats) st.push_back({(double)ci->min_i, (double)ci->max_i, 1.0});
-        else return false;
+        else if (is_int_class(ci->dtype) && ci->has_stats) st.push_back({{(double)ci->min_i, (double)ci->max_i}, 1.0});
+        else return out;
       } else if (e[i].kind == LLKV_TOK_LITERAL) {
         const llkv_literal &lit = e[i].literal;
         double v;
         if (lit.tag == LLKV_LIT_FLOAT64) v = lit.f64;
         else if (lit.tag == LLKV_LIT_INT128) v = (double)lit_i128(lit);
-        else return false;
-        if (!std::isfinite(v)) return false;
-        st.push_back({v, v, std::fabs(v)});
+        else return out;
+        if (!std::isfinite(v)) return out;
+        st.push_back({{v, v}, std::fabs(v)});
       } else {
-        if (st.size() < 2) return false;
+        if (st.size() < 2) return out;
         const I r = st.back(); st.pop_back();
         const I l = st.back(); st.pop_back();
         I o;
         switch (e[i].binop) {
-        case LLKV_BIN_ADD: o = {l.lo + r.lo, l.hi + r.hi, 0.0}; break;
-        case LLKV_BIN_SUB: o = {l.lo - r.hi, l.hi - r.lo, 0.0}; break;
-        case LLKV_BIN_MUL: {
-          const double c[4] = {l.lo * r.lo, l.lo * r.hi, l.hi * r.lo, l.hi * r.hi};
-          o = {std::min(std::min(c[0], c[1]), std::min(c[2], c[3])), std::max(std::max(c[0], c[1]), std::max(c[2], c[3])), l.nz * r.nz * 0.999999};
-          break;
+        case LLKV_BIN_ADD: o = {l.v + r.v, 0.0}; break;
+        case LLKV_BIN_SUB: o = {l.v - r.v, 0.0}; break;
+        case LLKV_BIN_MUL: o = {l.v * r.v, l.nz * r.nz * 0.999999}; break;
+        default: return out;
         }
-        default: return false;
-        }
-        if (!std::isfinite(o.lo) || !std::isfinite(o.hi)) return false;
+        if (!std::isfinite(o.v.lo) || !std::isfinite(o.v.hi)) return out;
         if (e[i].binop != LLKV_BIN_MUL) { // the rounded endpoints of a sum: move them outwards a little before trusting their sign
-          const double slack = 1e-12 * std::max(std::fabs(o.lo), std::fabs(o.hi));
-          if (o.lo - slack > 0.0) o.nz = o.lo - slack;
-          else if (o.hi + slack < 0.0) o.nz = -(o.hi + slack);
+          const double slack = 1e-12 * o.v.mag();
+          if (o.v.lo - slack > 0.0) o.nz = o.v.lo - slack;
+          else if (o.v.hi + slack < 0.0) o.nz = -(o.v.hi + slack);
         }
         st.push_back(o);
       }
     }
-    if (st.size() != 1) return false;
-    *absmax = std::max(std::fabs(st[0].lo), std::fabs(st[0].hi));
-    *nzmin = st[0].nz;
+    if (st.size() != 1) return out;
+    out.ok = true;
+    out.absmax = st[0].v.mag();
+    out.nzmin = st[0].nz;
+    return out;
+  }
+
+  // The exponents the three grids below start from: |v| ≤ absmax ≤ 2^b (the bound a little widened: the kernel evaluates the
+  // argument in f64 — every operation rounds, the interval endpoints did too) and nzmin ≥ 2^(nz_ex − 1).  False: no grid.
+  static bool grid_exponents(double absmax, double nzmin, int *b, int *nz_ex) {
+    if (!(absmax >= 0.0) || !std::isfinite(absmax)) return false;
+    if (absmax == 0.0) { absmax = 1.0; nzmin = 1.0; } // the argument is always zero
+    if (!(nzmin > 0.0)) return false;
+    absmax *= 1.0000001;
+    int ex;
+    const double m = std::frexp(absmax, &ex); // absmax = m·2^ex, m in [0.5, 1)
+    *b = m == 0.5 ? ex - 1 : ex;
+    (void)std::frexp(nzmin, nz_ex);
     return true;
   }
 
@@ -326,18 +380,11 @@ struct Lowering {
   // value to 2^-30 of itself: what a row drops is then ≤ 2^-31 of its own magnitude, so a group's sum is within
   // 5e-10 of Σ|v| — inside the contract whatever the group holds.  0 levels: no such choice (the caller's route).
   int exact_sum_constants(double absmax, double nzmin, uint64_t rows, double c[4]) {
-    if (!(absmax >= 0.0) || !std::isfinite(absmax)) return 0;
-    if (absmax == 0.0) { absmax = 1.0; nzmin = 1.0; } // the argument is always zero
-    if (!(nzmin > 0.0)) return 0;
-    absmax *= 1.0000001; // the kernel evaluates the argument in f64: every operation rounds, the interval endpoints did too
-    int ex;
-    const double m = std::frexp(absmax, &ex); // absmax = m·2^ex, m in [0.5, 1)
-    const int b = m == 0.5 ? ex - 1 : ex;
+    int b, nz_ex;
+    if (!grid_exponents(absmax, nzmin, &b, &nz_ex)) return 0;
     int L = 2;
     while (L < 63 && ((uint64_t)1 << L) < rows + 1) ++L;
     if (b < -900 || b + L > 1000 || L > 45) return 0;
-    int nz_ex;
-    (void)std::frexp(nzmin, &nz_ex); // nzmin ≥ 2^(nz_ex − 1)
     const int keep = strict_exact ? 52 : 30; // bits of the smallest non-zero value the last grid resolves (52: all of them)
     for (int levels = 2; levels <= (strict_exact ? 4 : 3); ++levels) {
       const int e_last = b + L - 52 + (levels - 1) * (L - 53); // log2 of the last grid
@@ -355,14 +402,8 @@ struct Lowering {
   // image scan runs at least 256 workgroups over tiles of ≤ 8 192 rows (engine.cpp: pick_image_grid honours
   // LoweredPlan::image_min_grid), so an image sees at most rows / 128 + 16 384 rows of the table.
   bool fixed_point_grid(double absmax, double nzmin, uint64_t rows, int *e_out) {
-    if (!(absmax >= 0.0) || !std::isfinite(absmax)) return false;
-    if (absmax == 0.0) { absmax = 1.0; nzmin = 1.0; }
-    if (!(nzmin > 0.0)) return false;
-    absmax *= 1.0000001;
-    int ex, nz_ex;
-    const double m = std::frexp(absmax, &ex);
-    const int b = m == 0.5 ? ex - 1 : ex;
-    (void)std::frexp(nzmin, &nz_ex);
+    int b, nz_ex;
+    if (!grid_exponents(absmax, nzmin, &b, &nz_ex)) return false;
     const int e = nz_ex - 1 - (strict_exact ? 52 : 30);
     const uint64_t image_rows = whole_table_image ? rows : rows / 128 + 16384; // (a partition's image may see every row)
     int lr = 1;
@@ -375,14 +416,8 @@ struct Lowering {
   // 2^e, e = the ulp of the smallest non-zero |v| — exact, since every value is a multiple of it — split by the kernel
   // into its low 32 bits and the rest: two ADD_I64 lanes that cannot overflow below 2^31 rows.  Needs |v| / 2^e < 2^62.
   bool exact_fixed_point(double absmax, double nzmin, uint64_t rows, int *e_out) {
-    if (!(absmax >= 0.0) || !std::isfinite(absmax) || rows >= (1ull << 31)) return false;
-    if (absmax == 0.0) { absmax = 1.0; nzmin = 1.0; }
-    if (!(nzmin > 0.0)) return false;
-    absmax *= 1.0000001;
-    int ex, nz_ex;
-    const double m = std::frexp(absmax, &ex);
-    const int b = m == 0.5 ? ex - 1 : ex;
-    (void)std::frexp(nzmin, &nz_ex);
+    int b, nz_ex;
+    if (rows >= (1ull << 31) || !grid_exponents(absmax, nzmin, &b, &nz_ex)) return false;
     const int e = nz_ex - 1 - 52;
     if (b - e > 62 || e < -900 || e > 900) return false;
     *e_out = e;
@@ -391,6 +426,19 @@ struct Lowering {
 
   int fail(int code, const std::string &m) { return set_err(err, code, m); }
 
+  // The slot of one buffer of a field — `part` as in LoweredPlan::slot_is_valid: 0 its values, 1 its validity mask, 2 the high
+  // halves of a wide Decimal128 column — taken when a rule first touches it: slot numbers follow the order of the lowering.
+  int take_slot(uint32_t field, uint8_t part, int32_t dtype, int *slot) {
+    static_assert(kMaxCols == 16, "the refusal below names the number");
+    for (size_t i = 0; i < p.slot_fields.size(); ++i)
+      if (p.slot_fields[i] == field && p.slot_is_valid[i] == part) { *slot = (int)i; return LLKV_OK; }
+    if ((int)p.slot_fields.size() >= kMaxCols) return fail(LLKV_UNSUPPORTED, "plan touches more than 16 column buffers");
+    p.slot_fields.push_back(field);
+    p.slot_dtypes.push_back(dtype);
+    p.slot_is_valid.push_back(part);
+    *slot = (int)p.slot_fields.size() - 1;
+    return LLKV_OK;
+  }
   // `wide_codes`: the caller reads a wide Utf8 column's 4-byte codes as such (string predicates, passthrough projections, GROUP BY keys)
   int slot_of(uint32_t field, const ColumnInfo **ci_out, int *slot, bool wide_codes = false) {
     const ColumnInfo *ci = resolve(field);
@@ -401,33 +449,14 @@ struct Lowering {
       return fail(LLKV_UNSUPPORTED, "Decimal128 values beyond 64 bits in field " + std::to_string(field) + ": only SUM / TOTAL / AVG / COUNT over the bare column are on the GPU path");
     // … and the codes of a wide Utf8 column are no 1-byte codes: readers that do not know the form refuse
     if (utf8_wide(*ci) && !wide_codes) return fail(LLKV_UNSUPPORTED, wide_utf8_refusal(*ci, "this operation"));
-    for (size_t i = 0; i < p.slot_fields.size(); ++i)
-      if (p.slot_fields[i] == field && !p.slot_is_valid[i]) { *slot = (int)i; return LLKV_OK; }
-    if ((int)p.slot_fields.size() >= kMaxColsHost) return fail(LLKV_UNSUPPORTED, "plan touches more than 16 column buffers");
-    p.slot_fields.push_back(field);
-    p.slot_dtypes.push_back(storage_dtype(*ci));
-    p.slot_is_valid.push_back(0);
-    *slot = (int)p.slot_fields.size() - 1;
-    return LLKV_OK;
+    return take_slot(field, 0, storage_dtype(*ci), slot);
   }
   // The two buffers of a wide Decimal128 column: low halves (u64), high halves (i64).
   int wide_slots_of(uint32_t field, int *lo, int *hi, bool want_hi = true) {
-    *lo = *hi = -1;
-    for (size_t i = 0; i < p.slot_fields.size(); ++i) {
-      if (p.slot_fields[i] != field) continue;
-      if (p.slot_is_valid[i] == 0) *lo = (int)i;
-      if (p.slot_is_valid[i] == 2) *hi = (int)i;
-    }
-    for (int part = 0; part < (want_hi ? 2 : 1); ++part) {
-      int &slot = part ? *hi : *lo;
-      if (slot >= 0) continue;
-      if ((int)p.slot_fields.size() >= kMaxColsHost) return fail(LLKV_UNSUPPORTED, "plan touches more than 16 column buffers");
-      p.slot_fields.push_back(field);
-      p.slot_dtypes.push_back(part ? LLKV_DT_INT64 : LLKV_DT_UINT64);
-      p.slot_is_valid.push_back(part ? 2 : 0);
-      slot = (int)p.slot_fields.size() - 1;
-    }
-    return LLKV_OK;
+    *hi = -1;
+    int rc = take_slot(field, 0, LLKV_DT_UINT64, lo);
+    if (!rc && want_hi) rc = take_slot(field, 2, LLKV_DT_INT64, hi);
+    return rc;
   }
   // Validity of a field as a predicate node: "" when the column has no NULL cell, else `Valid<slot>` over the
   // field's 1 B/row validity mask (a NULL cell is a row id absent from the column, llkv-table/src/table.rs:1202-1223).
@@ -436,35 +465,29 @@ struct Lowering {
     const ColumnInfo *ci = resolve(field);
     if (!ci) return fail(LLKV_NOT_FOUND, "field " + std::to_string(field) + " not found");
     if (!ci->nullable) return LLKV_OK;
-    int slot = -1;
-    for (size_t i = 0; i < p.slot_fields.size(); ++i)
-      if (p.slot_fields[i] == field && p.slot_is_valid[i] == 1) slot = (int)i;
-    if (slot < 0) {
-      if ((int)p.slot_fields.size() >= kMaxColsHost) return fail(LLKV_UNSUPPORTED, "plan touches more than 16 column buffers");
-      p.slot_fields.push_back(field);
-      p.slot_dtypes.push_back(LLKV_DT_UTF8); // 1-byte cells
-      p.slot_is_valid.push_back(1);
-      slot = (int)p.slot_fields.size() - 1;
-    }
+    int slot;
+    if (int rc = take_slot(field, 1, LLKV_DT_UTF8, &slot)) return rc; // 1-byte cells
     *v = "Valid<" + std::to_string(slot) + ">";
     return LLKV_OK;
   }
   static std::string all_of(const std::vector<std::string> &vs) { // conjunction of validity nodes; "" = always valid
     if (vs.empty()) return "";
     if (vs.size() == 1) return vs[0];
-    std::string s = "And<";
-    for (size_t i = 0; i < vs.size(); ++i) s += (i ? "," : "") + vs[i];
-    return s + ">";
+    return nary("And", vs);
+  }
+  // Adds the validity node of a field to the distinct ones in `vs`; `*some_never_null` is set when the field has no NULL cell.
+  int add_valid_of_field(uint32_t field, std::vector<std::string> *vs, bool *some_never_null = nullptr) {
+    std::string v;
+    if (int rc = valid_of_field(field, &v)) return rc;
+    if (v.empty()) { if (some_never_null) *some_never_null = true; }
+    else if (std::find(vs->begin(), vs->end(), v) == vs->end()) vs->push_back(v);
+    return LLKV_OK;
   }
   // NULL propagates through arithmetic: an expression is valid where all of its columns are.
-  int valid_of_expr(const llkv_expr_token *e, uint32_t n, std::vector<std::string> *vs) {
-    for (uint32_t i = 0; i < n; ++i) {
-      if (e[i].kind != LLKV_TOK_COLUMN) continue;
-      std::string v;
-      int rc = valid_of_field(e[i].field_id, &v);
-      if (rc) return rc;
-      if (!v.empty() && std::find(vs->begin(), vs->end(), v) == vs->end()) vs->push_back(v);
-    }
+  int valid_of_expr(const llkv_expr_token *e, uint32_t n, std::vector<std::string> *vs, bool *some_never_null = nullptr) {
+    for (uint32_t i = 0; i < n; ++i)
+      if (e[i].kind == LLKV_TOK_COLUMN)
+        if (int rc = add_valid_of_field(e[i].field_id, vs, some_never_null)) return rc;
     return LLKV_OK;
   }
   std::string col_node(int slot, int32_t dtype) { return "Col<" + std::to_string(slot) + "," + dtype_tag(dtype) + ">"; }
@@ -479,9 +502,34 @@ struct Lowering {
     else *node = "ColN<" + std::to_string(slot) + "," + dtype_tag((*ci)->dtype) + "," + v.substr(6, v.size() - 7) + ">"; // "Valid<k>" → k
     return LLKV_OK;
   }
+  // The key of a join or key set: an integer column without NULL cells, read as an i64
+  int key_column(uint32_t field, const ColumnInfo **ci, int *slot) {
+    if (int rc = slot_of(field, ci, slot)) return rc;
+    if ((*ci)->nullable) return fail(LLKV_UNSUPPORTED, "NULL join keys in the join-aggregate pipeline");
+    return LLKV_OK;
+  }
+  int key_node(const ColumnInfo &ci, int slot, std::string *key) {
+    if (ci.dtype == LLKV_DT_INT64 || ci.dtype == LLKV_DT_UINT64) *key = col_node(slot, LLKV_DT_INT64);
+    else if (ci.dtype == LLKV_DT_INT32 || ci.dtype == LLKV_DT_DATE32 || ci.dtype == LLKV_DT_UINT32) *key = "ToI64<" + col_node(slot, ci.dtype) + ">";
+    else return fail(LLKV_UNSUPPORTED, std::string("join key of type ") + dtype_name(ci.dtype));
+    return LLKV_OK;
+  }
+  // "the key of this field is in the key set the launch binds" (InKeySet, fused_scan.hip.h)
+  int in_key_set(uint32_t field, std::string *node) {
+    const ColumnInfo *ci;
+    int slot, rc;
+    std::string key;
+    if ((rc = key_column(field, &ci, &slot)) || (rc = key_node(*ci, slot, &key))) return rc;
+    *node = "InKeySet<" + key + ">";
+    return LLKV_OK;
+  }
   // Does the value of an expression depend on more than "all columns present"?  (NULL cells or divisions.)
   static bool has_division(const llkv_expr_token *e, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i) if (e[i].kind == LLKV_TOK_BINARY && (e[i].binop == LLKV_BIN_DIV || e[i].binop == LLKV_BIN_MOD)) return true;
+    return false;
+  }
+  static bool has_column(const llkv_expr_token *e, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) if (e[i].kind == LLKV_TOK_COLUMN) return true;
     return false;
   }
   // Validity of a lowered expression node as a predicate: "" when it can never be NULL.
@@ -503,7 +551,7 @@ struct Lowering {
     size_t at = 0;
     while (at < p.lit_i.size() && p.lit_i[at] != v) ++at;
     if (at == p.lit_i.size()) {
-      if ((int)p.lit_i.size() >= kMaxLitsHost) return fail(LLKV_UNSUPPORTED, "too many integer literals");
+      if ((int)p.lit_i.size() >= kMaxLits) return fail(LLKV_UNSUPPORTED, "too many integer literals");
       p.lit_i.push_back(v);
     }
     *node = std::string(kind) + "<" + std::to_string(at) + ">";
@@ -513,7 +561,7 @@ struct Lowering {
     size_t at = 0;
     while (at < p.lit_f.size() && std::memcmp(&p.lit_f[at], &v, 8) != 0) ++at; // by bit pattern: −0.0 and NaNs keep their own slots
     if (at == p.lit_f.size()) {
-      if ((int)p.lit_f.size() >= kMaxLitsHost) return fail(LLKV_UNSUPPORTED, "too many float literals");
+      if ((int)p.lit_f.size() >= kMaxLits) return fail(LLKV_UNSUPPORTED, "too many float literals");
       p.lit_f.push_back(v);
     }
     *node = "LitF<" + std::to_string(at) + ">";
@@ -553,6 +601,50 @@ struct Lowering {
            " distinct values, 4-byte codes) is not on the GPU path";
   }
 
+  // ---- what the string leaves of both Utf8 forms (1-byte and 4-byte codes) share
+  int lit_string(const llkv_literal &l, std::string *s) {
+    if (l.tag != LLKV_LIT_STRING || !l.str) return fail(LLKV_PREDICATE_BUILD, std::string("literal cast error: expected string, got ") + lit_kind(l));
+    *s = l.str;
+    return LLKV_OK;
+  }
+  // Operator::{StartsWith, EndsWith, Contains} (typed_predicate.rs:186-210): the pattern, lowered when the match is case-insensitive …
+  static bool is_pattern_op(int32_t op) { return op == LLKV_OP_STARTS_WITH || op == LLKV_OP_ENDS_WITH || op == LLKV_OP_CONTAINS; }
+  struct Pattern { int32_t op = 0; bool case_sensitive = true; std::string pat, folded; };
+  int pattern_of(const llkv_filter &f, Pattern *pt) {
+    pt->op = f.op;
+    pt->case_sensitive = f.case_sensitive;
+    if (int rc = lit_string(f.value, &pt->pat)) return rc;
+    if (!f.case_sensitive && !ascii_lower(pt->pat, &pt->pat)) return fail(LLKV_UNSUPPORTED, "case-insensitive pattern with non-ASCII characters (Unicode to_lowercase)");
+    return LLKV_OK;
+  }
+  // … and whether one dictionary string matches it
+  int pattern_matches(Pattern &pt, const std::string &v, bool *ok) {
+    if (!pt.case_sensitive && !ascii_lower(v, &pt.folded)) return fail(LLKV_UNSUPPORTED, "case-insensitive pattern over non-ASCII strings (Unicode to_lowercase)");
+    const std::string &x = pt.case_sensitive ? v : pt.folded, &pat = pt.pat;
+    if (pt.op == LLKV_OP_STARTS_WITH) *ok = x.size() >= pat.size() && x.compare(0, pat.size(), pat) == 0;
+    else if (pt.op == LLKV_OP_ENDS_WITH) *ok = x.size() >= pat.size() && x.compare(x.size() - pat.size(), pat.size(), pat) == 0;
+    else *ok = x.find(pat) != std::string::npos;
+    return LLKV_OK;
+  }
+  // the ordering operators as a pair of string bounds (str::cmp = byte order)
+  struct StringBounds { int lo_kind = LLKV_BOUND_UNBOUNDED, hi_kind = LLKV_BOUND_UNBOUNDED; std::string lo, hi; };
+  int string_bounds(const llkv_filter &f, StringBounds *b) {
+    switch (f.op) {
+    case LLKV_OP_GT: b->lo_kind = LLKV_BOUND_EXCLUDED; return lit_string(f.value, &b->lo);
+    case LLKV_OP_GE: b->lo_kind = LLKV_BOUND_INCLUDED; return lit_string(f.value, &b->lo);
+    case LLKV_OP_LT: b->hi_kind = LLKV_BOUND_EXCLUDED; return lit_string(f.value, &b->hi);
+    case LLKV_OP_LE: b->hi_kind = LLKV_BOUND_INCLUDED; return lit_string(f.value, &b->hi);
+    case LLKV_OP_RANGE: {
+      int rc;
+      b->lo_kind = f.lower_kind; b->hi_kind = f.upper_kind;
+      if (b->lo_kind != LLKV_BOUND_UNBOUNDED && (rc = lit_string(f.lower, &b->lo))) return rc;
+      if (b->hi_kind != LLKV_BOUND_UNBOUNDED && (rc = lit_string(f.upper, &b->hi))) return rc;
+      return LLKV_OK;
+    }
+    default: return fail(LLKV_PREDICATE_BUILD, "unsupported operator for typed predicate: operator lacks string literal support");
+    }
+  }
+
   // A leaf over a wide Utf8 column: its codes are positions in the byte-ordered dictionary, so
   // =, <, <=, >, >=, BETWEEN and case-sensitive StartsWith select one code interval [lo, hi) (CodeRange, found by binary search);
   // IN selects its codes (In up to kWideInCodes of them, else a bitmap); EndsWith, Contains and every case-insensitive pattern are
@@ -561,24 +653,16 @@ struct Lowering {
   int wide_code_leaf(const llkv_filter &f, const ColumnInfo *ci, std::string *out) {
     const std::vector<std::string> &d = ci->dictionary;
     const uint64_t n = d.size();
-    auto lit_str = [&](const llkv_literal &l, std::string *s) -> int {
-      if (l.tag != LLKV_LIT_STRING || !l.str) return fail(LLKV_PREDICATE_BUILD, std::string("literal cast error: expected string, got ") + lit_kind(l));
-      *s = l.str;
-      return LLKV_OK;
-    };
     auto first_ge = [&](const std::string &s) { return (uint64_t)(std::lower_bound(d.begin(), d.end(), s) - d.begin()); };
     auto first_gt = [&](const std::string &s) { return (uint64_t)(std::upper_bound(d.begin(), d.end(), s) - d.begin()); };
-    auto ascii = [](const std::string &x) { for (unsigned char ch : x) if (ch >= 0x80) return false; return true; };
-    auto lower = [](std::string x) { for (char &ch : x) if (ch >= 'A' && ch <= 'Z') ch = (char)(ch + 32); return x; };
     int rc, slot;
     std::vector<uint64_t> bits; // a bitmap leaf: bit c = code c qualifies
     uint64_t lo = 0, hi = n;
-    std::string a, b;
-    const bool pattern_op = f.op == LLKV_OP_STARTS_WITH || f.op == LLKV_OP_ENDS_WITH || f.op == LLKV_OP_CONTAINS;
+    std::string a;
     if (f.op == LLKV_OP_IN) {
       std::vector<uint64_t> codes;
       for (uint32_t i = 0; i < f.in_len; ++i) {
-        if ((rc = lit_str(f.in_list[i], &a))) return rc;
+        if ((rc = lit_string(f.in_list[i], &a))) return rc;
         const uint64_t c = first_ge(a);
         if (c < n && d[c] == a) codes.push_back(c);
       }
@@ -598,46 +682,32 @@ struct Lowering {
       }
       bits.assign((n + 63) / 64, 0);
       for (uint64_t c : codes) bits[c >> 6] |= 1ull << (c & 63);
-    } else if (pattern_op) { // Operator::{StartsWith, EndsWith, Contains} (typed_predicate.rs:186-210)
-      std::string pat;
-      if ((rc = lit_str(f.value, &pat))) return rc;
-      if (!f.case_sensitive) {
-        if (!ascii(pat)) return fail(LLKV_UNSUPPORTED, "case-insensitive pattern with non-ASCII characters (Unicode to_lowercase)");
-        pat = lower(pat);
-      }
+    } else if (is_pattern_op(f.op)) {
+      Pattern pt;
+      if ((rc = pattern_of(f, &pt))) return rc;
       if (f.op == LLKV_OP_STARTS_WITH && f.case_sensitive) { // the strings with this prefix follow each other in byte order
+        const std::string &pat = pt.pat;
         lo = first_ge(pat);
         hi = (uint64_t)(std::partition_point(d.begin() + lo, d.end(), [&](const std::string &v) { return v.compare(0, pat.size(), pat) == 0; }) - d.begin());
       } else {
         bits.assign((n + 63) / 64, 0);
         for (uint64_t c = 0; c < n; ++c) {
-          const std::string &v = d[c];
-          if (!f.case_sensitive && !ascii(v)) return fail(LLKV_UNSUPPORTED, "case-insensitive pattern over non-ASCII strings (Unicode to_lowercase)");
-          const std::string x = f.case_sensitive ? v : lower(v);
           bool ok;
-          if (f.op == LLKV_OP_STARTS_WITH) ok = x.size() >= pat.size() && x.compare(0, pat.size(), pat) == 0;
-          else if (f.op == LLKV_OP_ENDS_WITH) ok = x.size() >= pat.size() && x.compare(x.size() - pat.size(), pat.size(), pat) == 0;
-          else ok = x.find(pat) != std::string::npos;
+          if ((rc = pattern_matches(pt, d[c], &ok))) return rc;
           if (ok) bits[c >> 6] |= 1ull << (c & 63);
         }
       }
+    } else if (f.op == LLKV_OP_EQUALS) {
+      if ((rc = lit_string(f.value, &a))) return rc;
+      lo = first_ge(a);
+      hi = lo < n && d[lo] == a ? lo + 1 : lo;
     } else {
-      switch (f.op) {
-      case LLKV_OP_EQUALS: if ((rc = lit_str(f.value, &a))) return rc; lo = first_ge(a); hi = lo < n && d[lo] == a ? lo + 1 : lo; break;
-      case LLKV_OP_GT: if ((rc = lit_str(f.value, &a))) return rc; lo = first_gt(a); break;
-      case LLKV_OP_GE: if ((rc = lit_str(f.value, &a))) return rc; lo = first_ge(a); break;
-      case LLKV_OP_LT: if ((rc = lit_str(f.value, &a))) return rc; hi = first_ge(a); break;
-      case LLKV_OP_LE: if ((rc = lit_str(f.value, &a))) return rc; hi = first_gt(a); break;
-      case LLKV_OP_RANGE:
-        if (f.lower_kind != LLKV_BOUND_UNBOUNDED && (rc = lit_str(f.lower, &a))) return rc;
-        if (f.upper_kind != LLKV_BOUND_UNBOUNDED && (rc = lit_str(f.upper, &b))) return rc;
-        if (f.lower_kind == LLKV_BOUND_INCLUDED) lo = first_ge(a);
-        if (f.lower_kind == LLKV_BOUND_EXCLUDED) lo = first_gt(a);
-        if (f.upper_kind == LLKV_BOUND_INCLUDED) hi = first_gt(b);
-        if (f.upper_kind == LLKV_BOUND_EXCLUDED) hi = first_ge(b);
-        break;
-      default: return fail(LLKV_PREDICATE_BUILD, "unsupported operator for typed predicate: operator lacks string literal support");
-      }
+      StringBounds b;
+      if ((rc = string_bounds(f, &b))) return rc;
+      if (b.lo_kind == LLKV_BOUND_INCLUDED) lo = first_ge(b.lo);
+      if (b.lo_kind == LLKV_BOUND_EXCLUDED) lo = first_gt(b.lo);
+      if (b.hi_kind == LLKV_BOUND_INCLUDED) hi = first_gt(b.hi);
+      if (b.hi_kind == LLKV_BOUND_EXCLUDED) hi = first_ge(b.hi);
     }
     if (bits.empty()) { // an interval
       if (lo >= hi) { *out = "False"; return LLKV_OK; }
@@ -655,6 +725,65 @@ struct Lowering {
     const size_t at = p.code_bits.size();
     p.code_bits.insert(p.code_bits.end(), bits.begin(), bits.end());
     *out = "CodeBits<" + col_node(slot, storage_dtype(*ci)) + "," + std::to_string(at) + ">";
+    return LLKV_OK;
+  }
+
+  // A leaf over a Utf8 column of 1-byte dictionary codes: = and IN compare codes; the ordering and pattern operators are evaluated
+  // once per dictionary string (str::cmp = byte order) and ship the set of codes as a 256-bit mask
+  int narrow_code_leaf(const llkv_filter &f, const ColumnInfo *ci, std::string *out) {
+    int rc, slot;
+    auto code_of = [&](const llkv_literal &l, int *code) -> int {
+      std::string s;
+      if (int r = lit_string(l, &s)) return r;
+      *code = -1;
+      for (size_t i = 0; i < ci->dictionary.size(); ++i) if (ci->dictionary[i] == s) *code = (int)i;
+      return LLKV_OK;
+    };
+    if (f.op == LLKV_OP_EQUALS) {
+      int code;
+      if ((rc = code_of(f.value, &code))) return rc;
+      if (code < 0) { *out = "False"; return LLKV_OK; }
+      if ((rc = slot_of(f.field_id, &ci, &slot))) return rc;
+      std::string lit;
+      if ((rc = lit_i(code, &lit))) return rc;
+      *out = "Eq<" + col_node(slot, ci->dtype) + "," + lit + ">";
+      return LLKV_OK;
+    }
+    if (f.op == LLKV_OP_IN) {
+      std::string lits;
+      for (uint32_t i = 0; i < f.in_len; ++i) {
+        int code;
+        if ((rc = code_of(f.in_list[i], &code))) return rc;
+        if (code < 0) continue;
+        std::string lit;
+        if ((rc = lit_i(code, &lit))) return rc;
+        lits += "," + lit;
+      }
+      if (lits.empty()) { *out = "False"; return LLKV_OK; }
+      if ((rc = slot_of(f.field_id, &ci, &slot))) return rc;
+      *out = "In<" + col_node(slot, ci->dtype) + lits + ">";
+      return LLKV_OK;
+    }
+    Pattern pt;
+    StringBounds b;
+    if ((rc = is_pattern_op(f.op) ? pattern_of(f, &pt) : string_bounds(f, &b))) return rc;
+    uint64_t mask[4] = {0, 0, 0, 0};
+    bool any = false;
+    for (size_t i = 0; i < ci->dictionary.size() && i < 256; ++i) {
+      const std::string &v = ci->dictionary[i];
+      bool ok = true;
+      if (is_pattern_op(f.op) && (rc = pattern_matches(pt, v, &ok))) return rc;
+      if (b.lo_kind == LLKV_BOUND_INCLUDED) ok = ok && v.compare(b.lo) >= 0;
+      if (b.lo_kind == LLKV_BOUND_EXCLUDED) ok = ok && v.compare(b.lo) > 0;
+      if (b.hi_kind == LLKV_BOUND_INCLUDED) ok = ok && v.compare(b.hi) <= 0;
+      if (b.hi_kind == LLKV_BOUND_EXCLUDED) ok = ok && v.compare(b.hi) < 0;
+      if (ok) { mask[i >> 6] |= 1ull << (i & 63); any = true; }
+    }
+    if (!any) { *out = "False"; return LLKV_OK; }
+    if ((rc = slot_of(f.field_id, &ci, &slot))) return rc;
+    std::string m[4];
+    for (int w = 0; w < 4; ++w) if ((rc = lit_i((int64_t)mask[w], &m[w], "LitU"))) return rc;
+    *out = "InMask<" + col_node(slot, ci->dtype) + "," + m[0] + "," + m[1] + "," + m[2] + "," + m[3] + ">";
     return LLKV_OK;
   }
 
@@ -686,94 +815,7 @@ struct Lowering {
     int slot;
     int rc;
     if (utf8_wide(*ci)) return wide_code_leaf(f, ci, out);
-    if (ci->dtype == LLKV_DT_UTF8) { // dictionary codes: equality only
-      auto code_of = [&](const llkv_literal &l, int *code) -> int {
-        if (l.tag != LLKV_LIT_STRING || !l.str) return fail(LLKV_PREDICATE_BUILD, std::string("literal cast error: expected string, got ") + lit_kind(l));
-        *code = -1;
-        for (size_t i = 0; i < ci->dictionary.size(); ++i) if (ci->dictionary[i] == l.str) *code = (int)i;
-        return LLKV_OK;
-      };
-      if (f.op == LLKV_OP_EQUALS) {
-        int code;
-        if ((rc = code_of(f.value, &code))) return rc;
-        if (code < 0) { *out = "False"; return LLKV_OK; }
-        if ((rc = slot_of(f.field_id, &ci, &slot))) return rc;
-        std::string lit;
-        if ((rc = lit_i(code, &lit))) return rc;
-        *out = "Eq<" + col_node(slot, ci->dtype) + "," + lit + ">";
-        return LLKV_OK;
-      }
-      if (f.op == LLKV_OP_IN) {
-        std::string lits;
-        for (uint32_t i = 0; i < f.in_len; ++i) {
-          int code;
-          if ((rc = code_of(f.in_list[i], &code))) return rc;
-          if (code < 0) continue;
-          std::string lit;
-          if ((rc = lit_i(code, &lit))) return rc;
-          lits += "," + lit;
-        }
-        if (lits.empty()) { *out = "False"; return LLKV_OK; }
-        if ((rc = slot_of(f.field_id, &ci, &slot))) return rc;
-        *out = "In<" + col_node(slot, ci->dtype) + lits + ">";
-        return LLKV_OK;
-      }
-      // ordering predicates: evaluate once per dictionary string (str::cmp = byte order), ship the set of codes
-      auto lit_str = [&](const llkv_literal &l, std::string *out_s) -> int {
-        if (l.tag != LLKV_LIT_STRING || !l.str) return fail(LLKV_PREDICATE_BUILD, std::string("literal cast error: expected string, got ") + lit_kind(l));
-        *out_s = l.str;
-        return LLKV_OK;
-      };
-      std::string lo_s, hi_s, pat;
-      int lo_k = LLKV_BOUND_UNBOUNDED, hi_k = LLKV_BOUND_UNBOUNDED;
-      const bool pattern_op = f.op == LLKV_OP_STARTS_WITH || f.op == LLKV_OP_ENDS_WITH || f.op == LLKV_OP_CONTAINS;
-      auto ascii = [](const std::string &x) { for (unsigned char ch : x) if (ch >= 0x80) return false; return true; };
-      auto lower = [](std::string x) { for (char &ch : x) if (ch >= 'A' && ch <= 'Z') ch = (char)(ch + 32); return x; };
-      if (pattern_op) { // Operator::{StartsWith, EndsWith, Contains} (typed_predicate.rs:186-210)
-        if ((rc = lit_str(f.value, &pat))) return rc;
-        if (!f.case_sensitive) {
-          if (!ascii(pat)) return fail(LLKV_UNSUPPORTED, "case-insensitive pattern with non-ASCII characters (Unicode to_lowercase)");
-          pat = lower(pat);
-        }
-      }
-      switch (pattern_op ? LLKV_OP_RANGE + 1000 : f.op) {
-      case LLKV_OP_RANGE + 1000: break;
-      case LLKV_OP_GT: lo_k = LLKV_BOUND_EXCLUDED; if ((rc = lit_str(f.value, &lo_s))) return rc; break;
-      case LLKV_OP_GE: lo_k = LLKV_BOUND_INCLUDED; if ((rc = lit_str(f.value, &lo_s))) return rc; break;
-      case LLKV_OP_LT: hi_k = LLKV_BOUND_EXCLUDED; if ((rc = lit_str(f.value, &hi_s))) return rc; break;
-      case LLKV_OP_LE: hi_k = LLKV_BOUND_INCLUDED; if ((rc = lit_str(f.value, &hi_s))) return rc; break;
-      case LLKV_OP_RANGE:
-        lo_k = f.lower_kind; hi_k = f.upper_kind;
-        if (lo_k != LLKV_BOUND_UNBOUNDED && (rc = lit_str(f.lower, &lo_s))) return rc;
-        if (hi_k != LLKV_BOUND_UNBOUNDED && (rc = lit_str(f.upper, &hi_s))) return rc;
-        break;
-      default: return fail(LLKV_PREDICATE_BUILD, "unsupported operator for typed predicate: operator lacks string literal support");
-      }
-      uint64_t mask[4] = {0, 0, 0, 0};
-      bool any = false;
-      for (size_t i = 0; i < ci->dictionary.size() && i < 256; ++i) {
-        const std::string &v = ci->dictionary[i];
-        bool ok = true;
-        if (pattern_op) {
-          if (!f.case_sensitive && !ascii(v)) return fail(LLKV_UNSUPPORTED, "case-insensitive pattern over non-ASCII strings (Unicode to_lowercase)");
-          const std::string x = f.case_sensitive ? v : lower(v);
-          if (f.op == LLKV_OP_STARTS_WITH) ok = x.size() >= pat.size() && x.compare(0, pat.size(), pat) == 0;
-          else if (f.op == LLKV_OP_ENDS_WITH) ok = x.size() >= pat.size() && x.compare(x.size() - pat.size(), pat.size(), pat) == 0;
-          else ok = x.find(pat) != std::string::npos;
-        }
-        if (lo_k == LLKV_BOUND_INCLUDED) ok = ok && v.compare(lo_s) >= 0;
-        if (lo_k == LLKV_BOUND_EXCLUDED) ok = ok && v.compare(lo_s) > 0;
-        if (hi_k == LLKV_BOUND_INCLUDED) ok = ok && v.compare(hi_s) <= 0;
-        if (hi_k == LLKV_BOUND_EXCLUDED) ok = ok && v.compare(hi_s) < 0;
-        if (ok) { mask[i >> 6] |= 1ull << (i & 63); any = true; }
-      }
-      if (!any) { *out = "False"; return LLKV_OK; }
-      if ((rc = slot_of(f.field_id, &ci, &slot))) return rc;
-      std::string m[4];
-      for (int w = 0; w < 4; ++w) if ((rc = lit_i((int64_t)mask[w], &m[w], "LitU"))) return rc;
-      *out = "InMask<" + col_node(slot, ci->dtype) + "," + m[0] + "," + m[1] + "," + m[2] + "," + m[3] + ">";
-      return LLKV_OK;
-    }
+    if (ci->dtype == LLKV_DT_UTF8) return narrow_code_leaf(f, ci, out);
     if (ci->dtype == LLKV_DT_DECIMAL128) // llkv-table/src/table.rs:1160-1167
       return fail(LLKV_INTERNAL, "Filtering on type Decimal128(" + std::to_string(ci->precision) + ", " + std::to_string(ci->scale) + ") is not supported");
     if (dtype_width(ci->dtype) == 0 || ci->dtype == LLKV_DT_BOOLEAN)
@@ -889,7 +931,7 @@ struct Lowering {
   // (literal_type, llkv-compute/src/eval.rs:167-185), a computed side has the fast path's result type.
   enum class Side { S32, U32, S64, U64, F };
   int expr_side(const llkv_expr_token *e, uint32_t n, std::string *node, Side *cls) {
-    struct Exact { bool &f, was; explicit Exact(bool &x) : f(x), was(x) { f = true; } ~Exact() { f = was; } } exact(exact_nan); // compared by totalOrder
+    ExactNan exact(*this); // compared by totalOrder
     for (uint32_t i = 0; i < n; ++i)
       if (e[i].kind == LLKV_TOK_LITERAL && e[i].literal.tag == LLKV_LIT_NULL) return fail(LLKV_UNSUPPORTED, "NULL literal in a comparison");
     if (n == 1 && e[0].kind == LLKV_TOK_COLUMN) {
@@ -917,9 +959,10 @@ struct Lowering {
       *cls = Side::S64;
       return lit_i((int64_t)v, node);
     }
-    bool is_f64 = false;
-    const int rc = expr_fast(e, n, node, &is_f64);
-    *cls = is_f64 ? Side::F : last_fast_32 == 1 ? Side::S32 : last_fast_32 == 2 ? Side::U32 : Side::S64;
+    Lowered x;
+    const int rc = expr_fast(e, n, &x);
+    *node = x.node;
+    *cls = x.is_f64 ? Side::F : x.fit32 == 1 ? Side::S32 : x.fit32 == 2 ? Side::U32 : Side::S64;
     return rc;
   }
 
@@ -941,17 +984,16 @@ struct Lowering {
     std::vector<llkv_expr_token> fl;
     int rc = fold_constants(e, n, &fl);
     if (rc) return rc;
-    if (fl.size() != 1 || fl[0].kind != LLKV_TOK_LITERAL || (fl[0].literal.tag != LLKV_LIT_INT128 && fl[0].literal.tag != LLKV_LIT_FLOAT64 && fl[0].literal.tag != LLKV_LIT_NULL))
-      return fail(LLKV_UNSUPPORTED, "constant predicate over a side that does not fold to a numeric literal");
+    if (!one_literal(fl)) return fail(LLKV_UNSUPPORTED, "constant predicate over a side that does not fold to a numeric literal");
     *out = fl[0].literal;
     return LLKV_OK;
   }
   static bool constants_equal(const llkv_literal &a, const llkv_literal &b) { // arrow `eq` in the common type (floats by totalOrder)
     if (a.tag == LLKV_LIT_FLOAT64 || b.tag == LLKV_LIT_FLOAT64) {
-      const double x = a.tag == LLKV_LIT_FLOAT64 ? a.f64 : (double)(int64_t)lit_i128(a), y = b.tag == LLKV_LIT_FLOAT64 ? b.f64 : (double)(int64_t)lit_i128(b);
+      const double x = lit_as_f64(a), y = lit_as_f64(b);
       return std::memcmp(&x, &y, 8) == 0;
     }
-    return (int64_t)lit_i128(a) == (int64_t)lit_i128(b);
+    return lit_as_i64(a) == lit_as_i64(b);
   }
 
   // Expr::InList (evaluate_in_list_over_rows, llkv-scan/src/predicate.rs:443-560): the target is coerced item by
@@ -960,11 +1002,10 @@ struct Lowering {
   int in_list_leaf(const llkv_filter &f, std::string *out, std::string *dom) {
     if (!f.cmp_left || !f.cmp_left_len) return fail(LLKV_INVALID_ARGUMENT, "IN list needs a target expression");
     if (f.list_len && (!f.list_exprs || !f.list_expr_lens)) return fail(LLKV_INVALID_ARGUMENT, "IN list arrays are NULL");
-    bool any_col = false, div = has_division(f.cmp_left, f.cmp_left_len);
-    for (uint32_t i = 0; i < f.cmp_left_len; ++i) any_col |= f.cmp_left[i].kind == LLKV_TOK_COLUMN;
+    bool any_col = has_column(f.cmp_left, f.cmp_left_len), div = has_division(f.cmp_left, f.cmp_left_len);
     for (uint32_t k = 0; k < f.list_len; ++k) {
       div |= has_division(f.list_exprs[k], f.list_expr_lens[k]);
-      for (uint32_t i = 0; i < f.list_expr_lens[k]; ++i) any_col |= f.list_exprs[k][i].kind == LLKV_TOK_COLUMN;
+      any_col |= has_column(f.list_exprs[k], f.list_expr_lens[k]);
     }
     if (!any_col) {
       // evaluate_constant_in_list (:909-963): a NULL target matches and determines nothing; a matching item decides (→ !negated);
@@ -1019,28 +1060,20 @@ struct Lowering {
       return leaf(leaf_f, out, dom);
     }
     std::vector<std::string> vs;
-    bool some_never_null = false, any_col = false;
+    bool some_never_null = false;
     int rc;
-    for (uint32_t i = 0; i < f.cmp_left_len; ++i) {
-      if (f.cmp_left[i].kind != LLKV_TOK_COLUMN) continue;
-      any_col = true;
-      std::string v;
-      if ((rc = valid_of_field(f.cmp_left[i].field_id, &v))) return rc;
-      if (v.empty()) some_never_null = true;
-      else if (std::find(vs.begin(), vs.end(), v) == vs.end()) vs.push_back(v);
-    }
-    if (!any_col) { // (:276-284) the value is NULL or it is not; every row of the table or none, determined everywhere (:746-749)
+    if ((rc = valid_of_expr(f.cmp_left, f.cmp_left_len, &vs, &some_never_null))) return rc;
+    if (!has_column(f.cmp_left, f.cmp_left_len)) { // (:276-284) the value is NULL or it is not; every row of the table or none, determined everywhere (:746-749)
       llkv_literal v;
       if ((rc = constant_side(f.cmp_left, f.cmp_left_len, &v))) return rc;
       *out = ((v.tag == LLKV_LIT_NULL) != (bool)f.negated) ? "True" : "False";
       *dom = "True";
       return LLKV_OK;
     }
-    std::string node;
-    bool is_f64 = false;
-    if ((rc = expr_fast(f.cmp_left, f.cmp_left_len, &node, &is_f64))) return rc;
+    Lowered x;
+    if ((rc = expr_fast(f.cmp_left, f.cmp_left_len, &x))) return rc;
     std::string ve;
-    if ((rc = valid_of_node(f.cmp_left, f.cmp_left_len, node, false, &ve))) return rc;
+    if ((rc = valid_of_node(f.cmp_left, f.cmp_left_len, x.node, false, &ve))) return rc;
     // the scanned rows are those where AT LEAST ONE referenced field is present (:286-291)
     const std::string uni = some_never_null ? "" : (vs.size() == 1 ? vs[0] : nary("Or", vs));
     std::string hit = ve.empty() ? (f.negated ? "True" : "False") : (f.negated ? ve : "Not<" + ve + ">");
@@ -1070,29 +1103,22 @@ struct Lowering {
         return leaf(leaf_f, out, dom);
       }
     }
-    bool any_col = false;
-    for (uint32_t i = 0; i < f.cmp_left_len; ++i) any_col |= l[i].kind == LLKV_TOK_COLUMN;
-    for (uint32_t i = 0; i < f.cmp_right_len; ++i) any_col |= r[i].kind == LLKV_TOK_COLUMN;
     int rc;
-    if (!any_col) {
+    if (!has_column(l, f.cmp_left_len) && !has_column(r, f.cmp_right_len)) {
       // no field at all (predicate.rs:354-360, :791-796): evaluate_constant_compare — both sides are evaluated once, compared in their
       // common type; TRUE selects every row of the table, FALSE none (both are "determined" everywhere), NULL selects and determines
       // nothing.  Restated for sides that fold to one numeric or NULL literal (what `simplify` leaves of literal arithmetic).
       std::vector<llkv_expr_token> fl, fr;
       if ((rc = fold_constants(l, f.cmp_left_len, &fl)) || (rc = fold_constants(r, f.cmp_right_len, &fr))) return rc;
-      auto one_lit = [](const std::vector<llkv_expr_token> &v) {
-        return v.size() == 1 && v[0].kind == LLKV_TOK_LITERAL && (v[0].literal.tag == LLKV_LIT_INT128 || v[0].literal.tag == LLKV_LIT_FLOAT64 || v[0].literal.tag == LLKV_LIT_NULL);
-      };
-      if (!one_lit(fl) || !one_lit(fr)) return fail(LLKV_UNSUPPORTED, "constant comparison over sides that do not fold to a numeric literal");
+      if (!one_literal(fl) || !one_literal(fr)) return fail(LLKV_UNSUPPORTED, "constant comparison over sides that do not fold to a numeric literal");
       const llkv_literal &a = fl[0].literal, &b = fr[0].literal;
       if (a.tag == LLKV_LIT_NULL || b.tag == LLKV_LIT_NULL) { *out = "False"; *dom = "False"; return LLKV_OK; }
       bool m;
       auto rel = [&](auto x, auto y) { return f.cmp_op == LLKV_CMP_EQ ? x == y : f.cmp_op == LLKV_CMP_NOT_EQ ? x != y : f.cmp_op == LLKV_CMP_LT ? x < y : f.cmp_op == LLKV_CMP_LT_EQ ? x <= y : f.cmp_op == LLKV_CMP_GT ? x > y : x >= y; };
       if (a.tag == LLKV_LIT_FLOAT64 || b.tag == LLKV_LIT_FLOAT64) { // Float64 by totalOrder
         auto key = [](double v) { int64_t k; std::memcpy(&k, &v, 8); return k ^ (int64_t)((uint64_t)(k >> 63) >> 1); };
-        const double x = a.tag == LLKV_LIT_FLOAT64 ? a.f64 : (double)(int64_t)lit_i128(a), y = b.tag == LLKV_LIT_FLOAT64 ? b.f64 : (double)(int64_t)lit_i128(b);
-        m = rel(key(x), key(y));
-      } else m = rel((int64_t)lit_i128(a), (int64_t)lit_i128(b)); // (literal_to_array: `*v as i64`)
+        m = rel(key(lit_as_f64(a)), key(lit_as_f64(b)));
+      } else m = rel(lit_as_i64(a), lit_as_i64(b));
       *out = m ? "True" : "False";
       *dom = "True";
       return LLKV_OK;
@@ -1121,16 +1147,10 @@ struct Lowering {
     std::string ln, rn;
     Side lc, rc_;
     if ((rc = expr_side(l, f.cmp_left_len, &ln, &lc)) || (rc = expr_side(r, f.cmp_right_len, &rn, &rc_))) return rc;
-    // get_common_type (llkv-compute/src/kernels.rs:179-242) of the two sides
-    const auto is_unsigned = [](Side s) { return s == Side::U32 || s == Side::U64; };
-    const auto is_64 = [](Side s) { return s == Side::S64 || s == Side::U64; };
-    bool as_float = lc == Side::F || rc_ == Side::F;
-    if (!as_float && is_unsigned(lc) != is_unsigned(rc_) && (is_64(lc) || is_64(rc_))) as_float = true; // signed ⋈ unsigned, 64 bits wide → Float64
-    if (as_float) {
-      if (lc != Side::F) ln = "ToF64<" + ln + ">";
-      if (rc_ != Side::F) rn = "ToF64<" + rn + ">";
-    }
-    // otherwise both signed (Int32/Int64 → i64 compare), both unsigned (→ u64 compare; a widened UInt32
+    const Side common = common_side(lc, rc_);
+    ln = cast_side(ln, lc, common);
+    rn = cast_side(rn, rc_, common);
+    // short of Float64: both signed (Int32/Int64 → i64 compare), both unsigned (→ u64 compare; a widened UInt32
     // is a non-negative i64, which C++ converts to u64 unchanged) or 32-bit mixed (→ Int64)
     // rows where every referenced field is present = where both sides are determined (predicate.rs:366-388,635-638)
     std::vector<std::string> vs;
@@ -1156,9 +1176,7 @@ struct Lowering {
   // errors (integer overflow, x % 0) leaves the node as it was: such a plan is handed back.
   int fold_constants(const llkv_expr_token *e, uint32_t n, std::vector<llkv_expr_token> *out) {
     out->clear();
-    auto is_num = [](const llkv_expr_token &t) {
-      return t.kind == LLKV_TOK_LITERAL && (t.literal.tag == LLKV_LIT_INT128 || t.literal.tag == LLKV_LIT_FLOAT64 || t.literal.tag == LLKV_LIT_NULL);
-    };
+    auto is_num = [](const llkv_expr_token &t) { return t.kind == LLKV_TOK_LITERAL && numeric_or_null(t.literal); };
     for (uint32_t i = 0; i < n; ++i) {
       const size_t m = out->size();
       if (!(e[i].kind == LLKV_TOK_BINARY && m >= 2 && is_num((*out)[m - 1]) && is_num((*out)[m - 2]))) { out->push_back(e[i]); continue; }
@@ -1169,7 +1187,7 @@ struct Lowering {
       if (op < LLKV_BIN_ADD || op > LLKV_BIN_MOD) return fail(LLKV_UNSUPPORTED, "constant sub-expression under this operator");
       if (a.tag == LLKV_LIT_NULL || b.tag == LLKV_LIT_NULL) r.literal.tag = LLKV_LIT_NULL;
       else if (a.tag == LLKV_LIT_FLOAT64 || b.tag == LLKV_LIT_FLOAT64) {
-        const double x = a.tag == LLKV_LIT_FLOAT64 ? a.f64 : (double)(int64_t)lit_i128(a), y = b.tag == LLKV_LIT_FLOAT64 ? b.f64 : (double)(int64_t)lit_i128(b);
+        const double x = lit_as_f64(a), y = lit_as_f64(b);
         r.literal.tag = LLKV_LIT_FLOAT64;
         uint64_t ybits;
         memcpy(&ybits, &y, 8);
@@ -1181,7 +1199,7 @@ struct Lowering {
         default: r.literal.f64 = std::fmod(x, y); break;
         }
       } else {
-        const int64_t x = (int64_t)lit_i128(a), y = (int64_t)lit_i128(b);
+        const int64_t x = lit_as_i64(a), y = lit_as_i64(b);
         int64_t z = 0;
         bool bad = false, null = false;
         switch (op) {
@@ -1201,8 +1219,8 @@ struct Lowering {
     return LLKV_OK;
   }
 
-  int expr_fast(const llkv_expr_token *e_in, uint32_t n_in, std::string *node, bool *is_f64) {
-    last_fast_32 = 0;
+  int expr_fast(const llkv_expr_token *e_in, uint32_t n_in, Lowered *out) {
+    *out = Lowered{};
     std::vector<llkv_expr_token> folded;
     int frc = fold_constants(e_in, n_in, &folded);
     if (frc) return frc;
@@ -1222,7 +1240,7 @@ struct Lowering {
         if (e[i].literal.tag == LLKV_LIT_FLOAT64) any_float = true;
         else if (e[i].literal.tag != LLKV_LIT_INT128) return fail(LLKV_UNSUPPORTED, "non-numeric literal in computed projection");
       } else if (e[i].kind == LLKV_TOK_BINARY) {
-        if (e[i].binop == LLKV_BIN_DIV) return expr_generic(e, n, node, is_f64); // Divide leaves the fast path (fast_numeric.rs:273-275)
+        if (e[i].binop == LLKV_BIN_DIV) return expr_generic(e, n, out); // Divide leaves the fast path (fast_numeric.rs:273-275)
       }
     }
     // Int32 ⊕ Int32 (UInt32 ⊕ UInt32) stays 32 bits wide in the reference (checked i32 arithmetic, Int32 result): what decides is the
@@ -1236,7 +1254,7 @@ struct Lowering {
       }
       if (all_i32 || all_u32) fit32 = all_i32 ? 1 : 2; // every node's result must fit 32 bits (Fit32, fused_scan.hip.h)
     }
-    last_fast_32 = fit32;
+    out->fit32 = fit32;
     for (uint32_t i = 2; i < n; ++i) // (only non-numeric literal pairs are left unfolded)
       if (e[i].kind == LLKV_TOK_BINARY && e[i - 1].kind == LLKV_TOK_LITERAL && e[i - 2].kind == LLKV_TOK_LITERAL) return fail(LLKV_UNSUPPORTED, "constant sub-expression");
     // get_common_type (llkv-compute/src/kernels.rs:179-242): a 64-bit unsigned side with a signed side → Float64
@@ -1272,8 +1290,8 @@ struct Lowering {
       }
     }
     if (st.size() != 1) return fail(LLKV_INTERNAL, "fast path evaluation missing result");
-    *node = st[0];
-    *is_f64 = any_float;
+    out->node = st[0];
+    out->is_f64 = any_float;
     return LLKV_OK;
   }
 
@@ -1281,7 +1299,7 @@ struct Lowering {
   // compute_binary kernels.rs:99-177): every Binary node coerces its own two operands to their common type
   // (not the whole expression to one final type), integers stay checked, zeros of a divisor become NULLs.
   // Restated for Int64 / Float64 operands; narrower or unsigned ones keep the query on the caller's route.
-  int expr_generic(const llkv_expr_token *e, uint32_t n, std::string *node, bool *is_f64) {
+  int expr_generic(const llkv_expr_token *e, uint32_t n, Lowered *out) {
     struct V { std::string s; bool f; };
     std::vector<V> st;
     int rc;
@@ -1313,32 +1331,30 @@ struct Lowering {
       }
     }
     if (st.size() != 1) return fail(LLKV_INTERNAL, "expression evaluation missing result");
-    *node = st[0].s;
-    *is_f64 = st[0].f;
+    out->node = st[0].s;
+    out->is_f64 = st[0].f;
     return LLKV_OK;
   }
 
   // What a GROUP BY aggregate argument evaluates to (PlanValue::{Integer, Float, Decimal}); for the integer and decimal
-  // classes the interval [lo, hi] the column statistics and literals leave its 64-bit image in.
+  // classes the interval the column statistics and literals leave its 64-bit image in.
   struct PV {
     std::string s;
     bool f = false;     // Float
     bool dec = false;   // Decimal(scale): the value is raw / 10^scale
     int scale = 0;
     bool bounded = false;
-    i128 lo = 0, hi = 0;
+    Interval<i128> iv = {};
     bool lit = false;   // an integer / decimal literal (lo == hi)
   };
-  PlanValueInfo last_planvalue = {}; // (expr_planvalue) class, scale and bounds of the expression just lowered
 
-  static bool fits_i64(i128 v) { return v >= (i128)INT64_MIN && v <= (i128)INT64_MAX; }
   static i128 pow10_i128(int k) { i128 v = 1; for (int i = 0; i < k; ++i) v *= 10; return v; }
 
   // GROUP BY aggregate argument, PlanValue semantics (llkv-executor/src/lib.rs:7193-7389).
-  int expr_planvalue(const llkv_expr_token *e, uint32_t n, std::string *node, bool *is_f64) {
+  int expr_planvalue(const llkv_expr_token *e, uint32_t n, Lowered *out) {
     std::vector<PV> st;
     int rc;
-    last_planvalue = PlanValueInfo{};
+    *out = Lowered{};
     for (uint32_t i = 0; i < n; ++i) {
       if (e[i].kind == LLKV_TOK_COLUMN) {
         const ColumnInfo *ci;
@@ -1358,10 +1374,10 @@ struct Lowering {
         else return fail(LLKV_UNSUPPORTED, std::string("aggregate expression over ") + dtype_name(ci->dtype));
         if (!v.f) {
           v.bounded = true;
-          if (ci->has_stats) { v.lo = ci->min_i; v.hi = ci->max_i; }
-          else if (ci->dtype == LLKV_DT_INT32 || ci->dtype == LLKV_DT_DATE32) { v.lo = INT32_MIN; v.hi = INT32_MAX; }
-          else if (ci->dtype == LLKV_DT_UINT32) { v.lo = 0; v.hi = UINT32_MAX; }
-          else { v.lo = INT64_MIN; v.hi = INT64_MAX; }
+          if (ci->has_stats) v.iv = {ci->min_i, ci->max_i};
+          else if (ci->dtype == LLKV_DT_INT32 || ci->dtype == LLKV_DT_DATE32) v.iv = {INT32_MIN, INT32_MAX};
+          else if (ci->dtype == LLKV_DT_UINT32) v.iv = {0, UINT32_MAX};
+          else v.iv = {INT64_MIN, INT64_MAX};
         }
         st.push_back(v);
       } else if (e[i].kind == LLKV_TOK_LITERAL) {
@@ -1370,15 +1386,15 @@ struct Lowering {
         PV v;
         if (lit.tag == LLKV_LIT_FLOAT64) { if ((rc = lit_f(lit.f64, &l))) return rc; v.f = true; }
         else if (lit.tag == LLKV_LIT_INT128) { // `*v as i64` (:7019)
-          const int64_t x = (int64_t)lit_i128(lit);
+          const int64_t x = lit_as_i64(lit);
           if ((rc = lit_i(x, &l))) return rc;
-          v.bounded = true; v.lo = v.hi = x; v.lit = true;
+          v.bounded = true; v.iv = {x, x}; v.lit = true;
         }
         else if (lit.tag == LLKV_LIT_DECIMAL128) { // Literal::Decimal128(DecimalValue) (:7021)
           const i128 raw = lit_i128(lit);
           if (!fits_i64(raw) || lit.scale < -38 || lit.scale > 38) return fail(LLKV_UNSUPPORTED, "decimal literal beyond 64 bits in an aggregate expression");
           if ((rc = lit_i((int64_t)raw, &l))) return rc;
-          v.dec = true; v.scale = lit.scale; v.bounded = true; v.lo = v.hi = raw; v.lit = true;
+          v.dec = true; v.scale = lit.scale; v.bounded = true; v.iv = {raw, raw}; v.lit = true;
         }
         else return fail(LLKV_UNSUPPORTED, "literal kind in aggregate expression");
         v.s = l;
@@ -1396,20 +1412,20 @@ struct Lowering {
           o.dec = true;
           o.bounded = true;
           // rescale: value · 10^diff (decimal.rs:29-49), admitted when the statistics keep the product inside 64 bits
-          auto rescaled = [&](const PV &x, int target, PV *out) -> int {
-            *out = x;
-            out->scale = target;
+          auto rescaled = [&](const PV &x, int target, PV *res) -> int {
+            *res = x;
+            res->scale = target;
             const int diff = target - x.scale;
             if (diff == 0) return LLKV_OK;
             if (diff > 18) return fail(LLKV_UNSUPPORTED, "decimal rescale beyond 64 bits in an aggregate expression");
             const i128 f = pow10_i128(diff);
-            out->lo = x.lo * f; out->hi = x.hi * f;
-            if (!fits_i64(out->lo) || !fits_i64(out->hi)) return fail(LLKV_UNSUPPORTED, "decimal intermediate beyond 64 bits in an aggregate expression");
-            if (x.lit) return lit_i((int64_t)out->lo, &out->s); // a literal is rescaled here
+            res->iv = {x.iv.lo * f, x.iv.hi * f};
+            if (!fits_i64(res->iv)) return fail(LLKV_UNSUPPORTED, "decimal intermediate beyond 64 bits in an aggregate expression");
+            if (x.lit) return lit_i((int64_t)res->iv.lo, &res->s); // a literal is rescaled here
             std::string k;
             int rc2 = lit_i((int64_t)f, &k);
             if (rc2) return rc2;
-            out->s = "DecBin<3," + x.s + "," + k + ">";
+            res->s = "DecBin<3," + x.s + "," + k + ">";
             return LLKV_OK;
           };
           if (e[i].binop == LLKV_BIN_ADD || e[i].binop == LLKV_BIN_SUB) {
@@ -1417,29 +1433,26 @@ struct Lowering {
             PV a, b;
             if ((rc = rescaled(l, target, &a)) || (rc = rescaled(r, target, &b))) return rc;
             o.scale = target;
-            if (e[i].binop == LLKV_BIN_ADD) { o.lo = a.lo + b.lo; o.hi = a.hi + b.hi; }
-            else { o.lo = a.lo - b.hi; o.hi = a.hi - b.lo; }
+            o.iv = e[i].binop == LLKV_BIN_ADD ? a.iv + b.iv : a.iv - b.iv;
             o.s = std::string("DecBin<") + (e[i].binop == LLKV_BIN_ADD ? "1," : "2,") + a.s + "," + b.s + ">";
           } else if (e[i].binop == LLKV_BIN_MUL) {
             o.scale = l.scale + r.scale;
             if (o.scale < -38 || o.scale > 38) return fail(LLKV_UNSUPPORTED, "decimal product scale outside ±38 (an error in the reference)");
-            const i128 c4[4] = {l.lo * r.lo, l.lo * r.hi, l.hi * r.lo, l.hi * r.hi};
-            o.lo = std::min(std::min(c4[0], c4[1]), std::min(c4[2], c4[3]));
-            o.hi = std::max(std::max(c4[0], c4[1]), std::max(c4[2], c4[3]));
+            o.iv = l.iv * r.iv;
             o.s = "DecBin<3," + l.s + "," + r.s + ">";
           } else { // Divide: to the left operand's scale; numerator · 10^(divisor's scale)
             o.scale = l.scale;
             if (r.scale < 0 || r.scale > 18) return fail(LLKV_UNSUPPORTED, "decimal division by an operand of this scale is not on the GPU path");
             const i128 f = pow10_i128(r.scale);
-            const i128 nlo = l.lo * f, nhi = l.hi * f;
-            if (!fits_i64(nlo) || !fits_i64(nhi)) return fail(LLKV_UNSUPPORTED, "decimal intermediate beyond 64 bits in an aggregate expression");
-            const i128 m = std::max(nlo < 0 ? -nlo : nlo, nhi < 0 ? -nhi : nhi) + 1; // |quotient| ≤ |numerator|, + 1 for the rounding
-            o.lo = -m; o.hi = m;
+            const Interval<i128> num = {l.iv.lo * f, l.iv.hi * f};
+            if (!fits_i64(num)) return fail(LLKV_UNSUPPORTED, "decimal intermediate beyond 64 bits in an aggregate expression");
+            const i128 m = num.mag() + 1; // |quotient| ≤ |numerator|, + 1 for the rounding
+            o.iv = {-m, m};
             std::string k;
             if ((rc = lit_i((int64_t)f, &k))) return rc;
             o.s = "DecDiv<" + l.s + "," + r.s + "," + k + ">";
           }
-          if (!fits_i64(o.lo) || !fits_i64(o.hi)) return fail(LLKV_UNSUPPORTED, "decimal intermediate beyond 64 bits in an aggregate expression");
+          if (!fits_i64(o.iv)) return fail(LLKV_UNSUPPORTED, "decimal intermediate beyond 64 bits in an aggregate expression");
           st.push_back(o);
           continue;
         }
@@ -1447,16 +1460,16 @@ struct Lowering {
           // Int / Int truncates but turns Float for i64::MIN / -1 (:7213-7227): the type of the group's temp column
           // would depend on the data — unless the statistics (or a literal divisor) exclude that pair
           if (!l.f && !r.f) {
-            const bool never_min = l.bounded && l.lo > (i128)INT64_MIN, never_minus_one = r.bounded && (r.lo > -1 || r.hi < -1);
+            const bool never_min = l.bounded && l.iv.lo > (i128)INT64_MIN, never_minus_one = r.bounded && (r.iv.lo > -1 || r.iv.hi < -1);
             if (!never_min && !never_minus_one)
               return fail(LLKV_UNSUPPORTED, "integer division in GROUP BY aggregate arguments whose operands may be i64::MIN / −1 (it turns Float in the reference: the temp column's type would depend on the data)");
             PV o;
             o.s = "DivIntPV<" + l.s + "," + r.s + ">";
             o.bounded = true;
-            const i128 m = std::max(l.lo < 0 ? -l.lo : l.lo, l.hi < 0 ? -l.hi : l.hi);
-            o.lo = -m; o.hi = m;
-            if (!fits_i64(o.lo)) o.lo = INT64_MIN;
-            if (!fits_i64(o.hi)) o.hi = INT64_MAX;
+            const i128 m = l.iv.mag();
+            o.iv = {-m, m};
+            if (!fits_i64(o.iv.lo)) o.iv.lo = INT64_MIN;
+            if (!fits_i64(o.iv.hi)) o.iv.hi = INT64_MAX;
             st.push_back(o);
             continue;
           }
@@ -1472,24 +1485,17 @@ struct Lowering {
           o.s = "BinViaF64<" + std::to_string(op) + "," + l.s + "," + r.s + ">";
           // (computed in f64 and cast back: exact only below 2^53 — beyond that the interval is everything an i64 holds)
           o.bounded = true;
-          o.lo = INT64_MIN; o.hi = INT64_MAX;
+          o.iv = {INT64_MIN, INT64_MAX};
           const i128 lim = (i128)1 << 53;
+          const auto exact = [&](const Interval<i128> &v) { return v.lo > -lim && v.hi < lim; };
           if (op != 4 && l.bounded && r.bounded) {
-            i128 a, b;
-            if (op == 1) { a = l.lo + r.lo; b = l.hi + r.hi; }
-            else if (op == 2) { a = l.lo - r.hi; b = l.hi - r.lo; }
-            else {
-              const i128 c4[4] = {l.lo * r.lo, l.lo * r.hi, l.hi * r.lo, l.hi * r.hi};
-              a = std::min(std::min(c4[0], c4[1]), std::min(c4[2], c4[3]));
-              b = std::max(std::max(c4[0], c4[1]), std::max(c4[2], c4[3]));
-            }
-            if (a > -lim && b < lim && l.lo > -lim && l.hi < lim && r.lo > -lim && r.hi < lim) { o.lo = a; o.hi = b; }
-          } else if (op == 4 && l.bounded && r.bounded && l.lo > -lim && l.hi < lim && r.lo > -lim && r.hi < lim) {
+            const Interval<i128> v = op == 1 ? l.iv + r.iv : op == 2 ? l.iv - r.iv : l.iv * r.iv;
+            if (exact(v) && exact(l.iv) && exact(r.iv)) o.iv = v;
+          } else if (op == 4 && l.bounded && r.bounded && exact(l.iv) && exact(r.iv)) {
             // fmod keeps the dividend's sign and stays below the divisor in magnitude
-            const i128 ml = std::max(l.lo < 0 ? -l.lo : l.lo, l.hi < 0 ? -l.hi : l.hi), mr = std::max(r.lo < 0 ? -r.lo : r.lo, r.hi < 0 ? -r.hi : r.hi);
-            const i128 m = std::min(ml, mr > 0 ? mr - 1 : (i128)0);
-            o.lo = l.lo < 0 ? -m : 0;
-            o.hi = l.hi > 0 ? m : 0;
+            const i128 mr = r.iv.mag();
+            const i128 m = std::min(l.iv.mag(), mr > 0 ? mr - 1 : (i128)0);
+            o.iv = {l.iv.lo < 0 ? -m : 0, l.iv.hi > 0 ? m : 0};
           }
         } else {
           const std::string a = l.f ? l.s : "ToF64<" + l.s + ">", b = r.f ? r.s : "ToF64<" + r.s + ">";
@@ -1500,466 +1506,496 @@ struct Lowering {
       }
     }
     if (st.size() != 1) return fail(LLKV_INTERNAL, "expression evaluation missing result");
-    *node = st[0].s;
-    *is_f64 = st[0].f;
-    last_planvalue.is_decimal = st[0].dec;
-    last_planvalue.scale = st[0].scale;
-    last_planvalue.lo = st[0].lo;
-    last_planvalue.hi = st[0].hi;
-    last_planvalue.bounded = st[0].bounded && !st[0].f;
+    out->node = st[0].s;
+    out->is_f64 = st[0].f;
+    out->pv.is_decimal = st[0].dec;
+    out->pv.scale = st[0].scale;
+    out->pv.iv = st[0].iv;
+    out->pv.bounded = st[0].bounded && !st[0].f;
+    return LLKV_OK;
+  }
+};
+
+static std::string aggs_string(const std::vector<std::string> &groups) { return Lowering::nary("Aggs", groups); }
+
+// Aggregate list → deduplicated lane groups (node strings + lane ops) and one AggOut per aggregate.
+struct AggLowering {
+  Lowering &L;
+  const ColumnResolver &resolve;
+  const bool grouped;
+  LoweredPlan &p;
+  std::vector<std::string> groups;              // lane-group node strings
+  std::vector<std::vector<uint8_t>> group_ops;  // … and their lane ops
+  std::vector<int> group_lane;                  // first lane (relative to the group's lane block) of each lane group
+  int next_lane = 0;
+  // shared-image plans: exchange lane j of a lane group = xf(kernel lane src) (LoweredPlan::image_src / image_xf)
+  using Expand = std::vector<std::pair<uint8_t, uint8_t>>;
+  std::vector<Expand> group_expand;
+  // … and the largest |contribution| a row makes to any lane of a lane group (counts: 1; SumI64Fast: max |v| of its column) when
+  // every lane of the group is a plain integer add; −1: the group needs 8-byte cells
+  std::vector<double> group_narrow;
+
+  AggLowering(Lowering &l, bool grouped_semantics) : L(l), resolve(l.resolve), grouped(grouped_semantics), p(l.p) {}
+
+  // `expand` empty = the kernel's lanes as they are.  A node an earlier group has shares that group (its expansion and bound too).
+  int add_group(const std::string &node, const std::vector<uint8_t> &lane_ops, Expand expand = {}, double narrow = -1.0) {
+    for (size_t i = 0; i < groups.size(); ++i) if (groups[i] == node) return group_lane[i];
+    group_narrow.push_back(narrow);
+    if (expand.empty()) for (size_t j = 0; j < lane_ops.size(); ++j) expand.emplace_back((uint8_t)j, (uint8_t)0);
+    groups.push_back(node);
+    group_lane.push_back(next_lane);
+    group_ops.push_back(lane_ops);
+    group_expand.push_back(expand);
+    next_lane += (int)lane_ops.size();
+    return group_lane.back();
+  }
+
+  // One aggregate's argument, lowered
+  struct Arg {
+    const llkv_aggregate_spec &s;
+    explicit Arg(const llkv_aggregate_spec &spec) : s(spec) {}
+    bool simple = false;            // a bare column …
+    const ColumnInfo *ci = nullptr; // … and which
+    std::string node;
+    bool is_f64 = false;
+    std::string valid;              // rows where the argument is non-NULL ("": all)
+    PlanValueInfo pv = {};          // grouped computed arguments
+    uint64_t rows = 0;              // most rows of any column of the expression
+    const char *fn() const { return s.kind == LLKV_AGG_SUM ? "SUM" : s.kind == LLKV_AGG_TOTAL ? "TOTAL" : s.kind == LLKV_AGG_AVG ? "AVG" : s.kind == LLKV_AGG_MIN ? "MIN" : "MAX"; }
+  };
+  uint64_t expr_rows(const llkv_aggregate_spec &s) const {
+    uint64_t rows = 0;
+    for (uint32_t k = 0; k < s.expr_len; ++k)
+      if (s.expr[k].kind == LLKV_TOK_COLUMN) { const ColumnInfo *ci = resolve(s.expr[k].field_id); if (ci) rows = std::max(rows, ci->rows); }
+    return rows;
+  }
+  static AggFinal sum_final(int32_t kind, AggFinal sum, AggFinal total, AggFinal avg) { return kind == LLKV_AGG_SUM ? sum : kind == LLKV_AGG_TOTAL ? total : avg; }
+
+  // A lane group for one aggregate: NULL argument rows contribute each lane's identity; one more lane counts the non-NULL rows
+  void add_agg(const Arg &a, AggOut &o, const std::string &inner, std::vector<uint8_t> lane_ops, Expand expand = {}, double narrow = -1.0) {
+    if (a.valid.empty()) { o.lane = add_group(inner, lane_ops, expand, narrow); return; }
+    const int n_inner = (int)lane_ops.size();
+    lane_ops.push_back(OP_ADD_I64);
+    if (!expand.empty()) { // the count of non-NULL rows is one more kernel lane behind the inner ones
+      uint8_t kernel_lanes = 0;
+      for (auto &x : expand) kernel_lanes = std::max<uint8_t>(kernel_lanes, (uint8_t)(x.first + 1));
+      expand.emplace_back(kernel_lanes, (uint8_t)0);
+    }
+    o.lane = add_group("IfValid<" + a.valid + "," + inner + ">", lane_ops, expand, narrow);
+    o.count_lane = o.lane + n_inner;
+  }
+
+  // ---- DISTINCT COUNT / SUM / TOTAL / AVG inside GROUP BY
+  // every group runs the reference's distinct accumulator over its own rows (llkv-executor/src/lib.rs:5222-5247):
+  // on the sort-based route the argument is one more sort key and the reduction counts the first row of
+  // every run of equal values
+  struct DistinctArg {
+    bool f = false, dec = false; // what the sum lanes add: Float64 / the raw 64-bit image of a Decimal, else Int64
+    bool bounded = false;        // integer sums: |v| ≤ mag over at most `rows` rows
+    u128 mag = 0;
+    uint64_t rows = 0;
+    const ColumnInfo *ci = nullptr;
+    const char *unbounded = "", *overflow = ""; // the refusals of an integer sum whose checked_add chain could overflow in some order
+  };
+  // a bare column.  DistinctKey::from_array (llkv-aggregate/src/lib.rs:261-331): Int by value, Float by bits, Str by its string (here: its
+  // dictionary code — the staged dictionary holds every string once), Bool, Date by its day number; what SUM / TOTAL / AVG
+  // add for the last three is their numeric image in the Float64 accumulators (:400-449,889-924,1035-1066,1200-1232)
+  int distinct_column(const llkv_aggregate_spec &s, DistinctArg *d) {
+    if (p.distinct_proj) return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates over more than one argument in a GROUP BY");
+    const ColumnInfo *dci = resolve(s.expr[0].field_id);
+    if (!dci) return L.fail(LLKV_INVALID_ARGUMENT, "unknown column '" + std::to_string(s.expr[0].field_id) + "' in aggregate");
+    if (utf8_wide(*dci)) return L.fail(LLKV_UNSUPPORTED, L.wide_utf8_refusal(*dci, "a DISTINCT aggregate"));
+    const bool keyed = dci->dtype == LLKV_DT_UTF8 || dci->dtype == LLKV_DT_BOOLEAN || dci->dtype == LLKV_DT_DATE32;
+    // … and Decimal by its raw value (the 64-bit image; Sum / Total / AvgDistinctDecimal128 :943-967,1089-1112,1260-1284)
+    d->dec = dci->dtype == LLKV_DT_DECIMAL128 && !dci->wide128;
+    if (dci->dtype != LLKV_DT_INT64 && dci->dtype != LLKV_DT_FLOAT64 && !keyed && !d->dec) return L.fail(LLKV_UNSUPPORTED, std::string("DISTINCT aggregate over ") + dtype_name(dci->dtype));
+    if (p.distinct_field >= 0 && p.distinct_field != (int64_t)s.expr[0].field_id)
+      return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates over more than one column in a GROUP BY");
+    p.distinct_field = s.expr[0].field_id;
+    p.distinct_numeric = dci->dtype == LLKV_DT_UTF8 ? 1u : dci->dtype == LLKV_DT_BOOLEAN ? 2u : dci->dtype == LLKV_DT_DATE32 ? 3u : 0u;
+    if (dci->dtype == LLKV_DT_UTF8 && p.distinct_dict_num.empty()) {
+      p.distinct_dict_num.assign(256, 0.0);
+      for (size_t c = 0; c < dci->dictionary.size() && c < 256; ++c) p.distinct_dict_num[c] = parse_numeric_or_zero(dci->dictionary[c]);
+    }
+    d->ci = dci;
+    d->f = dci->dtype == LLKV_DT_FLOAT64 || keyed;
+    d->bounded = dci->has_stats;
+    d->mag = stats_mag(*dci);
+    d->rows = dci->rows;
+    d->unbounded = "SUM(DISTINCT) over an integer column without statistics (order-dependent overflow check)";
+    d->overflow = "possible i64 overflow in SUM(DISTINCT): order-dependent check is not on the GPU path";
+    return LLKV_OK;
+  }
+  // a computed argument: the group's temp column holds the PlanValue of every row (llkv-executor/src/lib.rs:5186-5199) and the
+  // distinct accumulator runs over it — Int by value, Float by bits.  The values are computed once for the selected rows by a
+  // projection plan of their own and sort as a column's cells would.
+  int distinct_computed(const llkv_aggregate_spec &s, DistinctArg *d) {
+    int rc;
+    if (p.distinct_field >= 0) return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates over more than one argument in a GROUP BY");
+    auto dp = std::make_shared<LoweredPlan>();
+    Lowering LP{resolve, *dp, L.err, true};
+    Lowering::ExactNan exact(LP); // the values are told apart by their bits
+    Lowered x;
+    std::string dvalid;
+    if ((rc = LP.expr_planvalue(s.expr, s.expr_len, &x))) return rc;
+    if (x.pv.is_decimal) return L.fail(LLKV_UNSUPPORTED, "DISTINCT inside GROUP BY over a computed decimal argument");
+    if ((rc = LP.valid_of_node(s.expr, s.expr_len, x.node, true, &dvalid))) return rc;
+    auto same_tokens = [&]() {
+      if (p.distinct_tokens.size() != s.expr_len) return false;
+      for (uint32_t k = 0; k < s.expr_len; ++k) {
+        const llkv_expr_token &a = p.distinct_tokens[k], &b = s.expr[k];
+        if (a.kind != b.kind) return false;
+        if (a.kind == LLKV_TOK_COLUMN && a.field_id != b.field_id) return false;
+        if (a.kind == LLKV_TOK_BINARY && a.binop != b.binop) return false;
+        if (a.kind == LLKV_TOK_LITERAL && (a.literal.tag != b.literal.tag || a.literal.scale != b.literal.scale || a.literal.lo != b.literal.lo || a.literal.hi != b.literal.hi ||
+                                           std::memcmp(&a.literal.f64, &b.literal.f64, 8) != 0)) return false;
+      }
+      return true;
+    };
+    if (p.distinct_proj && !same_tokens()) return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates over more than one argument in a GROUP BY");
+    if (!p.distinct_proj) {
+      p.distinct_tokens.assign(s.expr, s.expr + s.expr_len);
+      for (auto &tk : p.distinct_tokens) tk.literal.str = nullptr; // (numeric literals only: expr_planvalue took nothing else)
+      dp->out_dtypes = {x.is_f64 ? LLKV_DT_FLOAT64 : LLKV_DT_INT64};
+      dp->out_fields = {-1};
+      dp->out_nullable = {!dvalid.empty()};
+      dp->type_string = "ProjPlan<" + cols_string(*dp, &dp->bytes_per_row) + ",Outs<" + (dvalid.empty() ? x.node : "OutV<" + x.node + "," + dvalid + ">") + ">>";
+      p.distinct_proj = dp;
+      p.distinct_node = x.node;
+      p.distinct_numeric = 0;
+    }
+    d->f = x.is_f64;
+    d->bounded = x.pv.bounded;
+    d->mag = (u128)x.pv.iv.mag();
+    d->rows = expr_rows(s);
+    d->unbounded = d->overflow = "possible i64 overflow in SUM(DISTINCT) over a computed argument: order-dependent check is not on the GPU path";
+    return LLKV_OK;
+  }
+  int distinct(const llkv_aggregate_spec &s, AggOut &o) {
+    int rc;
+    if (!L.allow_sorted_distinct) return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates inside GROUP BY run on the sort-based route");
+    if (s.kind != LLKV_AGG_COUNT && s.kind != LLKV_AGG_SUM && s.kind != LLKV_AGG_TOTAL && s.kind != LLKV_AGG_AVG)
+      return L.fail(LLKV_UNSUPPORTED, "DISTINCT form of aggregate kind " + std::to_string(s.kind));
+    if (!s.expr || s.expr_len == 0) return L.fail(LLKV_INVALID_ARGUMENT, "aggregate requires an argument");
+    const bool simple = s.expr_len == 1 && s.expr[0].kind == LLKV_TOK_COLUMN;
+    DistinctArg d;
+    if ((rc = simple ? distinct_column(s, &d) : distinct_computed(s, &d))) return rc;
+    const int count_lane = add_group("DistinctCount", {OP_ADD_I64});
+    if (s.kind == LLKV_AGG_COUNT) { o.fin = AggFinal::CountValid; o.lane = count_lane; return LLKV_OK; }
+    if (!d.f && (s.kind != LLKV_AGG_TOTAL || d.dec)) { // the checked_add chain over the distinct values cannot overflow whatever their order (decimals: the i64 lane holds their i128 sum)
+      if (!d.bounded) return L.fail(LLKV_UNSUPPORTED, d.unbounded);
+      if (d.mag * (u128)d.rows > (u128)INT64_MAX) return L.fail(LLKV_UNSUPPORTED, d.overflow);
+    }
+    o.count_lane = count_lane;
+    o.typed_by_first_value = !simple; // (a group without a non-NULL value: the temp column is an Int64 column — SUM comes back as an Int64 NULL)
+    if (d.dec) { // finalize :1583-1612,1656-1672,1762-1800: i128 sum with the column's (precision, scale); SUM / AVG are NULL without a value
+      o.fin = sum_final(s.kind, AggFinal::SumDec, AggFinal::TotalDec, AggFinal::AvgDec);
+      o.precision = d.ci->precision; o.scale = d.ci->scale;
+      o.fast_sum = true;
+      o.null_without_values = s.kind != LLKV_AGG_TOTAL;
+      o.lane = add_group("DistinctSumI64", {OP_ADD_I64});
+      return LLKV_OK;
+    }
+    o.nan_default = simple && d.ci->dtype == LLKV_DT_FLOAT64 && d.ci->f_no_nan; // (AggOut::nan_default: the distinct values' ∞ − ∞)
+    if (s.kind == LLKV_AGG_TOTAL) { o.fin = AggFinal::TotalF64; o.lane = add_group(d.f ? "DistinctSumF64" : "DistinctTotalI64", {OP_ADD_F64}); }
+    else if (d.f) { o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumF64 : AggFinal::AvgF64; o.lane = add_group("DistinctSumF64", {OP_ADD_F64}); }
+    else { o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumI64Fast : AggFinal::AvgI64Fast; o.lane = add_group("DistinctSumI64", {OP_ADD_I64}); }
+    return LLKV_OK;
+  }
+
+  // ---- the argument: node, type and the rows where it is non-NULL (NULL propagates through arithmetic, x / 0 is NULL; accumulators
+  // skip NULLs, llkv-aggregate/src/lib.rs:769-786,801-830)
+  int argument(Arg *a) {
+    const llkv_aggregate_spec &s = a->s;
+    int rc;
+    if (!s.expr || s.expr_len == 0) return L.fail(LLKV_INVALID_ARGUMENT, "aggregate requires an argument");
+    a->simple = s.expr_len == 1 && s.expr[0].kind == LLKV_TOK_COLUMN;
+    if (a->simple) {
+      a->ci = resolve(s.expr[0].field_id);
+      if (!a->ci) return L.fail(LLKV_INVALID_ARGUMENT, "unknown column '" + std::to_string(s.expr[0].field_id) + "' in aggregate");
+      std::vector<std::string> vs;
+      if ((rc = L.valid_of_expr(s.expr, s.expr_len, &vs))) return rc;
+      a->valid = Lowering::all_of(vs);
+      return LLKV_OK;
+    }
+    Lowered x;
+    if ((rc = grouped ? L.expr_planvalue(s.expr, s.expr_len, &x) : L.expr_fast(s.expr, s.expr_len, &x))) return rc;
+    if (!grouped && x.fit32) return L.fail(LLKV_UNSUPPORTED, "aggregate over a 32-bit-only integer expression (the reference has no Int32 accumulator)");
+    a->node = x.node;
+    a->is_f64 = x.is_f64;
+    a->pv = x.pv;
+    // (what can make the value NULL is read off the expression the scan evaluates: the simplified one — a division of
+    // constants is gone from it — where the GROUP BY route reads the original)
+    std::vector<llkv_expr_token> folded;
+    if (!grouped && (rc = L.fold_constants(s.expr, s.expr_len, &folded))) return rc;
+    if ((rc = grouped ? L.valid_of_node(s.expr, s.expr_len, a->node, grouped, &a->valid) : L.valid_of_node(folded.data(), (uint32_t)folded.size(), a->node, grouped, &a->valid))) return rc;
+    if (a->pv.is_decimal) a->rows = expr_rows(s);
+    return LLKV_OK;
+  }
+  // a bare column as an accumulator's input (validate_aggregate_type llkv-executor/src/lib.rs:5946-5988)
+  int column_node(Arg *a) {
+    const int32_t dt = a->ci->dtype;
+    const uint32_t field = a->s.expr[0].field_id;
+    // Utf8 / Boolean / Date32 inputs get Float64 accumulators fed by array_value_to_numeric (llkv-aggregate/src/lib.rs:
+    // 400-449): strings parse or count as 0, booleans are 0 / 1; Date32 has no arm there — the first non-NULL row fails
+    if (dt == LLKV_DT_DATE32)
+      return L.fail(LLKV_UNSUPPORTED, std::string(a->fn()) + " over Date32 (the reference fails at the first non-NULL row) is not on the GPU path");
+    if (dt != LLKV_DT_INT64 && dt != LLKV_DT_FLOAT64 && dt != LLKV_DT_DECIMAL128 && dt != LLKV_DT_UTF8 && dt != LLKV_DT_BOOLEAN)
+      return L.fail(LLKV_INVALID_ARGUMENT, std::string(a->fn()) + " aggregate not supported for column type " + dtype_name(dt));
+    const ColumnInfo *ci;
+    int slot, rc;
+    if (utf8_wide(*a->ci)) return L.fail(LLKV_UNSUPPORTED, L.wide_utf8_refusal(*a->ci, a->fn()));
+    if ((rc = L.slot_of(field, &ci, &slot))) return rc;
+    if (dt == LLKV_DT_UTF8) {
+      if (!L.allow_dict_num) return L.fail(LLKV_UNSUPPORTED, std::string(a->fn()) + " over a Utf8 column is not on this route");
+      a->node = "DictNum<" + std::to_string(slot) + ">";
+      bool have = false;
+      for (auto &d : p.dict_num) have |= d.first == slot;
+      if (!have) {
+        std::vector<double> image(256, 0.0);
+        for (size_t c = 0; c < ci->dictionary.size() && c < 256; ++c) image[c] = parse_numeric_or_zero(ci->dictionary[c]);
+        p.dict_num.emplace_back(slot, std::move(image));
+      }
+    } else if (dt == LLKV_DT_BOOLEAN) {
+      a->node = "ToF64<" + L.col_node(slot, dt) + ">";
+    } else {
+      a->node = L.col_node(slot, dt);
+    }
+    a->is_f64 = dt == LLKV_DT_FLOAT64 || dt == LLKV_DT_UTF8 || dt == LLKV_DT_BOOLEAN;
+    return LLKV_OK;
+  }
+
+  // ---- COUNT / COUNT_NULLS.  NULL-free argument: COUNT(x) = rows, COUNT_NULLS(x) = 0
+  void count(const Arg &a, AggOut &o) {
+    const bool is_count = a.s.kind == LLKV_AGG_COUNT;
+    if (!a.simple && !grouped) {
+      // a computed argument is evaluated for its checked-arithmetic errors even though only its validity counts
+      o.fin = is_count ? AggFinal::CountValid : AggFinal::CountNulls;
+      o.lane = add_group("CountIfE<" + (a.valid.empty() ? std::string("True") : a.valid) + "," + a.node + ">", {OP_ADD_I64});
+    } else if (a.valid.empty()) o.fin = is_count ? AggFinal::CountRows : AggFinal::CountNullsZero;
+    else {
+      o.fin = is_count ? AggFinal::CountValid : AggFinal::CountNulls;
+      o.lane = add_group("CountIf<" + a.valid + ">", {OP_ADD_I64}, {}, 1.0);
+    }
+  }
+
+  // ---- a bare Decimal128 column with values beyond 64 bits (llkv-aggregate/src/lib.rs:925-943: `sum.checked_add(v)` in i128, row by row):
+  // four ADD_I64 lanes over the 32-bit limbs (the top one signed) — exact for < 2^31 rows, order-free.  The
+  // reference's overflow check is order dependent (a prefix may leave i128 although the total fits): the plan is
+  // taken only when rows · max|v| ≤ i128::MAX excludes that.  AVG: half away from zero (:1720-1742).
+  int wide_decimal(const Arg &a, AggOut &o) {
+    const llkv_aggregate_spec &s = a.s;
+    const ColumnInfo &ci = *a.ci;
+    int rc, lo, hi;
+    o.precision = ci.precision; o.scale = ci.scale;
+    o.wide = true;
+    if (s.kind == LLKV_AGG_MIN || s.kind == LLKV_AGG_MAX) {
+      // MinDecimal128 / MaxDecimal128 (llkv-aggregate/src/lib.rs:1332-1352,1400-1420: i128 min / max over the non-NULL rows).  A
+      // 128-bit compare has no order-free lanes, but a column whose values span less than 2^64 — known from staging — needs
+      // none: v − min(column) fits 64 bits and is the low halves' wrapping difference, so MAX is one MAX_U64 lane over
+      // lo − min_lo and MIN one over max_lo − lo; the host adds the column's min / max back in i128.
+      const i128 vmin = (i128)(((u128)ci.wide_min_hi << 64) | ci.wide_min_lo), vmax = (i128)(((u128)ci.wide_max_hi << 64) | ci.wide_max_lo);
+      if (vmax < vmin || (u128)(vmax - vmin) >> 64)
+        return L.fail(LLKV_UNSUPPORTED, std::string(a.fn()) + " over Decimal128 values beyond 64 bits that span 2^64 or more (a 128-bit compare has no order-free lanes) is not on the GPU path");
+      if ((rc = L.wide_slots_of(s.expr[0].field_id, &lo, &hi, /*want_hi=*/false))) return rc;
+      const bool is_min = s.kind == LLKV_AGG_MIN;
+      std::string base;
+      if ((rc = L.lit_i((int64_t)(is_min ? ci.wide_max_lo : ci.wide_min_lo), &base, "LitU"))) return rc;
+      o.wide_delta = is_min ? 2 : 1;
+      o.wide_base_hi = is_min ? ci.wide_max_hi : ci.wide_min_hi;
+      o.wide_base_lo = is_min ? ci.wide_max_lo : ci.wide_min_lo;
+      o.fin = is_min ? AggFinal::MinDec : AggFinal::MaxDec;
+      add_agg(a, o, "MaxWideDelta<" + std::to_string(lo) + "," + base + "," + (is_min ? "1" : "0") + ">", {OP_MAX_U64});
+      return LLKV_OK;
+    }
+    if (s.kind != LLKV_AGG_SUM && s.kind != LLKV_AGG_TOTAL && s.kind != LLKV_AGG_AVG) return L.fail(LLKV_UNSUPPORTED, "aggregate kind " + std::to_string(s.kind));
+    const u128 absmax = ((u128)ci.wide_absmax_hi << 64) | ci.wide_absmax_lo;
+    const u128 i128_max = ~(u128)0 >> 1;
+    if (ci.rows >= (1ull << 31) || (absmax != 0 && (u128)ci.rows > i128_max / absmax))
+      return L.fail(LLKV_UNSUPPORTED, "possible Decimal128 sum overflow (rows · max|v| exceeds i128): the reference's check is order dependent");
+    if ((rc = L.wide_slots_of(s.expr[0].field_id, &lo, &hi))) return rc;
+    o.fin = sum_final(s.kind, AggFinal::SumDec, AggFinal::TotalDec, AggFinal::AvgDec);
+    add_agg(a, o, "SumDecWide<" + std::to_string(lo) + "," + std::to_string(hi) + ">", {OP_ADD_I64, OP_ADD_I64, OP_ADD_I64, OP_ADD_I64});
+    return LLKV_OK;
+  }
+
+  // ---- Decimal128 accumulators (llkv-aggregate/src/lib.rs:925-967,1071-1088,1236-1259,1332-1352,1400-1420) over the 64-bit image of a
+  // bare column or of a computed argument: the same exact lanes as Int64, finalized in i128 with (precision, scale).
+  // `fast_sum`: the statistics exclude i64 overflow of any prefix sum — one wrapping lane
+  int decimal64(const Arg &a, AggOut &o, int32_t precision, int32_t scale, bool fast_sum) {
+    o.precision = precision; o.scale = scale;
+    o.fast_sum = fast_sum;
+    switch (a.s.kind) {
+    case LLKV_AGG_SUM: case LLKV_AGG_TOTAL: case LLKV_AGG_AVG:
+      o.fin = sum_final(a.s.kind, AggFinal::SumDec, AggFinal::TotalDec, AggFinal::AvgDec);
+      if (fast_sum) add_agg(a, o, "SumI64Fast<" + a.node + ">", {OP_ADD_I64});
+      else add_agg(a, o, "SumI64<" + a.node + ">", {OP_ADD_I64, OP_ADD_I64, OP_MAX_U64});
+      break;
+    case LLKV_AGG_MIN: o.fin = AggFinal::MinDec; add_agg(a, o, "MinI64<" + a.node + ">", {OP_MIN_I64}); break;
+    case LLKV_AGG_MAX: o.fin = AggFinal::MaxDec; add_agg(a, o, "MaxI64<" + a.node + ">", {OP_MAX_I64}); break;
+    default: return L.fail(LLKV_UNSUPPORTED, "aggregate kind " + std::to_string(a.s.kind));
+    }
+    return LLKV_OK;
+  }
+
+  // ---- SUM / TOTAL / AVG / MIN / MAX over Int64 and Float64 arguments
+  // The lanes of an f64 sum.  Plans that need order-free sums (shared-image plans, the exact-sum option): SumF64<node> →
+  // SumF64Q2 / SumF64Q (fixed point) or SumF64X<node, C1, C2, …> (exact grid levels); all need a bound on |argument|
+  int sum_f64(const Arg &a, AggOut &o, const std::string &arg) {
+    if (!L.exact_f64) { add_agg(a, o, "SumF64<" + arg + ">", {OP_ADD_F64}); return LLKV_OK; }
+    const Lowering::Bounds b = L.expr_bounds(a.s.expr, a.s.expr_len);
+    const uint64_t n_rows = a.ci ? a.ci->rows : L.table_rows; // (after expr_bounds: it counts this argument's columns in)
+    double c[4];
+    int levels = 0, e = 0;
+    std::string scale_lit;
+    if (!L.image_plan && b.ok && b.all_finite && L.exact_fixed_point(b.absmax, b.nzmin, n_rows, &e) && L.lit_f(std::ldexp(1.0, -e), &scale_lit) == 0) {
+      o.fixed_point = true;
+      o.fixed_exp = e;
+      add_agg(a, o, "SumF64Q2<" + arg + "," + scale_lit + ">", {OP_ADD_I64, OP_ADD_I64});
+      return LLKV_OK;
+    }
+    if (L.image_plan && b.ok && b.all_finite && !std::getenv("LLKV_HIP_IMAGE_NO_FIXED") && L.fixed_point_grid(b.absmax, b.nzmin, n_rows, &e) &&
+        L.lit_f(std::ldexp(1.0, -e), &scale_lit) == 0) { // one integer lane in the image, two in the exchange image
+      o.fixed_point = true;
+      o.fixed_exp = e;
+      p.image_min_grid = 256;
+      add_agg(a, o, "SumF64Q<" + arg + "," + scale_lit + ">", {OP_ADD_I64, OP_ADD_I64}, {{0, 1}, {0, 2}});
+      return LLKV_OK;
+    }
+    if (b.ok) levels = L.exact_sum_constants(b.absmax, b.nzmin, n_rows, c);
+    std::string node_x = "SumF64X<" + arg;
+    std::vector<uint8_t> lane_ops;
+    for (int j = 0; j < levels; ++j) {
+      std::string lit;
+      if (L.lit_f(c[j], &lit)) { levels = 0; break; }
+      node_x += "," + lit;
+      lane_ops.push_back(OP_ADD_F64);
+    }
+    if (levels == 0)
+      return L.fail(LLKV_UNSUPPORTED, std::string("the column statistics do not bound an f64 sum argument from above and (where non-zero) from below: no exact, order-free sum for ") + (L.image_plan ? "the shared-image GROUP BY" : "the exact-sum option"));
+    o.exact_levels = levels;
+    add_agg(a, o, node_x + ">", lane_ops);
+    return LLKV_OK;
+  }
+  int numeric(const Arg &a, AggOut &o) {
+    const llkv_aggregate_spec &s = a.s;
+    const std::string &node = a.node;
+    const bool f64_column = a.simple && a.ci->dtype == LLKV_DT_FLOAT64;
+    // statistics that exclude i64 overflow of any prefix sum: rows · max|v| ≤ i64::MAX — one wrapping lane; shared-image plans
+    // may then keep it in a 4-byte cell (SumI64Fast over a plain integer column: max |v|; with IfValid: + a count lane)
+    const bool fast_i64 = !a.is_f64 && a.simple && a.ci->has_stats && stats_mag(*a.ci) * (u128)a.ci->rows <= (u128)INT64_MAX;
+    const auto sum_i64 = [&]() {
+      if (fast_i64) add_agg(a, o, "SumI64Fast<" + node + ">", {OP_ADD_I64}, {}, std::max(1.0, std::max(std::fabs((double)a.ci->min_i), std::fabs((double)a.ci->max_i))));
+      else add_agg(a, o, "SumI64<" + node + ">", {OP_ADD_I64, OP_ADD_I64, OP_MAX_U64});
+    };
+    // MinFloat64 / MaxFloat64 (llkv-aggregate/src/lib.rs:1309-1331,1377-1399) fold sequentially by partial_cmp: a leading NaN sticks,
+    // ±0 ties keep the earlier row — which costs two row-order lanes beside the order key.  A bare Float64 column whose staging
+    // statistics say "no NaN / ±∞, no −0.0" has neither case: one order-key lane (a third of the DS instructions)
+    const bool plain_f64 = f64_column && a.ci->has_fstats && a.ci->f_all_finite && a.ci->f_no_neg_zero && !std::getenv("LLKV_HIP_MINMAX_ROW_ORDER");
+    // a NaN sum of a bare Float64 column without NaN cells is the reference's default NaN (AggOut::nan_default)
+    o.nan_default = f64_column && a.ci->f_no_nan && (s.kind == LLKV_AGG_SUM || s.kind == LLKV_AGG_TOTAL || s.kind == LLKV_AGG_AVG);
+    switch (s.kind) {
+    case LLKV_AGG_SUM: case LLKV_AGG_AVG: {
+      const bool sum = s.kind == LLKV_AGG_SUM;
+      if (a.is_f64) { o.fin = sum ? AggFinal::SumF64 : AggFinal::AvgF64; return sum_f64(a, o, node); }
+      o.fin = fast_i64 ? (sum ? AggFinal::SumI64Fast : AggFinal::AvgI64Fast) : (sum ? AggFinal::SumI64 : AggFinal::AvgI64);
+      sum_i64();
+      break;
+    }
+    case LLKV_AGG_TOTAL:
+      o.fin = AggFinal::TotalF64;
+      return sum_f64(a, o, a.is_f64 ? node : "ToF64<" + node + ">");
+    case LLKV_AGG_MIN:
+      if (a.is_f64 && plain_f64) { o.fin = AggFinal::MinF64; o.plain_minmax = true; add_agg(a, o, "MinF64P<" + node + ">", {OP_MIN_I64}); }
+      else if (a.is_f64) { o.fin = AggFinal::MinF64; add_agg(a, o, "MinF64<" + node + ">", {OP_MIN_I64, OP_MIN_I64, OP_MIN_I64}); }
+      else { o.fin = AggFinal::MinI64; add_agg(a, o, "MinI64<" + node + ">", {OP_MIN_I64}); }
+      break;
+    case LLKV_AGG_MAX:
+      if (a.is_f64 && plain_f64) { o.fin = AggFinal::MaxF64; o.plain_minmax = true; add_agg(a, o, "MaxF64P<" + node + ">", {OP_MAX_I64}); }
+      else if (a.is_f64) { o.fin = AggFinal::MaxF64; add_agg(a, o, "MaxF64<" + node + ">", {OP_MAX_I64, OP_MIN_I64, OP_MIN_I64}); }
+      else { o.fin = AggFinal::MaxI64; add_agg(a, o, "MaxI64<" + node + ">", {OP_MAX_I64}); }
+      break;
+    default: return L.fail(LLKV_UNSUPPORTED, "aggregate kind " + std::to_string(s.kind));
+    }
+    return LLKV_OK;
+  }
+
+  // ---- computed decimal arguments of a GROUP BY: the digit count of each group's first non-NULL value types its temp column
+  // (FirstDigits, fused_scan.hip.h) — arguments that are NULL in the same rows share a lane, packed after the last aggregate
+  struct PendingDigits { size_t agg; std::string valid, node; int dlo, dhi, scale; uint64_t rows; };
+  std::vector<PendingDigits> pending_digits;
+  void want_digits(const Arg &a) {
+    auto digits_of = [](i128 v) { int d = 0; u128 m = (u128)v; do { m /= 10; ++d; } while (m); return d; };
+    const i128 alo = abs_of(a.pv.iv.lo), ahi = abs_of(a.pv.iv.hi);
+    pending_digits.push_back({p.aggs.size(), a.valid.empty() ? "True" : a.valid, a.node, (a.pv.iv.lo <= 0 && a.pv.iv.hi >= 0) ? 1 : digits_of(std::min(alo, ahi)), digits_of(std::max(alo, ahi)),
+                              a.pv.scale, a.rows});
+  }
+  // FirstDigits lanes: per validity, the distinct argument nodes in packs of up to four 6-bit digit fields under the row id
+  // (the key must stay below 2^63: four fields leave 39 bits for the row id, one field 57)
+  void pack_first_digits() {
+    std::vector<bool> placed(pending_digits.size(), false);
+    for (size_t i = 0; i < pending_digits.size(); ++i) {
+      if (placed[i]) continue;
+      std::vector<size_t> nodes; // indices of the first pending entry of every distinct node in this pack
+      uint64_t rows = 0;
+      for (size_t j = i; j < pending_digits.size(); ++j) rows = std::max(rows, pending_digits[j].rows);
+      const size_t per_pack = rows < (1ull << 38) ? 4 : 1;
+      for (size_t j = i; j < pending_digits.size(); ++j) {
+        if (placed[j] || pending_digits[j].valid != pending_digits[i].valid) continue;
+        bool known = false;
+        for (size_t k : nodes) known |= pending_digits[k].node == pending_digits[j].node;
+        if (!known) { if (nodes.size() == per_pack) continue; nodes.push_back(j); }
+        placed[j] = true;
+      }
+      std::string g = "FirstDigits<" + pending_digits[i].valid;
+      for (size_t k : nodes) g += ",DecDigits<" + pending_digits[k].node + "," + std::to_string(pending_digits[k].dlo) + "," + std::to_string(pending_digits[k].dhi) + ">";
+      g += ">";
+      const int lane = add_group(g, {OP_MIN_I64});
+      for (size_t j = i; j < pending_digits.size(); ++j) {
+        if (!placed[j] || pending_digits[j].valid != pending_digits[i].valid || p.aggs[pending_digits[j].agg].digits_lane >= 0) continue;
+        for (size_t at = 0; at < nodes.size(); ++at)
+          if (pending_digits[nodes[at]].node == pending_digits[j].node) {
+            p.aggs[pending_digits[j].agg].digits_lane = lane;
+            p.aggs[pending_digits[j].agg].digits_shift = 6 * (int)(nodes.size() - 1 - at);
+            p.aggs[pending_digits[j].agg].scale = pending_digits[j].scale;
+          }
+      }
+    }
+  }
+
+  int one(const llkv_aggregate_spec &s, AggOut &o) {
+    int rc;
+    if (s.distinct && s.kind != LLKV_AGG_MIN && s.kind != LLKV_AGG_MAX && s.kind != LLKV_AGG_COUNT_STAR) return distinct(s, o);
+    if (s.distinct && s.kind == LLKV_AGG_COUNT_STAR) return L.fail(LLKV_UNSUPPORTED, "COUNT(DISTINCT *)");
+    if (s.kind == LLKV_AGG_COUNT_STAR) return LLKV_OK;
+    Arg a(s);
+    if ((rc = argument(&a))) return rc;
+    // a computed decimal argument: every aggregate kind — COUNT too — goes through the group's temp column (llkv-executor/src/lib.rs:5186-5199)
+    if (a.pv.is_decimal) want_digits(a);
+    if (s.kind == LLKV_AGG_COUNT || s.kind == LLKV_AGG_COUNT_NULLS) { count(a, o); return LLKV_OK; }
+    if (a.simple && a.ci->wide128) return wide_decimal(a, o);
+    if (a.simple) {
+      if ((rc = column_node(&a))) return rc;
+      if (a.ci->dtype == LLKV_DT_DECIMAL128) return decimal64(a, o, a.ci->precision, a.ci->scale, a.ci->has_stats && stats_mag(*a.ci) * (u128)a.ci->rows <= (u128)INT64_MAX);
+    } else {
+      o.typed_by_first_value = grouped; // (a bare column keeps its own type: only a computed argument becomes a temp column)
+      // precision = digits of the group's first non-NULL value (filled in at finalize from the FirstDigits lane), scale = the expression's
+      if (a.pv.is_decimal) return decimal64(a, o, 0, a.pv.scale, a.rows != 0 && (u128)a.pv.iv.mag() * (u128)a.rows <= (u128)INT64_MAX);
+    }
+    return numeric(a, o);
+  }
+  int run(const llkv_aggregate_spec *aggs, uint32_t n_aggs) {
+    for (uint32_t i = 0; i < n_aggs; ++i) {
+      AggOut o{AggFinal::CountRows, -1};
+      if (int rc = one(aggs[i], o)) return rc;
+      p.aggs.push_back(o);
+    }
+    pack_first_digits();
     return LLKV_OK;
   }
 };
 
 } // namespace
-
-// Aggregate list → deduplicated lane groups (node strings + lane ops) and one AggOut per aggregate.
-static int lower_aggregates(Lowering &L, const ColumnResolver &resolve, const llkv_aggregate_spec *aggs, uint32_t n_aggs, bool grouped,
-                            std::vector<std::string> &groups, std::vector<std::vector<uint8_t>> &group_ops, int &next_lane) {
-  LoweredPlan &p = L.p;
-  int rc;
-  std::vector<int> group_lane;     // first lane (relative to base) of each lane group
-  auto add_group = [&](const std::string &node, std::vector<uint8_t> lane_ops) -> int {
-    std::vector<std::pair<uint8_t, uint8_t>> expand;
-    expand.swap(L.next_expand);
-    const double narrow = L.next_narrow;
-    L.next_narrow = -1.0;
-    for (size_t i = 0; i < groups.size(); ++i) if (groups[i] == node) return group_lane[i];
-    L.group_narrow.push_back(narrow);
-    if (expand.empty()) for (size_t j = 0; j < lane_ops.size(); ++j) expand.emplace_back((uint8_t)j, (uint8_t)0);
-    groups.push_back(node);
-    group_lane.push_back(next_lane);
-    group_ops.push_back(lane_ops);
-    L.group_expand.push_back(expand);
-    next_lane += (int)lane_ops.size();
-    return group_lane.back();
-  };
-  enum { ADD_F64 = 0, ADD_I64 = 1, MIN_I64 = 2, MAX_I64 = 3, MAX_U64 = 4 };
-  // computed decimal arguments of a GROUP BY: the digit count of each group's first non-NULL value types its temp column
-  // (FirstDigits, fused_scan.hip.h) — arguments that are NULL in the same rows share a lane, packed after the loop
-  struct PendingDigits { size_t agg; std::string valid, node; int dlo, dhi, scale; uint64_t rows; };
-  std::vector<PendingDigits> pending_digits;
-  auto digits_of = [](i128 v) { int d = 0; u128 m = v < 0 ? (u128)(-v) : (u128)v; do { m /= 10; ++d; } while (m); return d; };
-
-  for (uint32_t a = 0; a < n_aggs; ++a) {
-    const llkv_aggregate_spec &s = aggs[a];
-    AggOut o{AggFinal::CountRows, -1};
-    if (s.distinct && s.kind != LLKV_AGG_MIN && s.kind != LLKV_AGG_MAX && s.kind != LLKV_AGG_COUNT_STAR) {
-      // every group runs the reference's distinct accumulator over its own rows (llkv-executor/src/lib.rs:5222-5247):
-      // on the sort-based route the argument column is one more sort key and the reduction counts the first row of
-      // every run of equal values
-      if (!L.allow_sorted_distinct) return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates inside GROUP BY run on the sort-based route");
-      if (s.kind != LLKV_AGG_COUNT && s.kind != LLKV_AGG_SUM && s.kind != LLKV_AGG_TOTAL && s.kind != LLKV_AGG_AVG)
-        return L.fail(LLKV_UNSUPPORTED, "DISTINCT form of aggregate kind " + std::to_string(s.kind));
-      if (!s.expr || s.expr_len == 0) return L.fail(LLKV_INVALID_ARGUMENT, "aggregate requires an argument");
-      if (s.expr_len != 1 || s.expr[0].kind != LLKV_TOK_COLUMN) {
-        // a computed argument: the group's temp column holds the PlanValue of every row (llkv-executor/src/lib.rs:5186-5199) and the
-        // distinct accumulator runs over it — Int by value, Float by bits.  The values are computed once for the selected rows by a
-        // projection plan of their own and sort as a column's cells would.
-        if (p.distinct_field >= 0) return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates over more than one argument in a GROUP BY");
-        auto dp = std::make_shared<LoweredPlan>();
-        Lowering LP{resolve, *dp, L.err, true};
-        LP.exact_nan = true; // the values are told apart by their bits
-        std::string dnode, dvalid;
-        bool df = false;
-        if ((rc = LP.expr_planvalue(s.expr, s.expr_len, &dnode, &df))) return rc;
-        const PlanValueInfo dpv = LP.last_planvalue;
-        if (dpv.is_decimal) return L.fail(LLKV_UNSUPPORTED, "DISTINCT inside GROUP BY over a computed decimal argument");
-        if ((rc = LP.valid_of_node(s.expr, s.expr_len, dnode, true, &dvalid))) return rc;
-        auto same_tokens = [&]() {
-          if (p.distinct_tokens.size() != s.expr_len) return false;
-          for (uint32_t k = 0; k < s.expr_len; ++k) {
-            const llkv_expr_token &x = p.distinct_tokens[k], &y = s.expr[k];
-            if (x.kind != y.kind) return false;
-            if (x.kind == LLKV_TOK_COLUMN && x.field_id != y.field_id) return false;
-            if (x.kind == LLKV_TOK_BINARY && x.binop != y.binop) return false;
-            if (x.kind == LLKV_TOK_LITERAL && (x.literal.tag != y.literal.tag || x.literal.scale != y.literal.scale || x.literal.lo != y.literal.lo || x.literal.hi != y.literal.hi ||
-                                               std::memcmp(&x.literal.f64, &y.literal.f64, 8) != 0)) return false;
-          }
-          return true;
-        };
-        if (p.distinct_proj && !same_tokens()) return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates over more than one argument in a GROUP BY");
-        if (!p.distinct_proj) {
-          p.distinct_tokens.assign(s.expr, s.expr + s.expr_len);
-          for (auto &tk : p.distinct_tokens) tk.literal.str = nullptr; // (numeric literals only: expr_planvalue took nothing else)
-          dp->out_dtypes = {df ? LLKV_DT_FLOAT64 : LLKV_DT_INT64};
-          dp->out_fields = {-1};
-          dp->out_nullable = {!dvalid.empty()};
-          dp->type_string = "ProjPlan<" + cols_string(*dp, &dp->bytes_per_row) + ",Outs<" + (dvalid.empty() ? dnode : "OutV<" + dnode + "," + dvalid + ">") + ">>";
-          p.distinct_proj = dp;
-          p.distinct_node = dnode;
-          p.distinct_numeric = 0;
-        }
-        const int count_lane = add_group("DistinctCount", {ADD_I64});
-        if (s.kind == LLKV_AGG_COUNT) { o.fin = AggFinal::CountValid; o.lane = count_lane; p.aggs.push_back(o); continue; }
-        if (!df && s.kind != LLKV_AGG_TOTAL) { // the checked_add chain over the distinct values cannot overflow whatever their order
-          auto mag = [](i128 v) -> u128 { return v < 0 ? (u128)(-v) : (u128)v; };
-          uint64_t rows = 0;
-          for (uint32_t k = 0; k < s.expr_len; ++k)
-            if (s.expr[k].kind == LLKV_TOK_COLUMN) { const ColumnInfo *ci = resolve(s.expr[k].field_id); if (ci) rows = std::max(rows, ci->rows); }
-          const u128 m = std::max(mag(dpv.lo), mag(dpv.hi));
-          if (!dpv.bounded || m * (u128)rows > (u128)INT64_MAX) return L.fail(LLKV_UNSUPPORTED, "possible i64 overflow in SUM(DISTINCT) over a computed argument: order-dependent check is not on the GPU path");
-        }
-        o.count_lane = count_lane;
-        o.typed_by_first_value = true; // (a group without a non-NULL value: the temp column is an Int64 column — SUM comes back as an Int64 NULL)
-        if (s.kind == LLKV_AGG_TOTAL) { o.fin = AggFinal::TotalF64; o.lane = add_group(df ? "DistinctSumF64" : "DistinctTotalI64", {ADD_F64}); }
-        else if (df) { o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumF64 : AggFinal::AvgF64; o.lane = add_group("DistinctSumF64", {ADD_F64}); }
-        else { o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumI64Fast : AggFinal::AvgI64Fast; o.lane = add_group("DistinctSumI64", {ADD_I64}); }
-        p.aggs.push_back(o);
-        continue;
-      }
-      if (p.distinct_proj) return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates over more than one argument in a GROUP BY");
-      const ColumnInfo *dci = resolve(s.expr[0].field_id);
-      if (!dci) return L.fail(LLKV_INVALID_ARGUMENT, "unknown column '" + std::to_string(s.expr[0].field_id) + "' in aggregate");
-      if (utf8_wide(*dci)) return L.fail(LLKV_UNSUPPORTED, L.wide_utf8_refusal(*dci, "a DISTINCT aggregate"));
-      // DistinctKey::from_array (llkv-aggregate/src/lib.rs:261-331): Int by value, Float by bits, Str by its string (here: its
-      // dictionary code — the staged dictionary holds every string once), Bool, Date by its day number; what SUM / TOTAL / AVG
-      // add for the last three is their numeric image in the Float64 accumulators (:400-449,889-924,1035-1066,1200-1232)
-      const bool keyed = dci->dtype == LLKV_DT_UTF8 || dci->dtype == LLKV_DT_BOOLEAN || dci->dtype == LLKV_DT_DATE32;
-      // … and Decimal by its raw value (the 64-bit image; Sum / Total / AvgDistinctDecimal128 :943-967,1089-1112,1260-1284)
-      const bool dec = dci->dtype == LLKV_DT_DECIMAL128 && !dci->wide128;
-      if (dci->dtype != LLKV_DT_INT64 && dci->dtype != LLKV_DT_FLOAT64 && !keyed && !dec) return L.fail(LLKV_UNSUPPORTED, std::string("DISTINCT aggregate over ") + dtype_name(dci->dtype));
-      if (p.distinct_field >= 0 && p.distinct_field != (int64_t)s.expr[0].field_id)
-        return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates over more than one column in a GROUP BY");
-      p.distinct_field = s.expr[0].field_id;
-      p.distinct_numeric = dci->dtype == LLKV_DT_UTF8 ? 1u : dci->dtype == LLKV_DT_BOOLEAN ? 2u : dci->dtype == LLKV_DT_DATE32 ? 3u : 0u;
-      if (dci->dtype == LLKV_DT_UTF8 && p.distinct_dict_num.empty()) {
-        p.distinct_dict_num.assign(256, 0.0);
-        for (size_t c = 0; c < dci->dictionary.size() && c < 256; ++c) p.distinct_dict_num[c] = parse_numeric_or_zero(dci->dictionary[c]);
-      }
-      const bool f = dci->dtype == LLKV_DT_FLOAT64 || keyed;
-      const int count_lane = add_group("DistinctCount", {ADD_I64});
-      if (s.kind == LLKV_AGG_COUNT) { o.fin = AggFinal::CountValid; o.lane = count_lane; p.aggs.push_back(o); continue; }
-      if (!f && (s.kind != LLKV_AGG_TOTAL || dec)) { // the checked_add chain over the distinct values cannot overflow whatever their order (decimals: the i64 lane holds their i128 sum)
-        auto mag = [](int64_t v) -> u128 { return v < 0 ? (u128)(-(i128)v) : (u128)v; };
-        if (!dci->has_stats) return L.fail(LLKV_UNSUPPORTED, "SUM(DISTINCT) over an integer column without statistics (order-dependent overflow check)");
-        const u128 m = mag(dci->min_i) > mag(dci->max_i) ? mag(dci->min_i) : mag(dci->max_i);
-        if (m * (u128)dci->rows > (u128)INT64_MAX) return L.fail(LLKV_UNSUPPORTED, "possible i64 overflow in SUM(DISTINCT): order-dependent check is not on the GPU path");
-      }
-      o.count_lane = count_lane;
-      if (dec) { // finalize :1583-1612,1656-1672,1762-1800: i128 sum with the column's (precision, scale); SUM / AVG are NULL without a value
-        o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumDec : s.kind == LLKV_AGG_TOTAL ? AggFinal::TotalDec : AggFinal::AvgDec;
-        o.precision = dci->precision; o.scale = dci->scale;
-        o.fast_sum = true;
-        o.null_without_values = s.kind != LLKV_AGG_TOTAL;
-        o.lane = add_group("DistinctSumI64", {ADD_I64});
-        p.aggs.push_back(o);
-        continue;
-      }
-      o.nan_default = dci->dtype == LLKV_DT_FLOAT64 && dci->f_no_nan; // (AggOut::nan_default: the distinct values' ∞ − ∞)
-      if (s.kind == LLKV_AGG_TOTAL) { o.fin = AggFinal::TotalF64; o.lane = add_group(f ? "DistinctSumF64" : "DistinctTotalI64", {ADD_F64}); }
-      else if (f) { o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumF64 : AggFinal::AvgF64; o.lane = add_group("DistinctSumF64", {ADD_F64}); }
-      else { o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumI64Fast : AggFinal::AvgI64Fast; o.lane = add_group("DistinctSumI64", {ADD_I64}); }
-      p.aggs.push_back(o);
-      continue;
-    }
-    if (s.distinct && s.kind == LLKV_AGG_COUNT_STAR) return L.fail(LLKV_UNSUPPORTED, "COUNT(DISTINCT *)");
-    if (s.kind == LLKV_AGG_COUNT_STAR) { p.aggs.push_back(o); continue; }
-    if (!s.expr || s.expr_len == 0) return L.fail(LLKV_INVALID_ARGUMENT, "aggregate requires an argument");
-    const bool simple = s.expr_len == 1 && s.expr[0].kind == LLKV_TOK_COLUMN;
-    std::string node;
-    bool is_f64 = false;
-    const ColumnInfo *simple_ci = nullptr;
-    if (simple) {
-      simple_ci = resolve(s.expr[0].field_id);
-      if (!simple_ci) return L.fail(LLKV_INVALID_ARGUMENT, "unknown column '" + std::to_string(s.expr[0].field_id) + "' in aggregate");
-    }
-    // rows where the argument is non-NULL (NULL propagates through arithmetic, x / 0 is NULL; accumulators
-    // skip NULLs, llkv-aggregate/src/lib.rs:769-786,801-830)
-    std::string valid;
-    if (simple) {
-      std::vector<std::string> vs;
-      if ((rc = L.valid_of_expr(s.expr, s.expr_len, &vs))) return rc;
-      valid = Lowering::all_of(vs);
-    } else {
-      rc = grouped ? L.expr_planvalue(s.expr, s.expr_len, &node, &is_f64) : L.expr_fast(s.expr, s.expr_len, &node, &is_f64);
-      if (rc) return rc;
-      if (!grouped && L.last_fast_32) return L.fail(LLKV_UNSUPPORTED, "aggregate over a 32-bit-only integer expression (the reference has no Int32 accumulator)");
-      // (what can make the value NULL is read off the expression the scan evaluates: the simplified one — a division of
-      // constants is gone from it)
-      std::vector<llkv_expr_token> folded;
-      if (!grouped && (rc = L.fold_constants(s.expr, s.expr_len, &folded))) return rc;
-      if ((rc = grouped ? L.valid_of_node(s.expr, s.expr_len, node, grouped, &valid) : L.valid_of_node(folded.data(), (uint32_t)folded.size(), node, grouped, &valid))) return rc;
-    }
-    const PlanValueInfo pvi = (grouped && !simple) ? L.last_planvalue : PlanValueInfo{};
-    if (pvi.is_decimal) {
-      // every aggregate kind — COUNT too — goes through the group's temp column (llkv-executor/src/lib.rs:5186-5199)
-      PendingDigits pd;
-      pd.agg = p.aggs.size();
-      pd.valid = valid.empty() ? "True" : valid;
-      pd.node = node;
-      const i128 alo = pvi.lo < 0 ? -pvi.lo : pvi.lo, ahi = pvi.hi < 0 ? -pvi.hi : pvi.hi;
-      pd.dlo = (pvi.lo <= 0 && pvi.hi >= 0) ? 1 : digits_of(std::min(alo, ahi));
-      pd.dhi = digits_of(std::max(alo, ahi));
-      pd.rows = 0;
-      pd.scale = pvi.scale;
-      for (uint32_t k = 0; k < s.expr_len; ++k)
-        if (s.expr[k].kind == LLKV_TOK_COLUMN) { const ColumnInfo *ci = resolve(s.expr[k].field_id); if (ci) pd.rows = std::max(pd.rows, ci->rows); }
-      pending_digits.push_back(pd);
-    }
-    if (s.kind == LLKV_AGG_COUNT || s.kind == LLKV_AGG_COUNT_NULLS) {
-      // NULL-free argument: COUNT(x) = rows, COUNT_NULLS(x) = 0
-      if (!simple && !grouped) {
-        // a computed argument is evaluated for its checked-arithmetic errors even though only its validity counts
-        o.fin = s.kind == LLKV_AGG_COUNT ? AggFinal::CountValid : AggFinal::CountNulls;
-        o.lane = add_group("CountIfE<" + (valid.empty() ? std::string("True") : valid) + "," + node + ">", {ADD_I64});
-      } else if (valid.empty()) o.fin = s.kind == LLKV_AGG_COUNT ? AggFinal::CountRows : AggFinal::CountNullsZero;
-      else {
-        o.fin = s.kind == LLKV_AGG_COUNT ? AggFinal::CountValid : AggFinal::CountNulls;
-        L.next_narrow = 1.0;
-        o.lane = add_group("CountIf<" + valid + ">", {ADD_I64});
-      }
-      p.aggs.push_back(o);
-      continue;
-    }
-    const char *fn = s.kind == LLKV_AGG_SUM ? "SUM" : s.kind == LLKV_AGG_TOTAL ? "TOTAL" : s.kind == LLKV_AGG_AVG ? "AVG" : s.kind == LLKV_AGG_MIN ? "MIN" : "MAX";
-    if (simple && !simple_ci->wide128) {
-      // validate_aggregate_type llkv-executor/src/lib.rs:5946-5988
-      const int32_t dt = simple_ci->dtype;
-      // Utf8 / Boolean / Date32 inputs get Float64 accumulators fed by array_value_to_numeric (llkv-aggregate/src/lib.rs:
-      // 400-449): strings parse or count as 0, booleans are 0 / 1; Date32 has no arm there — the first non-NULL row fails
-      if (dt == LLKV_DT_DATE32)
-        return L.fail(LLKV_UNSUPPORTED, std::string(fn) + " over Date32 (the reference fails at the first non-NULL row) is not on the GPU path");
-      if (dt != LLKV_DT_INT64 && dt != LLKV_DT_FLOAT64 && dt != LLKV_DT_DECIMAL128 && dt != LLKV_DT_UTF8 && dt != LLKV_DT_BOOLEAN)
-        return L.fail(LLKV_INVALID_ARGUMENT, std::string(fn) + " aggregate not supported for column type " + dtype_name(dt));
-      const ColumnInfo *ci;
-      int slot;
-      if (dt == LLKV_DT_UTF8 && utf8_wide(*resolve(s.expr[0].field_id))) return L.fail(LLKV_UNSUPPORTED, L.wide_utf8_refusal(*resolve(s.expr[0].field_id), fn));
-      if ((rc = L.slot_of(s.expr[0].field_id, &ci, &slot))) return rc;
-      if (dt == LLKV_DT_UTF8) {
-        if (!L.allow_dict_num) return L.fail(LLKV_UNSUPPORTED, std::string(fn) + " over a Utf8 column is not on this route");
-        node = "DictNum<" + std::to_string(slot) + ">";
-        bool have = false;
-        for (auto &d : p.dict_num) have |= d.first == slot;
-        if (!have) {
-          std::vector<double> image(256, 0.0);
-          for (size_t c = 0; c < ci->dictionary.size() && c < 256; ++c) image[c] = parse_numeric_or_zero(ci->dictionary[c]);
-          p.dict_num.emplace_back(slot, std::move(image));
-        }
-      } else if (dt == LLKV_DT_BOOLEAN) {
-        node = "ToF64<" + L.col_node(slot, dt) + ">";
-      } else {
-        node = L.col_node(slot, dt);
-      }
-      is_f64 = dt == LLKV_DT_FLOAT64 || dt == LLKV_DT_UTF8 || dt == LLKV_DT_BOOLEAN;
-    } else {
-      o.typed_by_first_value = grouped && !simple; // (a bare column keeps its own type: only a computed argument becomes a temp column)
-    }
-    // statistics that exclude i64 overflow of any prefix sum: rows · max|v| ≤ i64::MAX
-    bool fast_i64 = false;
-    if (!is_f64 && simple && simple_ci->has_stats) {
-      auto mag = [](int64_t v) -> u128 { return v < 0 ? (u128)(-(i128)v) : (u128)v; };
-      u128 m = mag(simple_ci->min_i) > mag(simple_ci->max_i) ? mag(simple_ci->min_i) : mag(simple_ci->max_i);
-      fast_i64 = m * (u128)simple_ci->rows <= (u128)INT64_MAX;
-    }
-    // shared-image plans: SumF64<node> → SumF64X<node, C1, C2> (exact, order-free); needs a bound on |argument|
-    bool no_bound = false;
-    auto sum_f64 = [&](const std::string &arg) -> std::pair<std::string, std::vector<uint8_t>> {
-      if (!L.exact_f64) return {"SumF64<" + arg + ">", {ADD_F64}};
-      double absmax = 0.0, nzmin = 0.0, c[4];
-      int levels = 0;
-      const bool bounded = L.expr_bounds(s.expr, s.expr_len, &absmax, &nzmin);
-      const uint64_t n_rows = simple_ci ? simple_ci->rows : L.table_rows;
-      int e = 0;
-      std::string scale_lit;
-      if (!L.image_plan && bounded && L.bounds_all_finite && L.exact_fixed_point(absmax, nzmin, n_rows, &e) && L.lit_f(std::ldexp(1.0, -e), &scale_lit) == 0) {
-        o.fixed_point = true;
-        o.fixed_exp = e;
-        return {"SumF64Q2<" + arg + "," + scale_lit + ">", {ADD_I64, ADD_I64}};
-      }
-      if (L.image_plan && bounded && L.bounds_all_finite && !std::getenv("LLKV_HIP_IMAGE_NO_FIXED") && L.fixed_point_grid(absmax, nzmin, n_rows, &e) &&
-          L.lit_f(std::ldexp(1.0, -e), &scale_lit) == 0) { // one integer lane in the image, two in the exchange image
-        o.fixed_point = true;
-        o.fixed_exp = e;
-        p.image_min_grid = 256;
-        L.next_expand = {{0, 1}, {0, 2}};
-        return {"SumF64Q<" + arg + "," + scale_lit + ">", {ADD_I64, ADD_I64}};
-      }
-      if (bounded) levels = L.exact_sum_constants(absmax, nzmin, n_rows, c);
-      std::string node_x = "SumF64X<" + arg;
-      std::vector<uint8_t> lane_ops;
-      for (int j = 0; j < levels; ++j) {
-        std::string lit;
-        if (L.lit_f(c[j], &lit)) { levels = 0; break; }
-        node_x += "," + lit;
-        lane_ops.push_back(ADD_F64);
-      }
-      if (levels == 0) {
-        no_bound = true;
-        return {"SumF64<" + arg + ">", {ADD_F64}};
-      }
-      o.exact_levels = levels;
-      return {node_x + ">", lane_ops};
-    };
-    // NULL argument rows contribute each lane's identity; one more lane counts the non-NULL rows
-    double narrow_bound = -1.0; // (SumI64Fast over a plain integer column: max |v|)
-    if (!is_f64 && simple && fast_i64 && simple_ci->dtype == LLKV_DT_INT64)
-      narrow_bound = std::max(std::fabs((double)simple_ci->min_i), std::fabs((double)simple_ci->max_i));
-    auto add_agg = [&](const std::string &inner, std::vector<uint8_t> lane_ops) {
-      if (inner.rfind("SumI64Fast<", 0) == 0 && narrow_bound >= 0.0) L.next_narrow = std::max(1.0, narrow_bound); // (with IfValid: + a count lane)
-      if (valid.empty()) { o.lane = add_group(inner, lane_ops); return; }
-      const int n_inner = (int)lane_ops.size();
-      lane_ops.push_back(ADD_I64);
-      if (!L.next_expand.empty()) { // the count of non-NULL rows is one more kernel lane behind the inner ones
-        uint8_t kernel_lanes = 0;
-        for (auto &x : L.next_expand) kernel_lanes = std::max<uint8_t>(kernel_lanes, (uint8_t)(x.first + 1));
-        L.next_expand.emplace_back(kernel_lanes, (uint8_t)0);
-      }
-      o.lane = add_group("IfValid<" + valid + "," + inner + ">", lane_ops);
-      o.count_lane = o.lane + n_inner;
-    };
-    if (simple && simple_ci->wide128) {
-      // Decimal128 values beyond 64 bits (llkv-aggregate/src/lib.rs:925-943: `sum.checked_add(v)` in i128, row by row):
-      // four ADD_I64 lanes over the 32-bit limbs (the top one signed) — exact for < 2^31 rows, order-free.  The
-      // reference's overflow check is order dependent (a prefix may leave i128 although the total fits): the plan is
-      // taken only when rows · max|v| ≤ i128::MAX excludes that.  AVG: half away from zero (:1720-1742).
-      if (s.kind == LLKV_AGG_MIN || s.kind == LLKV_AGG_MAX) {
-        // MinDecimal128 / MaxDecimal128 (llkv-aggregate/src/lib.rs:1332-1352,1400-1420: i128 min / max over the non-NULL rows).  A
-        // 128-bit compare has no order-free lanes, but a column whose values span less than 2^64 — known from staging — needs
-        // none: v − min(column) fits 64 bits and is the low halves' wrapping difference, so MAX is one MAX_U64 lane over
-        // lo − min_lo and MIN one over max_lo − lo; the host adds the column's min / max back in i128.
-        const i128 vmin = (i128)(((u128)simple_ci->wide_min_hi << 64) | simple_ci->wide_min_lo), vmax = (i128)(((u128)simple_ci->wide_max_hi << 64) | simple_ci->wide_max_lo);
-        if (vmax < vmin || (u128)(vmax - vmin) >> 64)
-          return L.fail(LLKV_UNSUPPORTED, std::string(fn) + " over Decimal128 values beyond 64 bits that span 2^64 or more (a 128-bit compare has no order-free lanes) is not on the GPU path");
-        int lo, hi;
-        if ((rc = L.wide_slots_of(s.expr[0].field_id, &lo, &hi, /*want_hi=*/false))) return rc;
-        const bool is_min = s.kind == LLKV_AGG_MIN;
-        std::string base;
-        if ((rc = L.lit_i((int64_t)(is_min ? simple_ci->wide_max_lo : simple_ci->wide_min_lo), &base, "LitU"))) return rc;
-        o.precision = simple_ci->precision; o.scale = simple_ci->scale;
-        o.wide = true;
-        o.wide_delta = is_min ? 2 : 1;
-        o.wide_base_hi = is_min ? simple_ci->wide_max_hi : simple_ci->wide_min_hi;
-        o.wide_base_lo = is_min ? simple_ci->wide_max_lo : simple_ci->wide_min_lo;
-        o.fin = is_min ? AggFinal::MinDec : AggFinal::MaxDec;
-        add_agg("MaxWideDelta<" + std::to_string(lo) + "," + base + "," + (is_min ? "1" : "0") + ">", {MAX_U64});
-        p.aggs.push_back(o);
-        continue;
-      }
-      if (s.kind != LLKV_AGG_SUM && s.kind != LLKV_AGG_TOTAL && s.kind != LLKV_AGG_AVG) return L.fail(LLKV_UNSUPPORTED, "aggregate kind " + std::to_string(s.kind));
-      const u128 absmax = ((u128)simple_ci->wide_absmax_hi << 64) | simple_ci->wide_absmax_lo;
-      const u128 i128_max = ~(u128)0 >> 1;
-      if (simple_ci->rows >= (1ull << 31) || (absmax != 0 && (u128)simple_ci->rows > i128_max / absmax))
-        return L.fail(LLKV_UNSUPPORTED, "possible Decimal128 sum overflow (rows · max|v| exceeds i128): the reference's check is order dependent");
-      int lo, hi;
-      if ((rc = L.wide_slots_of(s.expr[0].field_id, &lo, &hi))) return rc;
-      o.precision = simple_ci->precision; o.scale = simple_ci->scale;
-      o.wide = true;
-      o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumDec : s.kind == LLKV_AGG_TOTAL ? AggFinal::TotalDec : AggFinal::AvgDec;
-      add_agg("SumDecWide<" + std::to_string(lo) + "," + std::to_string(hi) + ">", {ADD_I64, ADD_I64, ADD_I64, ADD_I64});
-      p.aggs.push_back(o);
-      continue;
-    }
-    if (simple && simple_ci->dtype == LLKV_DT_DECIMAL128) {
-      // Decimal128 accumulators (llkv-aggregate/src/lib.rs:925-967,1071-1088,1236-1259,1332-1352,1400-1420) over the
-      // 64-bit image: the same exact lanes as Int64, finalized in i128 with the column's (precision, scale)
-      o.precision = simple_ci->precision; o.scale = simple_ci->scale;
-      o.fast_sum = fast_i64;
-      switch (s.kind) {
-      case LLKV_AGG_SUM: case LLKV_AGG_TOTAL: case LLKV_AGG_AVG:
-        o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumDec : s.kind == LLKV_AGG_TOTAL ? AggFinal::TotalDec : AggFinal::AvgDec;
-        if (fast_i64) add_agg("SumI64Fast<" + node + ">", {ADD_I64});
-        else add_agg("SumI64<" + node + ">", {ADD_I64, ADD_I64, MAX_U64});
-        break;
-      case LLKV_AGG_MIN: o.fin = AggFinal::MinDec; add_agg("MinI64<" + node + ">", {MIN_I64}); break;
-      case LLKV_AGG_MAX: o.fin = AggFinal::MaxDec; add_agg("MaxI64<" + node + ">", {MAX_I64}); break;
-      default: return L.fail(LLKV_UNSUPPORTED, "aggregate kind " + std::to_string(s.kind));
-      }
-      p.aggs.push_back(o);
-      continue;
-    }
-    if (pvi.is_decimal) {
-      // Decimal128 accumulators over the computed argument's 64-bit image; precision = digits of the group's first non-NULL
-      // value (filled in at finalize from the FirstDigits lane), scale = the expression's
-      o.precision = 0; o.scale = pvi.scale;
-      const u128 m = (u128)std::max(pvi.lo < 0 ? -pvi.lo : pvi.lo, pvi.hi < 0 ? -pvi.hi : pvi.hi);
-      const uint64_t rows = pending_digits.back().rows;
-      o.fast_sum = rows != 0 && m * (u128)rows <= (u128)INT64_MAX;
-      switch (s.kind) {
-      case LLKV_AGG_SUM: case LLKV_AGG_TOTAL: case LLKV_AGG_AVG:
-        o.fin = s.kind == LLKV_AGG_SUM ? AggFinal::SumDec : s.kind == LLKV_AGG_TOTAL ? AggFinal::TotalDec : AggFinal::AvgDec;
-        if (o.fast_sum) add_agg("SumI64Fast<" + node + ">", {ADD_I64});
-        else add_agg("SumI64<" + node + ">", {ADD_I64, ADD_I64, MAX_U64});
-        break;
-      case LLKV_AGG_MIN: o.fin = AggFinal::MinDec; add_agg("MinI64<" + node + ">", {MIN_I64}); break;
-      case LLKV_AGG_MAX: o.fin = AggFinal::MaxDec; add_agg("MaxI64<" + node + ">", {MAX_I64}); break;
-      default: return L.fail(LLKV_UNSUPPORTED, "aggregate kind " + std::to_string(s.kind));
-      }
-      p.aggs.push_back(o);
-      continue;
-    }
-    // MinFloat64 / MaxFloat64 (llkv-aggregate/src/lib.rs:1309-1331,1377-1399) fold sequentially by partial_cmp: a leading NaN sticks,
-    // ±0 ties keep the earlier row — which costs two row-order lanes beside the order key.  A bare Float64 column whose staging
-    // statistics say "no NaN / ±∞, no −0.0" has neither case: one order-key lane (a third of the DS instructions)
-    const bool plain_f64 = simple && simple_ci->dtype == LLKV_DT_FLOAT64 && simple_ci->has_fstats && simple_ci->f_all_finite && simple_ci->f_no_neg_zero &&
-                           !std::getenv("LLKV_HIP_MINMAX_ROW_ORDER");
-    // a NaN sum of a bare Float64 column without NaN cells is the reference's default NaN (AggOut::nan_default)
-    o.nan_default = simple && simple_ci->dtype == LLKV_DT_FLOAT64 && simple_ci->f_no_nan && (s.kind == LLKV_AGG_SUM || s.kind == LLKV_AGG_TOTAL || s.kind == LLKV_AGG_AVG);
-    switch (s.kind) {
-    case LLKV_AGG_SUM:
-      if (is_f64) { o.fin = AggFinal::SumF64; auto g = sum_f64(node); add_agg(g.first, g.second); }
-      else if (fast_i64) { o.fin = AggFinal::SumI64Fast; add_agg("SumI64Fast<" + node + ">", {ADD_I64}); }
-      else { o.fin = AggFinal::SumI64; add_agg("SumI64<" + node + ">", {ADD_I64, ADD_I64, MAX_U64}); }
-      break;
-    case LLKV_AGG_TOTAL: {
-      o.fin = AggFinal::TotalF64;
-      auto g = sum_f64(is_f64 ? node : "ToF64<" + node + ">");
-      add_agg(g.first, g.second);
-      break;
-    }
-    case LLKV_AGG_AVG:
-      if (is_f64) { o.fin = AggFinal::AvgF64; auto g = sum_f64(node); add_agg(g.first, g.second); }
-      else if (fast_i64) { o.fin = AggFinal::AvgI64Fast; add_agg("SumI64Fast<" + node + ">", {ADD_I64}); }
-      else { o.fin = AggFinal::AvgI64; add_agg("SumI64<" + node + ">", {ADD_I64, ADD_I64, MAX_U64}); }
-      break;
-    case LLKV_AGG_MIN:
-      if (is_f64 && plain_f64) { o.fin = AggFinal::MinF64; o.plain_minmax = true; add_agg("MinF64P<" + node + ">", {MIN_I64}); }
-      else if (is_f64) { o.fin = AggFinal::MinF64; add_agg("MinF64<" + node + ">", {MIN_I64, MIN_I64, MIN_I64}); }
-      else { o.fin = AggFinal::MinI64; add_agg("MinI64<" + node + ">", {MIN_I64}); }
-      break;
-    case LLKV_AGG_MAX:
-      if (is_f64 && plain_f64) { o.fin = AggFinal::MaxF64; o.plain_minmax = true; add_agg("MaxF64P<" + node + ">", {MAX_I64}); }
-      else if (is_f64) { o.fin = AggFinal::MaxF64; add_agg("MaxF64<" + node + ">", {MAX_I64, MIN_I64, MIN_I64}); }
-      else { o.fin = AggFinal::MaxI64; add_agg("MaxI64<" + node + ">", {MAX_I64}); }
-      break;
-    default: return L.fail(LLKV_UNSUPPORTED, "aggregate kind " + std::to_string(s.kind));
-    }
-    if (no_bound) return L.fail(LLKV_UNSUPPORTED, std::string("the column statistics do not bound an f64 sum argument from above and (where non-zero) from below: no exact, order-free sum for ") + (L.image_plan ? "the shared-image GROUP BY" : "the exact-sum option"));
-    p.aggs.push_back(o);
-  }
-
-  // FirstDigits lanes: per validity, the distinct argument nodes in packs of up to four 6-bit digit fields under the row id
-  // (the key must stay below 2^63: four fields leave 39 bits for the row id, one field 57)
-  std::vector<bool> placed(pending_digits.size(), false);
-  for (size_t i = 0; i < pending_digits.size(); ++i) {
-    if (placed[i]) continue;
-    std::vector<size_t> nodes; // indices of the first pending entry of every distinct node in this pack
-    uint64_t rows = 0;
-    for (size_t j = i; j < pending_digits.size(); ++j) rows = std::max(rows, pending_digits[j].rows);
-    const size_t per_pack = rows < (1ull << 38) ? 4 : 1;
-    for (size_t j = i; j < pending_digits.size(); ++j) {
-      if (placed[j] || pending_digits[j].valid != pending_digits[i].valid) continue;
-      bool known = false;
-      for (size_t k : nodes) known |= pending_digits[k].node == pending_digits[j].node;
-      if (!known) { if (nodes.size() == per_pack) continue; nodes.push_back(j); }
-      placed[j] = true;
-    }
-    std::string g = "FirstDigits<" + pending_digits[i].valid;
-    for (size_t k : nodes) g += ",DecDigits<" + pending_digits[k].node + "," + std::to_string(pending_digits[k].dlo) + "," + std::to_string(pending_digits[k].dhi) + ">";
-    g += ">";
-    const int lane = add_group(g, {MIN_I64});
-    for (size_t j = i; j < pending_digits.size(); ++j) {
-      if (!placed[j] || pending_digits[j].valid != pending_digits[i].valid || p.aggs[pending_digits[j].agg].digits_lane >= 0) continue;
-      for (size_t at = 0; at < nodes.size(); ++at)
-        if (pending_digits[nodes[at]].node == pending_digits[j].node) {
-          p.aggs[pending_digits[j].agg].digits_lane = lane;
-          p.aggs[pending_digits[j].agg].digits_shift = 6 * (int)(nodes.size() - 1 - at);
-          p.aggs[pending_digits[j].agg].scale = pending_digits[j].scale;
-        }
-    }
-  }
-  return LLKV_OK;
-}
 
 static std::atomic<bool> g_exact_f64_sums{false};
 void plan_set_exact_f64_sums(bool on) { g_exact_f64_sums.store(on); }
@@ -1991,7 +2027,8 @@ int lower_plan(const ColumnResolver &resolve, const llkv_filter *filters, uint32
   // keys
   std::string keys = "Keys<";
   if (grouped) {
-    if (n_keys > (uint32_t)kMaxKeysHost) return L.fail(LLKV_UNSUPPORTED, "more than 4 GROUP BY keys");
+    static_assert(kMaxKeys == 4, "the refusal below names the number");
+    if (n_keys > (uint32_t)kMaxKeys) return L.fail(LLKV_UNSUPPORTED, "more than 4 GROUP BY keys");
     uint64_t ng = 1;
     std::string nodes;
     for (uint32_t k = 0; k < n_keys; ++k) {
@@ -2052,21 +2089,18 @@ int lower_plan(const ColumnResolver &resolve, const llkv_filter *filters, uint32
 
   // aggregates → deduplicated lane groups
   const int base = (grouped && track_first) ? 2 : 1;
-  std::vector<std::string> groups; // lane-group node strings
-  std::vector<std::vector<uint8_t>> group_ops;
-  int next_lane = 0;
   const size_t early_slots = p.slot_fields.size(); // what the predicate and the keys read; the slots behind feed aggregate arguments only
-  if ((rc = lower_aggregates(L, resolve, aggs, n_aggs, grouped, groups, group_ops, next_lane))) return rc;
-  enum { ADD_F64 = 0, ADD_I64 = 1, MIN_I64 = 2, MAX_I64 = 3, MAX_U64 = 4 };
+  AggLowering A(L, grouped);
+  if ((rc = A.run(aggs, n_aggs))) return rc;
 
-  p.k = base + next_lane;
+  p.k = base + A.next_lane;
   p.lanes = (int)p.ng * p.k + 1;
   // the kernel's lanes per group (shared-image plans may keep a lane group in fewer lanes than the exchange image has)
   p.image_src.clear();
   p.image_xf.clear();
   for (int j = 0; j < base; ++j) { p.image_src.push_back((uint8_t)j); p.image_xf.push_back(0); }
   int kernel_lane = base;
-  for (auto &ge : L.group_expand) {
+  for (auto &ge : A.group_expand) {
     int used = 0;
     for (auto &x : ge) {
       p.image_src.push_back((uint8_t)(kernel_lane + x.first));
@@ -2078,11 +2112,11 @@ int lower_plan(const ColumnResolver &resolve, const llkv_filter *filters, uint32
   p.k_image = kernel_lane;
   p.lane_ops.clear();
   for (uint32_t g = 0; g < p.ng; ++g) {
-    p.lane_ops.push_back(ADD_I64);
-    if (grouped && track_first) p.lane_ops.push_back(MIN_I64);
-    for (auto &go : group_ops) for (uint8_t op : go) p.lane_ops.push_back(op);
+    p.lane_ops.push_back(OP_ADD_I64);
+    if (grouped && track_first) p.lane_ops.push_back(OP_MIN_I64);
+    for (auto &go : A.group_ops) for (uint8_t op : go) p.lane_ops.push_back(op);
   }
-  p.lane_ops.push_back(MAX_U64);
+  p.lane_ops.push_back(OP_MAX_U64);
   // accumulator placement: grouped plans keep their state in per-thread LDS slots (DS atomics
   // indexed by the row's group id); ungrouped plans keep it in registers
   p.acc_image = image;
@@ -2098,8 +2132,8 @@ int lower_plan(const ColumnResolver &resolve, const llkv_filter *filters, uint32
     uint64_t rows = 0;
     for (uint32_t k = 0; k < n_keys; ++k) if (const ColumnInfo *ci = resolve(key_fields[k])) rows = std::max(rows, ci->rows);
     double bound = 1.0;
-    narrow = rows > 0 && rows < (1ull << 32) && L.group_narrow.size() == groups.size();
-    for (double b : L.group_narrow) { narrow = narrow && b >= 0.0; bound = std::max(bound, b); }
+    narrow = rows > 0 && rows < (1ull << 32);
+    for (double b : A.group_narrow) { narrow = narrow && b >= 0.0; bound = std::max(bound, b); }
     narrow = narrow && bound * ((double)(rows / 128 + 16384)) < 2147483648.0;
     if (narrow) p.image_min_grid = 256;
   }
@@ -2117,35 +2151,15 @@ int lower_plan(const ColumnResolver &resolve, const llkv_filter *filters, uint32
     if (u == 1 || u == 2 || u == 4 || u == 8) p.unroll = u;
   }
 
-  std::string cols = "Cols<";
-  p.bytes_per_row = 0;
-  for (size_t i = 0; i < p.slot_dtypes.size(); ++i) {
-    cols += (i ? "," : "") + std::string(dtype_tag(p.slot_dtypes[i]));
-    p.bytes_per_row += dtype_width(p.slot_dtypes[i]);
-  }
-  cols += ">";
-  std::string ag = "Aggs<";
-  for (size_t i = 0; i < groups.size(); ++i) ag += (i ? "," : "") + groups[i];
-  ag += ">";
+  const std::string cols = cols_string(p, &p.bytes_per_row);
   // register-state plans with a predicate: the argument-only columns are read for the rows that pass (fused_scan.hip.h:
   // Plan::EARLY, late materialisation — Q6 reads 20 B of every row and the price of the 2 % that pass)
   const bool late = !p.acc_part && !p.acc_image && !p.acc_lds && pred != "True" && pred != "False" && early_slots > 0 && early_slots < p.slot_fields.size() &&
                     !std::getenv("LLKV_HIP_SCAN_NO_LATE");
   p.late_columns = late;
-  p.type_string = "Plan<" + cols + "," + pred + "," + keys + "," + ag + "," + std::to_string(p.unroll) + "," + (p.acc_part ? "3" : p.acc_image ? "2" : p.acc_lds ? "1" : "0") +
+  p.type_string = "Plan<" + cols + "," + pred + "," + keys + "," + aggs_string(A.groups) + "," + std::to_string(p.unroll) + "," + (p.acc_part ? "3" : p.acc_image ? "2" : p.acc_lds ? "1" : "0") +
                   (late ? ",1," + std::to_string(early_slots) : p.image_cell32 ? "," + std::to_string(p.image_passes) + ",-1,1" : p.image_passes > 1 ? "," + std::to_string(p.image_passes) : std::string()) + ">";
   return LLKV_OK;
-}
-
-static std::string cols_string(const LoweredPlan &p, uint64_t *bytes) {
-  std::string cols = "Cols<";
-  uint64_t b = 0;
-  for (size_t i = 0; i < p.slot_dtypes.size(); ++i) {
-    cols += (i ? "," : "") + std::string(dtype_tag(p.slot_dtypes[i]));
-    b += dtype_width(p.slot_dtypes[i]);
-  }
-  if (bytes) *bytes = b;
-  return cols + ">";
 }
 
 int lower_reduce(const ColumnResolver &resolve, const llkv_aggregate_spec *aggs, uint32_t n_aggs, LoweredPlan *out, std::string *err) {
@@ -2158,18 +2172,14 @@ int lower_reduce(const ColumnResolver &resolve, const llkv_aggregate_spec *aggs,
   L.exact_f64 = L.strict_exact;
   p.grouped = true;
   p.track_first = true;
-  std::vector<std::string> groups;
-  std::vector<std::vector<uint8_t>> group_ops;
-  int next_lane = 0, rc;
-  if ((rc = lower_aggregates(L, resolve, aggs, n_aggs, true, groups, group_ops, next_lane))) return rc;
+  AggLowering A(L, true);
+  if (int rc = A.run(aggs, n_aggs)) return rc;
   p.ng = 1;
-  p.k = 2 + next_lane;
+  p.k = 2 + A.next_lane;
   p.lanes = p.k;
-  p.lane_ops = {1 /*ADD_I64 rows*/, 2 /*MIN_I64 first row*/};
-  for (auto &go : group_ops) for (uint8_t op : go) p.lane_ops.push_back(op);
-  std::string ag = "Aggs<";
-  for (size_t i = 0; i < groups.size(); ++i) ag += (i ? "," : "") + groups[i];
-  p.type_string = "ReducePlan<" + cols_string(p, &p.bytes_per_row) + "," + ag + ">>";
+  p.lane_ops = {OP_ADD_I64 /*rows*/, OP_MIN_I64 /*first row*/};
+  for (auto &go : A.group_ops) for (uint8_t op : go) p.lane_ops.push_back(op);
+  p.type_string = "ReducePlan<" + cols_string(p, &p.bytes_per_row) + "," + aggs_string(A.groups) + ">";
   return LLKV_OK;
 }
 
@@ -2187,12 +2197,8 @@ int lower_selection(const ColumnResolver &resolve, const llkv_filter *filters, u
   if (n_drop_null_fields) {
     std::vector<std::string> vs;
     bool some_never_null = false;
-    for (uint32_t i = 0; i < n_drop_null_fields; ++i) {
-      std::string v;
-      if ((rc = L.valid_of_field(drop_null_fields[i], &v))) return rc;
-      if (v.empty()) some_never_null = true;
-      else if (std::find(vs.begin(), vs.end(), v) == vs.end()) vs.push_back(v);
-    }
+    for (uint32_t i = 0; i < n_drop_null_fields; ++i)
+      if ((rc = L.add_valid_of_field(drop_null_fields[i], &vs, &some_never_null))) return rc;
     if (!some_never_null && pred != "False") {
       const std::string any = vs.size() == 1 ? vs[0] : Lowering::nary("Or", vs);
       pred = pred == "True" ? any : "And<" + pred + "," + any + ">";
@@ -2208,18 +2214,11 @@ int lower_selection_in_set(const ColumnResolver &resolve, const llkv_filter *fil
                            LoweredPlan *out, std::string *err) {
   *out = LoweredPlan{};
   Lowering L{resolve, *out, err, false};
-  std::string pred, key;
+  std::string pred, in_set;
   int rc = L.predicate(filters, n_filters, nullptr, 0, &pred);
   if (rc) return rc;
-  const ColumnInfo *ci;
-  int slot;
-  if ((rc = L.slot_of(key_field, &ci, &slot))) return rc;
-  if (ci->nullable) return L.fail(LLKV_UNSUPPORTED, "NULL join keys in the join-aggregate pipeline");
-  if (ci->dtype == LLKV_DT_INT64 || ci->dtype == LLKV_DT_UINT64) key = L.col_node(slot, LLKV_DT_INT64);
-  else if (ci->dtype == LLKV_DT_INT32 || ci->dtype == LLKV_DT_DATE32 || ci->dtype == LLKV_DT_UINT32) key = "ToI64<" + L.col_node(slot, ci->dtype) + ">";
-  else return L.fail(LLKV_UNSUPPORTED, std::string("join key of type ") + dtype_name(ci->dtype));
+  if ((rc = L.in_key_set(key_field, &in_set))) return rc;
   out->always_false = pred == "False";
-  const std::string in_set = "InKeySet<" + key + ">";
   if (!out->always_false) pred = pred == "True" ? in_set : "AndThen<" + pred + "," + in_set + ">";
   out->type_string = "SelPlan<" + cols_string(*out, &out->bytes_per_row) + "," + pred + ">";
   return LLKV_OK;
@@ -2235,15 +2234,8 @@ int lower_emit(const ColumnResolver &resolve, const llkv_filter *filters, uint32
   if (rc) return rc;
   out->always_false = pred == "False";
   if (in_set_field && !out->always_false) { // … AND the key of this field is in the launch's key set (a semi join as a conjunct)
-    const ColumnInfo *ci;
-    int slot;
-    std::string key;
-    if ((rc = L.slot_of(*in_set_field, &ci, &slot))) return rc;
-    if (ci->nullable) return L.fail(LLKV_UNSUPPORTED, "NULL join keys in the join-aggregate pipeline");
-    if (ci->dtype == LLKV_DT_INT64 || ci->dtype == LLKV_DT_UINT64) key = L.col_node(slot, LLKV_DT_INT64);
-    else if (ci->dtype == LLKV_DT_INT32 || ci->dtype == LLKV_DT_DATE32 || ci->dtype == LLKV_DT_UINT32) key = "ToI64<" + L.col_node(slot, ci->dtype) + ">";
-    else return L.fail(LLKV_UNSUPPORTED, std::string("join key of type ") + dtype_name(ci->dtype));
-    const std::string in_set = "InKeySet<" + key + ">";
+    std::string in_set;
+    if ((rc = L.in_key_set(*in_set_field, &in_set))) return rc;
     pred = pred == "True" ? in_set : "AndThen<" + pred + "," + in_set + ">";
   }
   bool is_f64 = false;
@@ -2262,12 +2254,13 @@ int lower_emit(const ColumnResolver &resolve, const llkv_filter *filters, uint32
     is_f64 = ci->dtype == LLKV_DT_FLOAT64;
     if (key_dtype) *key_dtype = ci->dtype;
   } else {
-    L.exact_nan = true; // the emitted values are told apart by their bits (DISTINCT)
-    rc = L.expr_fast(expr, expr_len, &val, &is_f64);
-    L.exact_nan = false;
+    Lowered x;
+    { Lowering::ExactNan exact(L); rc = L.expr_fast(expr, expr_len, &x); } // the emitted values are told apart by their bits (DISTINCT)
     if (rc) return rc;
-    if (L.last_fast_32) return L.fail(LLKV_UNSUPPORTED, "aggregate over a 32-bit-only integer expression (the reference has no Int32 accumulator)");
-    if (is_f64 && !allow_f64) return L.fail(LLKV_INTERNAL, "exact sum check over a float expression");
+    if (x.fit32) return L.fail(LLKV_UNSUPPORTED, "aggregate over a 32-bit-only integer expression (the reference has no Int32 accumulator)");
+    if (x.is_f64 && !allow_f64) return L.fail(LLKV_INTERNAL, "exact sum check over a float expression");
+    val = x.node;
+    is_f64 = x.is_f64;
     if (key_dtype) *key_dtype = is_f64 ? LLKV_DT_FLOAT64 : LLKV_DT_INT64;
   }
   if (is_f64_out) *is_f64_out = is_f64;
@@ -2284,29 +2277,26 @@ int lower_probe(const ColumnResolver &resolve, const llkv_filter *filters, uint3
                 const llkv_expr_token *expr, uint32_t expr_len, LoweredPlan *out, std::string *err, bool emit_keybit) {
   *out = LoweredPlan{};
   Lowering L{resolve, *out, err, true};
-  std::string pred, key, val;
+  std::string pred, key;
   int rc = L.predicate(filters, n_filters, nullptr, 0, &pred);
   if (rc) return rc;
   out->always_false = pred == "False";
   const ColumnInfo *ci;
   int slot;
-  if ((rc = L.slot_of(key_field, &ci, &slot))) return rc;
-  if (ci->nullable) return L.fail(LLKV_UNSUPPORTED, "NULL join keys in the join-aggregate pipeline");
+  if ((rc = L.key_column(key_field, &ci, &slot))) return rc;
   for (uint32_t i = 0; i < expr_len; ++i)
     if (expr && expr[i].kind == LLKV_TOK_COLUMN && resolve(expr[i].field_id) && resolve(expr[i].field_id)->nullable)
       return L.fail(LLKV_UNSUPPORTED, "NULL aggregate arguments in the join-aggregate pipeline");
-  if (ci->dtype == LLKV_DT_INT64 || ci->dtype == LLKV_DT_UINT64) key = L.col_node(slot, LLKV_DT_INT64);
-  else if (ci->dtype == LLKV_DT_INT32 || ci->dtype == LLKV_DT_DATE32 || ci->dtype == LLKV_DT_UINT32) key = "ToI64<" + L.col_node(slot, ci->dtype) + ">";
-  else return L.fail(LLKV_UNSUPPORTED, std::string("join key of type ") + dtype_name(ci->dtype));
-  bool is_f64 = false;
+  if ((rc = L.key_node(*ci, slot, &key))) return rc;
   if (!expr || expr_len == 0) return L.fail(LLKV_INVALID_ARGUMENT, "aggregate requires an argument");
   const size_t early = out->slot_fields.size(); // the slots so far feed the predicate and the key; what the value adds is read late
-  if ((rc = L.expr_planvalue(expr, expr_len, &val, &is_f64))) return rc;
-  if (!is_f64) return L.fail(LLKV_UNSUPPORTED, "integer SUM in the join-aggregate pipeline");
+  Lowered val;
+  if ((rc = L.expr_planvalue(expr, expr_len, &val))) return rc;
+  if (!val.is_f64) return L.fail(LLKV_UNSUPPORTED, "integer SUM in the join-aggregate pipeline");
   const bool late = early < out->slot_fields.size() && !std::getenv("LLKV_HIP_JOIN_NO_LATE");
   // (the direct-table probe of a plan with KEYBIT = 1 emits the key's bit position instead of its rank: join_agg.cpp)
   const std::string tail = emit_keybit ? "," + std::to_string(late ? early : out->slot_fields.size()) + ",1" : late ? "," + std::to_string(early) : "";
-  out->type_string = "ProbePlan<" + cols_string(*out, &out->bytes_per_row) + "," + pred + "," + key + "," + val + tail + ">";
+  out->type_string = "ProbePlan<" + cols_string(*out, &out->bytes_per_row) + "," + pred + "," + key + "," + val.node + tail + ">";
   return LLKV_OK;
 }
 
@@ -2318,69 +2308,49 @@ int lower_projection(const ColumnResolver &resolve, const llkv_projection *proje
   if (n_projections > 8) return L.fail(LLKV_UNSUPPORTED, "more than 8 projections");
   std::string outs = "Outs<";
   int rc;
+  // A column passed through as it was staged; a Decimal128 column with values beyond 64 bits: low and high halves → 16 bytes.
+  // (Only ScanProjection::Column refuses a column without a device image; the same column written as an expression is not checked.)
+  auto passthrough = [&](uint32_t field, bool computed, std::string *node) -> int {
+    const ColumnInfo *ci = resolve(field);
+    if (ci && ci->wide128) {
+      int lo, hi;
+      if (int r = L.wide_slots_of(field, &lo, &hi)) return r;
+      *node = "Join128<" + std::to_string(lo) + "," + std::to_string(hi) + ">";
+    } else {
+      int slot;
+      if (int r = L.slot_of(field, &ci, &slot, true)) return r;
+      if (!computed && dtype_width(ci->dtype) == 0) return L.fail(LLKV_UNSUPPORTED, std::string("projection of ") + dtype_name(ci->dtype));
+      *node = L.col_node(slot, storage_dtype(*ci));
+      if (ci->dtype == LLKV_DT_DECIMAL128) *node = "Widen128<" + *node + ">"; // back to arrow's 16-byte raw values
+    }
+    out->out_dtypes.push_back(ci->dtype);
+    out->out_wide.push_back(utf8_wide(*ci) ? 1 : 0);
+    out->out_fields.push_back((int32_t)field);
+    return LLKV_OK;
+  };
   for (uint32_t i = 0; i < n_projections; ++i) {
     const llkv_projection &pr = projections[i];
-    std::string node;
-    // a Decimal128 column with values beyond 64 bits passes through as it was staged: low and high halves → 16 bytes
-    auto wide_column = [&](uint32_t field, std::string *n, const ColumnInfo **ci_out) -> int {
-      const ColumnInfo *ci = resolve(field);
-      if (!ci || !ci->wide128) return -1; // not one
-      int lo, hi;
-      int r = L.wide_slots_of(field, &lo, &hi);
-      if (r) return r;
-      *n = "Join128<" + std::to_string(lo) + "," + std::to_string(hi) + ">";
-      *ci_out = ci;
-      return LLKV_OK;
-    };
-    if (!pr.computed) {
-      const ColumnInfo *ci;
-      int slot;
-      if ((rc = wide_column(pr.field_id, &node, &ci)) > 0) return rc;
-      if (rc < 0) {
-        if ((rc = L.slot_of(pr.field_id, &ci, &slot, true))) return rc;
-        if (dtype_width(ci->dtype) == 0) return L.fail(LLKV_UNSUPPORTED, std::string("projection of ") + dtype_name(ci->dtype));
-        node = L.col_node(slot, storage_dtype(*ci));
-        if (ci->dtype == LLKV_DT_DECIMAL128) node = "Widen128<" + node + ">"; // back to arrow's 16-byte raw values
-      }
-      out->out_dtypes.push_back(ci->dtype);
-      out->out_wide.push_back(utf8_wide(*ci) ? 1 : 0);
-      out->out_fields.push_back((int32_t)pr.field_id);
-      std::string v;
-      if ((rc = L.valid_of_field(pr.field_id, &v))) return rc;
-      if (pad_rows) v = v.empty() ? "RowPresent" : "And<RowPresent," + v + ">"; // NULL padding of a LEFT join (select.hip.h: ProjPlan PAD)
-      if (!v.empty()) node = "OutV<" + node + "," + v + ">";
-      out->out_nullable.push_back(!v.empty());
-    } else {
+    std::string node, v;
+    if (pr.computed) {
       if (pad_rows) return L.fail(LLKV_INVALID_ARGUMENT, "join projections cannot include computed columns yet"); // hash_join.rs:822-826
-      bool is_f64 = false;
       if (!pr.expr || pr.expr_len == 0) return L.fail(LLKV_INVALID_ARGUMENT, "computed projection without expression");
-      if (pr.expr_len == 1 && pr.expr[0].kind == LLKV_TOK_COLUMN) { // bare column written as an expression
-        const ColumnInfo *ci;
-        int slot;
-        if ((rc = wide_column(pr.expr[0].field_id, &node, &ci)) > 0) return rc;
-        if (rc < 0) {
-          if ((rc = L.slot_of(pr.expr[0].field_id, &ci, &slot, true))) return rc;
-          node = L.col_node(slot, storage_dtype(*ci));
-          if (ci->dtype == LLKV_DT_DECIMAL128) node = "Widen128<" + node + ">";
-        }
-        out->out_dtypes.push_back(ci->dtype);
-        out->out_wide.push_back(utf8_wide(*ci) ? 1 : 0);
-        out->out_fields.push_back((int32_t)pr.expr[0].field_id);
-      } else {
-        L.exact_nan = true; // the consumer sees the bits of a projected value
-        rc = L.expr_fast(pr.expr, pr.expr_len, &node, &is_f64);
-        L.exact_nan = false;
-        if (rc) return rc;
-        if (L.last_fast_32) node = std::string("Narrow32<") + node + (L.last_fast_32 == 1 ? ",I32>" : ",U32>");
-        out->out_dtypes.push_back(is_f64 ? LLKV_DT_FLOAT64 : L.last_fast_32 == 1 ? LLKV_DT_INT32 : L.last_fast_32 == 2 ? LLKV_DT_UINT32 : LLKV_DT_INT64);
-        out->out_wide.push_back(0);
-        out->out_fields.push_back(-1);
-      }
-      std::string v;
-      if ((rc = L.valid_of_node(pr.expr, pr.expr_len, node, false, &v))) return rc;
-      if (!v.empty()) node = "OutV<" + node + "," + v + ">";
-      out->out_nullable.push_back(!v.empty());
     }
+    if (!pr.computed || (pr.expr_len == 1 && pr.expr[0].kind == LLKV_TOK_COLUMN)) { // a column, or a bare column written as an expression
+      const uint32_t field = pr.computed ? pr.expr[0].field_id : pr.field_id;
+      if ((rc = passthrough(field, pr.computed, &node)) || (rc = L.valid_of_field(field, &v))) return rc;
+      if (pad_rows) v = v.empty() ? "RowPresent" : "And<RowPresent," + v + ">"; // NULL padding of a LEFT join (select.hip.h: ProjPlan PAD)
+    } else {
+      Lowered x;
+      { Lowering::ExactNan exact(L); rc = L.expr_fast(pr.expr, pr.expr_len, &x); } // the consumer sees the bits of a projected value
+      if (rc) return rc;
+      node = x.fit32 ? std::string("Narrow32<") + x.node + (x.fit32 == 1 ? ",I32>" : ",U32>") : x.node;
+      out->out_dtypes.push_back(x.is_f64 ? LLKV_DT_FLOAT64 : x.fit32 == 1 ? LLKV_DT_INT32 : x.fit32 == 2 ? LLKV_DT_UINT32 : LLKV_DT_INT64);
+      out->out_wide.push_back(0);
+      out->out_fields.push_back(-1);
+      if ((rc = L.valid_of_node(pr.expr, pr.expr_len, node, false, &v))) return rc;
+    }
+    if (!v.empty()) node = "OutV<" + node + "," + v + ">";
+    out->out_nullable.push_back(!v.empty());
     outs += (i ? "," : "") + node;
   }
   out->type_string = "ProjPlan<" + cols_string(*out, &out->bytes_per_row) + "," + outs + (pad_rows ? ">,1>" : ">>");
