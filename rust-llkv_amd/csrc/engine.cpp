@@ -692,10 +692,7 @@ int Query::distinct_set(size_t agg, Scratch *dv_out, uint64_t *m_out) {
     HIP_TRY(hipMemsetAsync(flags.p, 0, (n + 1) * 8, s));
     HIP_TRY(hj_launch_run_heads(vals_s.as<uint64_t>(), n, flags.as<uint64_t>(), s));
     HIP_TRY(hipStreamSynchronize(s));
-    tb = 0;
-    HIP_TRY(hj_exclusive_scan_u64(nullptr, &tb, flags.as<uint64_t>(), offs.as<uint64_t>(), n + 1, s));
-    if ((rc = tmp.alloc(tb ? tb : 8))) return rc;
-    HIP_TRY(hj_exclusive_scan_u64(tmp.p, &tb, flags.as<uint64_t>(), offs.as<uint64_t>(), n + 1, s));
+    if ((rc = exclusive_scan_u64(flags.as<uint64_t>(), offs.as<uint64_t>(), n + 1, tmp, s))) return rc;
     HIP_TRY(hipMemcpyAsync(&m, offs.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if ((rc = hv.alloc(m * 8)) || (rc = hp.alloc(m * 4)) || (rc = hp_s.alloc(m * 4)) || (rc = dv.alloc(m * 8))) return rc;

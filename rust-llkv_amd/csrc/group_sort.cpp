@@ -394,12 +394,7 @@ int SortedGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOr
   // random gathers per position
   if (n_keys == 1 && !ks.k[0].valid) HIP_TRY(hj_launch_run_heads(keys_b.as<uint64_t>(), n, flags.as<uint64_t>(), s));
   else HIP_TRY(hj_launch_group_boundaries(ks, sel.d_dev, perm, n, flags.as<uint64_t>(), s));
-  {
-    size_t tb = 0;
-    HIP_TRY(hj_exclusive_scan_u64(nullptr, &tb, flags.as<uint64_t>(), offs.as<uint64_t>(), n + 1, s));
-    if ((rc = tmp.alloc(tb ? tb : 8))) return rc;
-    HIP_TRY(hj_exclusive_scan_u64(tmp.p, &tb, flags.as<uint64_t>(), offs.as<uint64_t>(), n + 1, s));
-  }
+  if ((rc = exclusive_scan_u64(flags.as<uint64_t>(), offs.as<uint64_t>(), n + 1, tmp, s))) return rc;
   uint64_t n_groups = 0;
   HIP_TRY(hipMemcpyAsync(&n_groups, offs.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

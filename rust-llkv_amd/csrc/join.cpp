@@ -19,6 +19,7 @@ constexpr uint32_t kJoinTileRows = 8192;
 // probe rows per device step: 32 reference scan batches.  (One batch per step — 8 workgroups, two synchronisations,
 // three small copies — ran at 0.13 G probe rows/s.)
 constexpr uint32_t kWindowTiles = 256;
+constexpr uint64_t kRefWindow = 65536; // rows of one scan batch of the reference
 
 bool fast_key_type(int32_t dt) { return dt == LLKV_DT_INT32 || dt == LLKV_DT_INT64 || dt == LLKV_DT_UINT32 || dt == LLKV_DT_UINT64; }
 // the types extract_key_value (hash_join.rs:405-505) turns into a KeyValue; any other key type fails there
@@ -235,15 +236,194 @@ static int join_build(const Table *left, const Table *right, JoinPlan *jp, hipSt
   }
   return LLKV_OK;
 }
+
+// ---- the probe (left), step by step ----------------------------------------------------------------------------------
+// Batches.  The reference probes one scan batch (65 536 rows of the left table) at a time and flushes after the probe row
+// that brings the pending pairs to ≥ batch_size, and at the end of the scan batch (fast path, hash_join.rs:1141-1213); the
+// generic path first cuts every scan batch into slices of batch_size probe rows and applies the same rule inside each slice
+// (:228-246,509-565).
+//
+// A device step covers kWindowTiles tiles — a few dozen scan batches — and is one pipeline for both deliveries of a join:
+// count (pairs per probe position) → exclusive scan (counts[npos] = 0, so offsets[npos] is the step's total; the
+// one-workgroup scan of the selection kernels is too slow for millions of positions) → the reference's forced cuts as
+// segments in position space (forced_cut, on the host) → the size cuts inside every segment, on the device from the scan
+// alone (hj_launch_batch_cuts: count, scan, write) → one readback of the total, the cuts and the pairs the step leaves in
+// the running batch (`carry`: the first segment of the next step goes on from it).  The consumer then writes the step's
+// pairs — row ids (run_join), or device rows in a layout of whole batches whose columns it gathers (run_join_batches) —
+// into one of two output buffers: step i crosses PCIe on a copy stream while step i + 1 is counted and the host hands out
+// the batches of step i − 1.
+// A many-to-many key can turn one step into billions of pairs: a consumer whose buffers the step does not fit asks for it
+// again over half the tiles (shrink).
+struct ProbeStep {
+  uint32_t t0 = 0, nt = 0, npos = 0; // tiles [t0, t0 + nt) of the probe side: nt · kJoinTileRows positions
+  uint64_t L0 = 0, L1 = 0;           // their logical rows (the rows of a rank are contiguous)
+  uint64_t total = 0;                // pairs
+  // host, until the next step is run: batch b of the step = pairs [cuts[b − 1], cuts[b]), the first one after the `carry_in`
+  // pairs of the running batch that earlier steps hold; the pairs from cuts[n_cuts − 1] on go on in the next step
+  const uint64_t *cuts = nullptr;
+  uint64_t n_cuts = 0, carry_in = 0;
+  ProbeParams p;                     // counts, match slots, offsets and the device's copy of the cuts: ready for a write pass
+};
+
+// What each of a consumer's two output buffers carries: `written` (compute stream) lets the copy stream start, `copied` the host read
+struct StepEvents {
+  hipEvent_t written = nullptr, copied = nullptr;
+  int create() {
+    HIP_TRY(hipEventCreateWithFlags(&written, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+    return LLKV_OK;
+  }
+  ~StepEvents() { // the buffers go back to their pools: nothing may still be writing them (error paths leave early)
+    if (written) { (void)hipEventSynchronize(written); (void)hipEventDestroy(written); }
+    if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
+  }
+};
+
+struct ProbeSteps {
+  const JoinPlan *jp = nullptr;
+  bool synthetic = false; // the probe side is the ONE batch an all-NULL table comes out of the reference's scan as (side_live_mask)
+  hipStream_t s = nullptr;
+  Scratch counts, mslot, offsets, scan_tmp, seg_pos_d, seg_cuts, seg_base, cuts_d, carry_d;
+  PinnedBuf seg_pos_h, cuts_h;
+  std::vector<TileDesc> ltiles;
+  uint64_t left_end = 0;
+  uint32_t step_tiles = kWindowTiles, t_next = 0;
+  uint64_t carry = 0; // pairs of the running batch in the steps run so far
+
+  int init(const JoinPlan &plan, const Table &left, bool synthetic_probe, hipStream_t stream) {
+    jp = &plan;
+    synthetic = synthetic_probe;
+    s = stream;
+    uint32_t otb[kOctantsHost + 1];
+    build_tiles_host(left, kJoinTileRows, ltiles, otb);
+    left_end = left.local_logical_start + left.local_rows;
+    const uint32_t win_pos = std::min(kWindowTiles, std::max(1u, plan.tl->n_tiles)) * kJoinTileRows;
+    int rc;
+    if ((rc = counts.ensure((size_t)(win_pos + 1) * 8)) || (rc = mslot.ensure((size_t)win_pos * 4)) || (rc = offsets.ensure((size_t)(win_pos + 1) * 8)) || (rc = carry_d.ensure(8))) return rc;
+    return LLKV_OK;
+  }
+  bool more() const { return t_next < jp->tl->n_tiles; }
+
+  ProbeParams params(uint32_t t0, uint32_t nt) const {
+    ProbeParams p;
+    std::memset(&p, 0, sizeof p);
+    p.lkey = jp->lk; p.rkey = jp->rk;
+    p.tiles = jp->tl->d_tiles.get<TileDesc>() + t0; p.n_tiles = nt; p.tile_rows = kJoinTileRows;
+    p.slot_owner = (const unsigned long long *)jp->owner.p; p.cap_mask = jp->cap - 1;
+    p.seg_start = (const uint32_t *)jp->seg_start.p; p.seg_count = (const uint32_t *)jp->seg_count.p;
+    p.sorted_idx = (const uint32_t *)jp->idx_sorted.p; p.build_logical = (const uint64_t *)jp->log_of.p;
+    p.build_dev = (const uint64_t *)jp->dev_of.p;
+    p.join_type = jp->jt;
+    p.counts = (uint64_t *)counts.p; p.match_slot = (uint32_t *)mslot.p; p.offsets = (const uint64_t *)offsets.p;
+    return p;
+  }
+
+  // The first forced cut after `row`: the end of the reference's scan batch, of the slice (generic path), of the table
+  uint64_t forced_cut(uint64_t row) const {
+    const uint64_t in_win = synthetic ? row : row % kRefWindow; // (the synthetic batch: one window)
+    uint64_t b = synthetic ? left_end : row - in_win + kRefWindow;
+    if (!jp->fast) b = std::min(b, row - in_win + (in_win / jp->batch_size + 1) * jp->batch_size);
+    return std::min(b, left_end);
+  }
+  // The step's segments in position space; returns whether the last one goes on in the next step
+  bool segments(const ProbeStep &st, std::vector<uint32_t> *seg_pos) const {
+    bool last_open = false;
+    seg_pos->assign(1, 0u);
+    if (!jp->executor) {
+      uint32_t t = st.t0;
+      auto pos_of = [&](uint64_t row) { // row in [L0, L1]
+        while (t + 1 < st.t0 + st.nt && row >= ltiles[t + 1].logical_row) ++t;
+        return (uint32_t)((t - st.t0) * kJoinTileRows + std::min<uint64_t>(row - ltiles[t].logical_row, ltiles[t].rows));
+      };
+      for (uint64_t row = st.L0; row < st.L1;) {
+        uint64_t b = forced_cut(row);
+        if (b > st.L1) { last_open = true; b = st.L1; }
+        seg_pos->push_back(b == st.L1 ? st.npos : pos_of(b));
+        row = b;
+      }
+    }
+    if (seg_pos->size() == 1) seg_pos->push_back(st.npos); // the executor's rules: one batch per device step; a step without rows
+    return last_open;
+  }
+
+  // Runs the next step (more() holds) up to the readback
+  int run(ProbeStep *step) {
+    int rc;
+    ProbeStep &st = *step;
+    st.t0 = t_next;
+    st.nt = std::min(step_tiles, jp->tl->n_tiles - st.t0);
+    const uint32_t npos = st.npos = st.nt * kJoinTileRows;
+    st.p = params(st.t0, st.nt);
+    HIP_TRY(hj_launch_probe_count(st.p, s));
+    HIP_TRY(hipMemsetAsync((uint64_t *)counts.p + npos, 0, 8, s));
+    if ((rc = exclusive_scan_u64((const uint64_t *)counts.p, (uint64_t *)offsets.p, (uint64_t)npos + 1, scan_tmp, s))) return rc;
+    uint64_t wrows = 0;
+    for (uint32_t t = 0; t < st.nt; ++t) wrows += ltiles[st.t0 + t].rows;
+    st.L0 = ltiles[st.t0].logical_row;
+    st.L1 = st.L0 + wrows;
+    std::vector<uint32_t> seg_pos;
+    const bool last_open = segments(st, &seg_pos);
+    const uint32_t n_seg = (uint32_t)seg_pos.size() - 1;
+    const uint64_t cut_cap = (uint64_t)npos + n_seg + 1;
+    if ((rc = seg_pos_h.ensure(seg_pos.size() * 4)) || (rc = seg_pos_d.ensure(seg_pos.size() * 4)) || (rc = seg_cuts.ensure((size_t)(n_seg + 1) * 8)) ||
+        (rc = seg_base.ensure((size_t)(n_seg + 1) * 8)) || (rc = cuts_d.ensure(cut_cap * 8)))
+      return rc;
+    std::memcpy(seg_pos_h.p, seg_pos.data(), seg_pos.size() * 4);
+    HIP_TRY(hipMemcpyAsync(seg_pos_d.p, seg_pos_h.p, seg_pos.size() * 4, hipMemcpyHostToDevice, s));
+    CutParams cp;
+    std::memset(&cp, 0, sizeof cp);
+    cp.offsets = (const uint64_t *)offsets.p; cp.seg_pos = (const uint32_t *)seg_pos_d.p; cp.n_seg = n_seg; cp.last_open = last_open;
+    cp.batch_size = jp->batch_size; cp.carry_in = carry; cp.carry_out = (uint64_t *)carry_d.p;
+    cp.seg_cuts = (uint64_t *)seg_cuts.p;
+    HIP_TRY(hj_launch_batch_cuts(cp, s));
+    if ((rc = exclusive_scan_u64((const uint64_t *)seg_cuts.p, (uint64_t *)seg_base.p, (uint64_t)n_seg + 1, scan_tmp, s))) return rc;
+    cp.seg_cut_base = (const uint64_t *)seg_base.p; cp.cuts = (uint64_t *)cuts_d.p;
+    HIP_TRY(hj_launch_batch_cuts(cp, s));
+    uint64_t carry_out = 0;
+    constexpr uint64_t kEagerCuts = 4096; // the first cuts travel with the counts
+    if ((rc = cuts_h.ensure(std::max<uint64_t>(cut_cap, kEagerCuts) * 8))) return rc;
+    {
+      Readback rb;
+      if ((rc = rb.add(&st.total, (uint64_t *)offsets.p + npos, 8, s)) || (rc = rb.add(&st.n_cuts, (uint64_t *)seg_base.p + n_seg, 8, s)) ||
+          (rc = rb.add(&carry_out, carry_d.p, 8, s)) || (rc = rb.add(cuts_h.p, cuts_d.p, std::min<uint64_t>(cut_cap, kEagerCuts) * 8, s)) || (rc = rb.wait()))
+        return rc;
+    }
+    if (st.n_cuts > kEagerCuts) {
+      HIP_TRY(hipMemcpyAsync(cuts_h.p, cuts_d.p, st.n_cuts * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+    }
+    st.cuts = (const uint64_t *)cuts_h.p;
+    st.p.cuts = (const uint64_t *)cuts_d.p; st.p.n_cuts = (uint32_t)st.n_cuts;
+    st.carry_in = carry;
+    carry = carry_out;
+    t_next = st.t0 + st.nt;
+    return LLKV_OK;
+  }
+  // The step just run is too large for its consumer: the next run() counts it again over half the tiles.  false: it is one tile already
+  bool shrink(const ProbeStep &st) {
+    if (st.nt <= 1) return false;
+    step_tiles = st.nt / 2;
+    t_next = st.t0;
+    carry = st.carry_in;
+    return true;
+  }
+};
 } // namespace
+
+int exclusive_scan_u64(const uint64_t *in, uint64_t *out, uint64_t n, Scratch &tmp, hipStream_t s) {
+  size_t tb = 0;
+  HIP_TRY(hj_exclusive_scan_u64(nullptr, &tb, in, out, n, s));
+  int rc = tmp.ensure(tb);
+  if (rc) return rc;
+  HIP_TRY(hj_exclusive_scan_u64(tmp.p, &tb, in, out, n, s));
+  return LLKV_OK;
+}
 
 int run_join(const Table *left, const Table *right, const llkv_join_key *keys, uint32_t n_keys,
              const llkv_join_options *options, llkv_on_join_batch on_batch, void *user) {
   JoinPlan jp;
   int rc = join_options(options, n_keys, &jp);
   if (rc) return rc;
-  const bool executor = jp.executor;
-  const uint64_t batch_size = jp.batch_size;
   const int jt = jp.jt;
   if ((rc = ensure_device())) return rc;
   if (!left || !right || !on_batch) return set_error(LLKV_INVALID_ARGUMENT, "NULL argument");
@@ -284,14 +464,12 @@ int run_join(const Table *left, const Table *right, const llkv_join_key *keys, u
     return LLKV_OK;
   }
   if ((rc = join_key_setup(left, right, keys, n_keys, &jp))) return rc;
-  const bool fast = jp.fast;
-  const JoinKeySet &lk = jp.lk, &rk = jp.rk;
 
   hipStream_t s = g_ctx.stream;
   // LLKV_HIP_TRACE=1: phase times on stderr
   const bool trace = std::getenv("LLKV_HIP_TRACE") != nullptr;
   auto t_last = std::chrono::steady_clock::now();
-  double t_acc[4] = {0, 0, 0, 0}; // probe steps: count+scan, write+copy, cuts+callbacks
+  double t_acc[3] = {0, 0, 0}; // probe steps: count+scan+cuts, write+copy, callbacks
   auto lap = [&]() {
     const auto now = std::chrono::steady_clock::now();
     const double ms = std::chrono::duration<double, std::milli>(now - t_last).count();
@@ -300,66 +478,41 @@ int run_join(const Table *left, const Table *right, const llkv_join_key *keys, u
   };
   // ---- build (right) ----
   if ((rc = join_build(left, right, &jp, s))) return rc;
-  const TileSet *tl = jp.tl;
-  const uint64_t n_build = jp.n_build, cap = jp.cap;
-  Scratch &owner = jp.owner, &log_of = jp.log_of, &seg_start = jp.seg_start, &seg_count = jp.seg_count, &idx_sorted = jp.idx_sorted;
-
-  if (trace) { (void)hipStreamSynchronize(s); std::fprintf(stderr, "[llkv join] build %9.3f ms (%llu rows)\n", lap(), (unsigned long long)n_build); }
-  // ---- probe (left), window by window ----
-  const uint32_t win_pos = std::min(kWindowTiles, std::max(1u, tl->n_tiles)) * kJoinTileRows;
-  Scratch counts, mslot, offsets, scan_tmp;
-  if ((rc = counts.ensure((size_t)(win_pos + 1) * 8)) || (rc = mslot.ensure((size_t)win_pos * 4)) || (rc = offsets.ensure((size_t)(win_pos + 1) * 8))) return rc;
+  if (trace) { (void)hipStreamSynchronize(s); std::fprintf(stderr, "[llkv join] build %9.3f ms (%llu rows)\n", lap(), (unsigned long long)jp.n_build); }
+  // ---- probe (left), step by step (ProbeSteps) ----
+  ProbeSteps ps;
+  if ((rc = ps.init(jp, *left, false, s))) return rc;
   const bool left_only = jp.left_only;
-  // Batches.  The reference probes one scan batch (65 536 rows of the left table) at a time and flushes after the
-  // probe row that brings the pending pairs to ≥ batch_size, and at the end of the scan batch (fast path,
-  // hash_join.rs:1141-1213); the generic path first cuts every scan batch into slices of batch_size probe rows
-  // and applies the same rule inside each slice (:228-246,509-565).  A device step covers many scan batches; the
-  // host finds the cuts in the left-row column of the pairs (ascending): a forced cut before the first pair of a
-  // row ≥ the boundary, a size cut after the last pair of the row that holds the batch_size-th pair.  Pairs after the
-  // last cut of a step wait in `pend_*` for the next one.
-  constexpr uint64_t kRefWindow = 65536;
-  std::vector<TileDesc> ltiles;
-  {
-    uint32_t otb[kOctantsHost + 1];
-    build_tiles_host(*left, kJoinTileRows, ltiles, otb);
-  }
-  const uint64_t left_end = left->local_logical_start + left->local_rows;
-  std::vector<uint64_t> pend_l, pend_r;
-  // Two pair buffers: while the pairs of step i cross PCIe on the copy stream and the host cuts step i − 1 into
-  // batches, the compute stream already counts step i + 1.
-  struct Step {
+  std::vector<uint64_t> pend_l, pend_r; // the pairs after the last cut of a step wait here for the next one
+  // Two pair buffers: while the pairs of step i cross PCIe on the copy stream and the host hands out the batches of
+  // step i − 1, the compute stream already counts step i + 1.
+  struct Step : StepEvents {
     Scratch out_l, out_r;
     PinnedBuf h_l, h_r;
-    hipEvent_t written = nullptr, copied = nullptr;
-    uint64_t total = 0, L0 = 0, L1 = 0;
+    uint64_t total = 0, carry_in = 0;
+    std::vector<uint64_t> cuts;
     bool live = false;
-    ~Step() { // the buffers go back to their pools: nothing may still be writing them (error paths leave early)
-      if (written) { (void)hipEventSynchronize(written); (void)hipEventDestroy(written); }
-      if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
-    }
   } steps[2];
-  for (Step &st : steps) {
-    HIP_TRY(hipEventCreateWithFlags(&st.written, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
-  }
+  for (Step &st : steps)
+    if ((rc = st.create())) return rc;
   struct CopyStream {
     hipStream_t s = nullptr;
     ~CopyStream() { if (s) (void)hipStreamDestroy(s); }
   } copy;
   HIP_TRY(hipStreamCreateWithFlags(&copy.s, hipStreamNonBlocking));
 
-  // cuts one finished step into the reference's batches
+  // hands out the batches of a finished step (the executor's rules: no batch structure to reproduce, one callback per step)
   auto emit = [&](Step &st) -> int {
     if (!st.live) return LLKV_OK;
     st.live = false;
     HIP_TRY(hipEventSynchronize(st.copied));
-    const uint64_t total = st.total, L0 = st.L0, L1 = st.L1;
+    if (st.carry_in != pend_l.size()) return set_error(LLKV_INTERNAL, "join batch carry out of step");
     const uint64_t *hl = (const uint64_t *)st.h_l.p, *hr = left_only ? nullptr : (const uint64_t *)st.h_r.p;
     uint64_t start = 0; // pairs of this step already delivered
-    auto deliver = [&](uint64_t end) {
+    for (const uint64_t end : st.cuts) {
       if (pend_l.empty()) {
         on_batch(hl + start, hr ? hr + start : nullptr, end - start, user);
-      } else {
+      } else { // the batch began in an earlier step
         pend_l.insert(pend_l.end(), hl + start, hl + end);
         if (hr) pend_r.insert(pend_r.end(), hr + start, hr + end);
         on_batch(pend_l.data(), hr ? pend_r.data() : nullptr, pend_l.size(), user);
@@ -367,80 +520,31 @@ int run_join(const Table *left, const Table *right, const llkv_join_key *keys, u
         pend_r.clear();
       }
       start = end;
-    };
-    if (executor) { // no batch structure to reproduce: one callback per device step
-      if (total) deliver(total);
-      return LLKV_OK;
     }
-    for (uint64_t row = L0; row < L1;) {
-      // the next forced cut: end of the reference scan batch, of the slice (generic path), of the table
-      const uint64_t in_win = row % kRefWindow;
-      uint64_t b = row - in_win + kRefWindow;
-      if (!fast) b = std::min(b, row - in_win + (in_win / batch_size + 1) * batch_size);
-      b = std::min(b, left_end);
-      const uint64_t seg_end = (uint64_t)(std::lower_bound(hl + start, hl + total, b) - hl); // first pair of a row ≥ b
-      while (pend_l.size() + (seg_end - start) >= batch_size) {
-        const uint64_t j = start + (batch_size - pend_l.size()) - 1; // the pair that fills the batch …
-        deliver((uint64_t)(std::upper_bound(hl + j, hl + seg_end, hl[j]) - hl)); // … and the rest of its probe row
-      }
-      if (b <= L1 && pend_l.size() + (seg_end - start) > 0) deliver(seg_end);
-      row = b;
-    }
-    if (total > start) { // the reference batch goes on in the next step
-      pend_l.insert(pend_l.end(), hl + start, hl + total);
-      if (hr) pend_r.insert(pend_r.end(), hr + start, hr + total);
+    if (st.total > start) { // the reference batch goes on in the next step
+      pend_l.insert(pend_l.end(), hl + start, hl + st.total);
+      if (hr) pend_r.insert(pend_r.end(), hr + start, hr + st.total);
     }
     return LLKV_OK;
   };
 
   int cur = 0;
-  // a many-to-many key can turn one step into billions of pairs: steps shrink until their pairs fit kMaxStepPairs
   constexpr uint64_t kMaxStepPairs = 64ull << 20; // 1 GiB of row-id pairs per buffer
-  uint32_t step_tiles = kWindowTiles;
-  for (uint32_t t0 = 0, nt = 0; t0 < tl->n_tiles; t0 += nt) {
-    nt = std::min(step_tiles, tl->n_tiles - t0);
-    const uint32_t npos = nt * kJoinTileRows;
-    ProbeParams p;
-    std::memset(&p, 0, sizeof p);
-    p.lkey = lk; p.rkey = rk;
-    p.tiles = tl->d_tiles.get<TileDesc>() + t0; p.n_tiles = nt; p.tile_rows = kJoinTileRows;
-    p.slot_owner = (const unsigned long long *)owner.p; p.cap_mask = cap - 1;
-    p.seg_start = (const uint32_t *)seg_start.p; p.seg_count = (const uint32_t *)seg_count.p;
-    p.sorted_idx = (const uint32_t *)idx_sorted.p; p.build_logical = (const uint64_t *)log_of.p;
-    p.join_type = jt;
-    p.counts = (uint64_t *)counts.p; p.match_slot = (uint32_t *)mslot.p;
-    HIP_TRY(hj_launch_probe_count(p, s));
-    // counts[npos] = 0, so offsets[npos] is the total (the one-workgroup scan of the selection kernels is too slow
-    // for millions of positions)
-    HIP_TRY(hipMemsetAsync((uint64_t *)counts.p + npos, 0, 8, s));
-    {
-      size_t tb = 0;
-      HIP_TRY(hj_exclusive_scan_u64(nullptr, &tb, (const uint64_t *)counts.p, (uint64_t *)offsets.p, (uint64_t)npos + 1, s));
-      if ((rc = scan_tmp.ensure(tb))) return rc;
-      HIP_TRY(hj_exclusive_scan_u64(scan_tmp.p, &tb, (const uint64_t *)counts.p, (uint64_t *)offsets.p, (uint64_t)npos + 1, s));
-    }
-    uint64_t total = 0;
-    Readback rb;
-    if ((rc = rb.add(&total, (uint64_t *)offsets.p + npos, 8, s)) || (rc = rb.wait())) return rc;
+  ProbeStep step;
+  while (ps.more()) {
+    if ((rc = ps.run(&step))) return rc;
     if (trace) t_acc[0] += lap();
-    if (total > kMaxStepPairs && nt > 1) { // count again over fewer tiles
-      step_tiles = std::max(1u, nt / 2);
-      nt = 0;
-      continue;
-    }
+    if (step.total > kMaxStepPairs && ps.shrink(step)) continue;
     Step &st = steps[cur];
     if ((rc = emit(st))) return rc; // its buffers are about to be reused (normally already emitted below)
-    uint64_t wrows = 0;
-    for (uint32_t t = 0; t < nt; ++t) wrows += ltiles[t0 + t].rows;
-    st.total = total;
-    st.L0 = ltiles[t0].logical_row; // the rows of a rank are contiguous
-    st.L1 = st.L0 + wrows;
+    const uint64_t total = st.total = step.total;
+    st.carry_in = step.carry_in;
+    st.cuts.assign(step.cuts, step.cuts + step.n_cuts);
     st.live = true;
     if (total) {
       if ((rc = st.out_l.ensure(total * 8)) || (rc = st.out_r.ensure(total * 8)) || (rc = st.h_l.ensure(total * 8)) || (rc = st.h_r.ensure(total * 8))) return rc;
-      p.offsets = (const uint64_t *)offsets.p;
-      p.out_left = (uint64_t *)st.out_l.p; p.out_right = (uint64_t *)st.out_r.p;
-      HIP_TRY(hj_launch_probe_write(p, s));
+      step.p.out_left = (uint64_t *)st.out_l.p; step.p.out_right = (uint64_t *)st.out_r.p;
+      HIP_TRY(hj_launch_probe_write(step.p, s));
       HIP_TRY(hipEventRecord(st.written, s));
       HIP_TRY(hipStreamWaitEvent(copy.s, st.written, 0));
       HIP_TRY(hipMemcpyAsync(st.h_l.p, st.out_l.p, total * 8, hipMemcpyDeviceToHost, copy.s));
@@ -458,7 +562,7 @@ int run_join(const Table *left, const Table *right, const llkv_join_key *keys, u
     pend_l.clear();
     pend_r.clear();
   }
-  if (trace) std::fprintf(stderr, "[llkv join] probe: count+scan %9.3f ms, write+copy %9.3f ms, cuts+callbacks %9.3f ms\n", t_acc[0], t_acc[1], t_acc[2]);
+  if (trace) std::fprintf(stderr, "[llkv join] probe: count+scan+cuts %9.3f ms, write+copy %9.3f ms, callbacks %9.3f ms\n", t_acc[0], t_acc[1], t_acc[2]);
   return LLKV_OK;
 }
 
@@ -467,16 +571,13 @@ int run_join(const Table *left, const Table *right, const llkv_join_key *keys, u
 // the device (emit_joined_batch / emit_left_joined_batch / emit_semi_batch hash_join.rs:715-772, cross_join_pair
 // cartesian.rs:22-110, synthesize_left_join_nulls hash_join.rs:1468-1497) and cross PCIe once, as column values.
 //
-// A probe step (a few dozen scan batches of the left table) runs count → scan as above; the batch cuts are then found on
-// the device from the scan alone (hj_launch_batch_cuts), the host lays the step's batches out so that each starts on a
-// multiple of 64 rows (one validity word never spans two batches, every batch's values are 256-byte aligned), the write
-// pass emits DEVICE row indices into that layout and one gather launch per side and group of columns (the projection
-// kernel of scan_stream, `ProjPlan`; PAD form for the NULL-padded side of a LEFT join) fills the output columns.  Outputs
-// are double-buffered: step i crosses PCIe on the copy stream while step i + 1 is counted and the host hands out step
-// i − 1's batches as views into the pinned buffers.
+// A probe step (ProbeSteps above) ends with its batch cuts on the host; the host lays the step's batches out so that each
+// starts on a multiple of 64 rows (one validity word never spans two batches, every batch's values are 256-byte aligned), the
+// write pass emits DEVICE row indices into that layout and one gather launch per side and group of columns (the projection
+// kernel of scan_stream, `ProjPlan`; PAD form for the NULL-padded side of a LEFT join) fills the output columns, which the
+// host hands out as views into the pinned buffers.
 namespace {
 constexpr uint32_t kGatherGroup = 5; // columns per gather launch: 5 × (values + validity mask + high halves) ≤ kMaxCols slots
-constexpr uint64_t kRefWindow = 65536;
 
 // The projected columns of one side
 struct SideOut {
@@ -562,19 +663,14 @@ int side_live_mask(const SideOut &so, Scratch *live, uint64_t *dead, hipStream_t
 }
 
 // Output buffers of one device step and what the host needs to hand its batches out
-struct OutStep {
+struct OutStep : StepEvents {
   std::vector<Scratch> d, d_valid;
   std::vector<PinnedBuf> h, h_valid;
-  hipEvent_t written = nullptr, copied = nullptr;
   bool live = false;
   uint64_t carry_in = 0;              // rows of the running batch that earlier steps hold (the device saw the same number)
   std::vector<uint64_t> pos, len;     // the step's batches: first row in the layout, rows
   std::vector<uint8_t> closed;        // the batch ends in this step
   uint32_t error = 0;
-  ~OutStep() {
-    if (written) { (void)hipEventSynchronize(written); (void)hipEventDestroy(written); }
-    if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
-  }
 };
 
 struct JoinEmitter {
@@ -607,8 +703,8 @@ struct JoinEmitter {
     pend_valid.resize(n_out());
     for (OutStep &st : steps) {
       st.d.resize(n_out()); st.d_valid.resize(n_out()); st.h.resize(n_out()); st.h_valid.resize(n_out());
-      HIP_TRY(hipEventCreateWithFlags(&st.written, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+      int rc = st.create();
+      if (rc) return rc;
     }
     HIP_TRY(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
     return d_err.ensure(8);
@@ -870,7 +966,6 @@ int run_join_batches(const Table *left, const Table *right, const llkv_join_key 
   if (l_dead && !jp.fast && !jp.executor)
     return set_error(LLKV_UNSUPPORTED, "generic join path over a probe side with rows that are NULL in every user column (the slices count surviving rows)");
   if ((rc = join_build(left, right, &jp, s))) return rc;
-  const TileSet *tl = jp.tl;
   // a build side without a batch (no right columns, no rows): INNER / SEMI find nothing, ANTI everything; a LEFT join's
   // gather_optional_indices_from_batches returns no arrays and RecordBatch::try_new fails on the column count — the
   // fast path logs and drops that error per probe batch (hash_join.rs:1058-1060), the generic path returns it (:313-317)
@@ -885,106 +980,20 @@ int run_join_batches(const Table *left, const Table *right, const llkv_join_key 
                                         std::to_string(em.L.n() + em.R.n()) + ") in schema");
   }
 
-  const uint32_t win_pos = std::min(kWindowTiles, std::max(1u, tl->n_tiles)) * kJoinTileRows;
-  Scratch counts, mslot, offsets, scan_tmp, seg_pos_d, seg_cuts, seg_base, cuts_d, carry_d, shift_d, d_lrows, d_rrows;
-  PinnedBuf seg_pos_h, cuts_h, shift_h;
-  if ((rc = counts.ensure((size_t)(win_pos + 1) * 8)) || (rc = mslot.ensure((size_t)win_pos * 4)) || (rc = offsets.ensure((size_t)(win_pos + 1) * 8)) || (rc = carry_d.ensure(8))) return rc;
-  std::vector<TileDesc> ltiles;
-  {
-    uint32_t otb[kOctantsHost + 1];
-    build_tiles_host(*left, kJoinTileRows, ltiles, otb);
-  }
-  const uint64_t left_end = left->local_logical_start + left->local_rows;
-  const uint64_t batch_size = jp.batch_size;
+  ProbeSteps ps;
+  if ((rc = ps.init(jp, *left, l_synthetic, s))) return rc;
+  Scratch shift_d, d_lrows, d_rrows;
+  PinnedBuf shift_h;
   constexpr uint64_t kMaxStepRows = 16ull << 20; // output rows of one step (× the row width in HBM and in pinned memory, twice)
-  uint32_t step_tiles = kWindowTiles;
-  uint64_t carry = 0; // rows of the running batch in steps already launched
   int cur = 0;
-  for (uint32_t t0 = 0, nt = 0; t0 < tl->n_tiles; t0 += nt) {
-    nt = std::min(step_tiles, tl->n_tiles - t0);
-    const uint32_t npos = nt * kJoinTileRows;
-    ProbeParams p;
-    std::memset(&p, 0, sizeof p);
-    p.lkey = jp.lk; p.rkey = jp.rk;
-    p.tiles = tl->d_tiles.get<TileDesc>() + t0; p.n_tiles = nt; p.tile_rows = kJoinTileRows;
-    p.slot_owner = (const unsigned long long *)jp.owner.p; p.cap_mask = jp.cap - 1;
-    p.seg_start = (const uint32_t *)jp.seg_start.p; p.seg_count = (const uint32_t *)jp.seg_count.p;
-    p.sorted_idx = (const uint32_t *)jp.idx_sorted.p; p.build_logical = (const uint64_t *)jp.log_of.p;
-    p.build_dev = (const uint64_t *)jp.dev_of.p;
-    p.join_type = jt;
-    p.counts = (uint64_t *)counts.p; p.match_slot = (uint32_t *)mslot.p;
-    HIP_TRY(hj_launch_probe_count(p, s));
-    HIP_TRY(hipMemsetAsync((uint64_t *)counts.p + npos, 0, 8, s));
-    {
-      size_t tb = 0;
-      HIP_TRY(hj_exclusive_scan_u64(nullptr, &tb, (const uint64_t *)counts.p, (uint64_t *)offsets.p, (uint64_t)npos + 1, s));
-      if ((rc = scan_tmp.ensure(tb))) return rc;
-      HIP_TRY(hj_exclusive_scan_u64(scan_tmp.p, &tb, (const uint64_t *)counts.p, (uint64_t *)offsets.p, (uint64_t)npos + 1, s));
-    }
-    // the step's segments in position space: a forced cut at the end of every reference scan batch (65 536 row ids), of
-    // every slice of batch_size rows of it (generic path), and of the table
-    uint64_t wrows = 0;
-    for (uint32_t t = 0; t < nt; ++t) wrows += ltiles[t0 + t].rows;
-    const uint64_t L0 = ltiles[t0].logical_row, L1 = L0 + wrows; // the rows of a rank are contiguous
-    std::vector<uint32_t> seg_pos;
-    bool last_open = false;
-    if (jp.executor) { // one batch per device step
-      seg_pos = {0u, npos};
-    } else {
-      uint32_t t = t0;
-      auto pos_of = [&](uint64_t row) { // row in [L0, L1]
-        while (t + 1 < t0 + nt && row >= ltiles[t + 1].logical_row) ++t;
-        return (uint32_t)((t - t0) * kJoinTileRows + std::min<uint64_t>(row - ltiles[t].logical_row, ltiles[t].rows));
-      };
-      seg_pos.push_back(0);
-      for (uint64_t row = L0; row < L1;) {
-        const uint64_t in_win = l_synthetic ? row : row % kRefWindow; // (the synthetic batch of an all-NULL side: one window)
-        uint64_t b = l_synthetic ? left_end : row - in_win + kRefWindow;
-        if (!jp.fast) b = std::min(b, row - in_win + (in_win / batch_size + 1) * batch_size);
-        b = std::min(b, left_end);
-        if (b > L1) { last_open = true; b = L1; }
-        seg_pos.push_back(b == L1 ? npos : pos_of(b));
-        row = b;
-      }
-      if (seg_pos.size() == 1) seg_pos.push_back(npos); // (a step without rows)
-    }
-    const uint32_t n_seg = (uint32_t)seg_pos.size() - 1;
-    const uint64_t cut_cap = (uint64_t)npos + n_seg + 1;
-    if ((rc = seg_pos_h.ensure(seg_pos.size() * 4)) || (rc = seg_pos_d.ensure(seg_pos.size() * 4)) || (rc = seg_cuts.ensure((size_t)(n_seg + 1) * 8)) ||
-        (rc = seg_base.ensure((size_t)(n_seg + 1) * 8)) || (rc = cuts_d.ensure(cut_cap * 8)))
-      return rc;
-    std::memcpy(seg_pos_h.p, seg_pos.data(), seg_pos.size() * 4);
-    HIP_TRY(hipMemcpyAsync(seg_pos_d.p, seg_pos_h.p, seg_pos.size() * 4, hipMemcpyHostToDevice, s));
-    CutParams cp;
-    std::memset(&cp, 0, sizeof cp);
-    cp.offsets = (const uint64_t *)offsets.p; cp.seg_pos = (const uint32_t *)seg_pos_d.p; cp.n_seg = n_seg; cp.last_open = last_open;
-    cp.batch_size = batch_size; cp.carry_in = carry; cp.carry_out = (uint64_t *)carry_d.p;
-    cp.seg_cuts = (uint64_t *)seg_cuts.p;
-    HIP_TRY(hj_launch_batch_cuts(cp, s));
-    {
-      size_t tb = 0;
-      HIP_TRY(hj_exclusive_scan_u64(nullptr, &tb, (const uint64_t *)seg_cuts.p, (uint64_t *)seg_base.p, (uint64_t)n_seg + 1, s));
-      if ((rc = scan_tmp.ensure(tb))) return rc;
-      HIP_TRY(hj_exclusive_scan_u64(scan_tmp.p, &tb, (const uint64_t *)seg_cuts.p, (uint64_t *)seg_base.p, (uint64_t)n_seg + 1, s));
-    }
-    cp.seg_cut_base = (const uint64_t *)seg_base.p; cp.cuts = (uint64_t *)cuts_d.p;
-    HIP_TRY(hj_launch_batch_cuts(cp, s));
-    uint64_t total = 0, n_cuts = 0, carry_out = 0;
-    constexpr uint64_t kEagerCuts = 4096; // the first cuts travel with the counts
-    if ((rc = cuts_h.ensure(std::max<uint64_t>(cut_cap, kEagerCuts) * 8))) return rc;
-    {
-      Readback rb;
-      if ((rc = rb.add(&total, (uint64_t *)offsets.p + npos, 8, s)) || (rc = rb.add(&n_cuts, (uint64_t *)seg_base.p + n_seg, 8, s)) ||
-          (rc = rb.add(&carry_out, carry_d.p, 8, s)) || (rc = rb.add(cuts_h.p, cuts_d.p, std::min<uint64_t>(cut_cap, kEagerCuts) * 8, s)) || (rc = rb.wait()))
-        return rc;
-    }
-    if (n_cuts > kEagerCuts) {
-      HIP_TRY(hipMemcpyAsync(cuts_h.p, cuts_d.p, n_cuts * 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-    }
+  ProbeStep step;
+  while (ps.more()) {
+    if ((rc = ps.run(&step))) return rc;
+    const uint64_t total = step.total, n_cuts = step.n_cuts, carry = step.carry_in;
+    const uint64_t *cuts = step.cuts;
+    ProbeParams &p = step.p;
     // the layout: batch b of the step (b = n_cuts: the rows after the last cut, which the next step continues) at a
     // multiple of 64 — the first one at carry % 64, where the running batch's validity words go on
-    const uint64_t *cuts = (const uint64_t *)cuts_h.p;
     std::vector<uint64_t> pos(n_cuts + 1), len(n_cuts + 1);
     uint64_t at = carry % 64, start = 0;
     for (uint64_t b = 0; b <= n_cuts; ++b) {
@@ -994,18 +1003,13 @@ int run_join_batches(const Table *left, const Table *right, const llkv_join_key 
       start = end;
     }
     const uint64_t rows = at;
-    if (rows > kMaxStepRows && nt > 1) { // a many-to-many key: count again over fewer tiles
-      step_tiles = std::max(1u, nt / 2);
-      nt = 0;
-      continue;
-    }
+    if (rows > kMaxStepRows && ps.shrink(step)) continue; // a many-to-many key
     OutStep &st = em.steps[cur];
     if ((rc = em.emit(st))) return rc; // its buffers are about to be reused (normally already emitted below)
     st.carry_in = carry;
     st.pos = pos; st.len = len;
     st.closed.assign(n_cuts + 1, 1);
     st.closed[n_cuts] = 0;
-    carry = carry_out;
     if (total) {
       if ((rc = shift_h.ensure((n_cuts + 1) * 8)) || (rc = shift_d.ensure((n_cuts + 1) * 8)) || (rc = d_lrows.ensure(rows * 8)) || (rc = d_rrows.ensure(rows * 8))) return rc;
       int64_t *sh = (int64_t *)shift_h.p;
@@ -1015,8 +1019,7 @@ int run_join_batches(const Table *left, const Table *right, const llkv_join_key 
       // layout positions no pair lands on gather row 0 (left) / nothing (right)
       HIP_TRY(hipMemsetAsync(d_lrows.p, 0, rows * 8, s));
       if (em.right_out) HIP_TRY(hipMemsetAsync(d_rrows.p, jt == LLKV_JOIN_LEFT ? 0xFF : 0, rows * 8, s));
-      p.offsets = (const uint64_t *)offsets.p;
-      p.cuts = (const uint64_t *)cuts_d.p; p.n_cuts = (uint32_t)n_cuts; p.batch_shift = (const int64_t *)shift_d.p;
+      p.batch_shift = (const int64_t *)shift_d.p;
       p.out_left = (uint64_t *)d_lrows.p; p.out_right = em.right_out ? (uint64_t *)d_rrows.p : nullptr;
       HIP_TRY(hj_launch_probe_write_rows(p, s));
       if ((rc = em.gather(st, (const uint64_t *)d_lrows.p, (const uint64_t *)d_rrows.p, rows, build_empty, s))) return rc;

@@ -169,6 +169,10 @@ hipError_t hj_launch_semi_flags(const JoinKeyColumn &fk, const uint64_t *dev_row
                                 const unsigned long long *set_owner, uint64_t set_mask, uint64_t *flags, hipStream_t s);
 hipError_t hj_launch_compact(const uint64_t *in, const uint64_t *flags, const uint64_t *offsets, uint64_t n, uint64_t *out, hipStream_t s);
 hipError_t hj_exclusive_scan_u64(void *tmp, size_t *tmp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s);
+// … with its temporary storage: asks for the size, grows `tmp` to it, scans (join.cpp).  `tmp` belongs to the caller and must
+// outlive the scan on the stream (no host synchronisation here); nothing queued earlier may still use it when it has to grow.
+struct Scratch;
+int exclusive_scan_u64(const uint64_t *in, uint64_t *out, uint64_t n, Scratch &tmp, hipStream_t s);
 hipError_t hj_sort_u32_u64(void *tmp, size_t *tmp_bytes, const uint32_t *kin, uint32_t *kout, const uint64_t *vin, uint64_t *vout,
                            uint64_t n, uint32_t bits, hipStream_t s);
 hipError_t hj_sort_u64_u32(void *tmp, size_t *tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout,

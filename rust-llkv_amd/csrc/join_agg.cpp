@@ -113,16 +113,6 @@ struct DirectTable {
   }
 };
 
-// `tmp` belongs to the caller and must outlive the scan on the stream (no host synchronisation here)
-int scan_exclusive(const uint64_t *in, uint64_t *out, uint64_t n, DB &tmp, hipStream_t s) {
-  size_t tb = 0;
-  HIP_TRY(hj_exclusive_scan_u64(nullptr, &tb, in, out, n, s));
-  int rc = tmp.alloc(tb ? tb : 8);
-  if (rc) return rc;
-  HIP_TRY(hj_exclusive_scan_u64(tmp.p, &tb, in, out, n, s));
-  return LLKV_OK;
-}
-
 // ORDER BY sum DESC, payload[0] ASC (arrow lexsort, llkv-executor/src/lib.rs:13847-13864); ties beyond that
 // are left in an unspecified order by the reference — here: dim row order, so every rank count agrees.
 bool row_before(const llkv_join_group_row &a, const llkv_join_group_row &b, uint32_t n_payload) {
@@ -440,7 +430,7 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
     DB flags, offs, scan_tmp;
     if ((rc = flags.alloc(seld.n * 8)) || (rc = offs.alloc((seld.n + 1) * 8))) return rc;
     HIP_TRY(hj_launch_semi_flags(fk, seld.d_dev, seld.n, k2, (const unsigned long long *)set2.owner.p, set2.cap - 1, (uint64_t *)flags.p, s));
-    if ((rc = scan_exclusive((const uint64_t *)flags.p, (uint64_t *)offs.p, seld.n, scan_tmp, s))) return rc;
+    if ((rc = exclusive_scan_u64((const uint64_t *)flags.p, (uint64_t *)offs.p, seld.n, scan_tmp, s))) return rc;
     uint64_t last_off = 0, last_flag = 0;
     HIP_TRY(hipMemcpyAsync(&last_off, (uint64_t *)offs.p + seld.n - 1, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&last_flag, (uint64_t *)flags.p + seld.n - 1, 8, hipMemcpyDeviceToHost, s));
@@ -649,7 +639,7 @@ int JoinAgg::compact_pairs(bool run_sums) {
   DB scan_tmp;
   if (n_slots <= 64 * 1024) HIP_TRY(launch_exclusive_scan((const uint64_t *)counts.p, (uint64_t *)offsets.p, n_slots, s)); // one workgroup, rounds of 8 192
   else {
-    if ((rc = scan_exclusive((const uint64_t *)counts.p, (uint64_t *)offsets.p, n_slots + 1, scan_tmp, s))) return rc;
+    if ((rc = exclusive_scan_u64((const uint64_t *)counts.p, (uint64_t *)offsets.p, n_slots + 1, scan_tmp, s))) return rc;
     HIP_TRY(hipStreamSynchronize(s)); // scan_tmp is released on return
   }
   const uint64_t max_pairs = tf->local_rows;
@@ -722,7 +712,7 @@ int JoinAgg::straddlers() {
   HIP_TRY(hj_launch_fill(flags.p, (n_pairs + 1) * 8, 0, s));
   HIP_TRY(hj_launch_straddler_flags((const uint32_t *)s_group.p, n_pairs, (const uint64_t *)cnts.p, (const int64_t *)gcnts.p, (uint64_t *)flags.p, s));
   DB scan_tmp;
-  if ((rc = scan_exclusive((const uint64_t *)flags.p, (uint64_t *)offs.p, n_pairs + 1, scan_tmp, s))) return rc;
+  if ((rc = exclusive_scan_u64((const uint64_t *)flags.p, (uint64_t *)offs.p, n_pairs + 1, scan_tmp, s))) return rc;
   uint64_t n = 0;
   Readback rb;
   if ((rc = rb.add(&n, (uint64_t *)offs.p + n_pairs, 8, s)) || (rc = rb.wait())) return rc;

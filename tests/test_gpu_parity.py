@@ -2572,6 +2572,34 @@ def test_join_with_exploding_match_counts_shrinks_its_steps(rt, abi):
     assert sum(sizes) == nl * nr and sizes == want
 
 
+@pytest.mark.parametrize("path", ["fast", "generic"])
+@pytest.mark.parametrize("chunk", [83, 211])
+def test_join_batches_are_cut_the_same_across_device_steps(rt, orc, abi, chunk, path):
+    """A probe side of 700 tiny chunks: a tile never spans a chunk and a device step is 256 tiles, so its 58 100 (chunk 83: under
+    one 65 536-row scan batch — size cuts and carries only) or 147 700 rows (chunk 211: forced cuts inside a step) cross three
+    steps.  Every probe row meets 3 build rows.  Both deliveries follow the oracle batch by batch, and — no column has a NULL
+    cell, so no row is dropped — the index-pair batches of an INNER / LEFT join are as long as its RecordBatches."""
+    n_chunks, nb = 700, 150
+    n = n_chunks * chunk
+    lk, rk = np.arange(n, dtype=np.int64) % 50, np.arange(nb, dtype=np.int64) % 50
+    lv, rv = np.arange(n, dtype=np.int64), -np.arange(nb, dtype=np.int64)
+    lt = rt.HipTable(1, [chunk] * n_chunks); lt.append_column(1, abi.DT_INT64, lk); lt.append_column(2, abi.DT_INT64, lv)
+    rtab = rt.HipTable(2, [nb]); rtab.append_column(11, abi.DT_INT64, rk); rtab.append_column(12, abi.DT_INT64, rv)
+    ol = orc.OracleTable(n).add(1, abi.DT_INT64, lk).add(2, abi.DT_INT64, lv)
+    orr = orc.OracleTable(nb).add(11, abi.DT_INT64, rk).add(12, abi.DT_INT64, rv)
+    keys = [(1, 11)] if path == "fast" else [(1, 11), (1, 11)]  # the same pair twice: the generic typed-key path
+    lcols, rcols = [(2, "v")], [(12, "w")]
+    for batch in (100, 4096, 5000):
+        for jt in ("inner", "left", "semi", "anti"):
+            pairs = rt.join_stream(lt, rtab, keys, JT[jt], batch)
+            assert pairs == orc.hash_join(ol, orr, keys, JT[jt], batch), (batch, jt)
+            rows = rt.join_stream_batches(lt, rtab, keys, lcols, rcols, JT[jt], batch)
+            _same_batches(rows, orc.hash_join_batches(ol, orr, keys, lcols, rcols, JT[jt], batch), (batch, jt))
+            if jt in ("inner", "left"):
+                assert [len(b[0]) for b in pairs] == [len(cols[0]) for _, cols in rows], (batch, jt)
+                assert sum(len(b[0]) for b in pairs) == 3 * n
+
+
 def test_executor_rule_joins_match_oracle(rt, orc, abi):
     """llkv_join_options.key_rules = EXECUTOR: the SQL joins of the executor (normalised keys, arrow-row equality,
     INNER / LEFT, no batch structure) — llkv-executor/src/lib.rs:12218-12581."""
