@@ -866,6 +866,34 @@ llkv_status llkv_hip_join_groupby_topk(const llkv_join_side *fact, const llkv_jo
                                        uint32_t limit, llkv_join_group_row *out_rows, uint32_t *out_n,
                                        uint64_t *out_total_groups);
 
+/* The same star, order and delivery for an EXACT sum: `sum_expr` is any expression the GROUP BY (PlanValue) semantics type as
+ * Int64 or as a decimal — a bare Int64 column, a bare Decimal128 column whose values fit 64 bits, Int64 or decimal
+ * arithmetic (TPC-H Q3 over DECIMAL(15,2): l_extendedprice * (1 - l_discount)).  Integer sums do not depend on the order of
+ * the additions: every run of a group's rows is added to the group's sum with one atomic add, so the fact table need not be
+ * clustered by the join key.  `sum` is, cell for cell (dtype, is_null, raw value, precision, scale), what
+ * llkv_hip_join_groupby_prepare / _rows return for [SUM(expr), COUNT(*)]: Int64 for an Int64 argument, Decimal128(15,2)-style
+ * column types for a bare decimal column, and for a computed decimal argument Decimal128(p, scale of the expression) with
+ * p = the digits of the group's first value in row order.  When ANY group's first value has fewer digits than a positive
+ * scale the call fails as that route does (LLKV_INVALID_ARGUMENT, "invalid Decimal128 precision/scale: …"), whatever `limit`
+ * is; when several groups do, the message names the one whose dimension row comes first.
+ * LLKV_UNSUPPORTED (the general route keeps the query): a Float64 argument (that is llkv_hip_join_groupby_topk's), an
+ * argument the column statistics do not bound or whose rows · max|v| may leave i64, NULL-able argument columns, a sharded
+ * fact table (world != 1).                                                                                              */
+typedef struct llkv_join_group_exact_row {
+  int64_t key;
+  llkv_value sum;
+  uint64_t count;
+  int64_t payload[4];
+  uint64_t group_index;
+} llkv_join_group_exact_row;
+
+llkv_status llkv_hip_join_groupby_topk_exact(const llkv_join_side *fact, const llkv_join_side *dim,
+                                             uint32_t dim_fk_field, const llkv_join_side *dim2 /* may be NULL */,
+                                             const uint32_t *payload_fields, uint32_t n_payload,
+                                             const llkv_expr_token *sum_expr, uint32_t sum_expr_len,
+                                             uint32_t limit, llkv_join_group_exact_row *out_rows, uint32_t *out_n,
+                                             uint64_t *out_total_groups);
+
 /* The same pipeline for a fact table sharded over ranks (one process per GPU):
  * the dimension tables are staged whole (world = 1) on every rank, the fact table by chunk.
  *   1. prepare            local build, probe, per-group sums and row counts (group = qualifying dim row)
@@ -1085,7 +1113,9 @@ typedef enum llkv_route {
   LLKV_ROUTE_COMPOUND = 1,          /* :531-533 execute_compound_select          — CPU                              */
   LLKV_ROUTE_NO_TABLE = 2,          /* :534-536 execute_select_without_table     — CPU                              */
   LLKV_ROUTE_GROUP_BY = 3,          /* :541-543 execute_group_by_single_table    → llkv_hip_query_prepare_groupby  */
-  LLKV_ROUTE_CROSS_PRODUCT = 4,     /* :537-539,544-546 execute_cross_product    → llkv_hip_join_groupby_topk /
+  LLKV_ROUTE_CROSS_PRODUCT = 4,     /* :537-539,544-546 execute_cross_product    → llkv_hip_join_groupby_topk (f64 sums) /
+                                                                                    llkv_hip_join_groupby_topk_exact
+                                                                                    (Int64 / decimal sums) /
                                                                                     llkv_hip_join_stream            */
   LLKV_ROUTE_AGGREGATES = 5,        /* :552-554 execute_aggregates               → llkv_hip_query_prepare_aggregate */
   LLKV_ROUTE_COMPUTED_AGGREGATES = 6, /* :555-557 execute_computed_aggregates    → llkv_hip_query_prepare_aggregate */
@@ -1139,6 +1169,20 @@ llkv_status llkv_plan_lower(const llkv_column_desc *cols, uint32_t n_cols,
                             int32_t grouped, char *type_string_out, uint64_t type_string_cap,
                             uint32_t *lanes_out, uint64_t *bytes_per_row_out);
 const char *llkv_plan_last_error(void);
+/* The fact side of the join → GROUP BY → top-k calls, lowered as their prepare does ("ProbePlan<…>").  `flags`: 1 = the
+ * exact form (llkv_hip_join_groupby_topk_exact: an Int64 or decimal SUM argument; without it the argument must be Float64),
+ * 2 = emit key-bit positions.  `value`, when given, reports what the argument is.  Host only.                        */
+typedef struct llkv_probe_value_info {
+  int32_t is_f64, is_decimal, scale;
+  int32_t bounded;          /* [min, max] bound every row's value (column statistics through interval arithmetic) */
+  int64_t min_i, max_i;     /* … saturated to the i64 range                                                       */
+  uint64_t rows;            /* most rows the argument takes                                                       */
+  int32_t typed_by_first_value; /* exact form: the cell is typed by each group's first value (a computed argument)       */
+  int32_t sum_precision;    /* exact form: Decimal128 cells of a bare column carry this precision (0: the first value's digits) */
+} llkv_probe_value_info;
+llkv_status llkv_plan_lower_probe(const llkv_column_desc *cols, uint32_t n_cols, const llkv_filter *filters, uint32_t n_filters,
+                                  uint32_t key_field, const llkv_expr_token *expr, uint32_t expr_len, int32_t flags,
+                                  char *type_string_out, uint64_t type_string_cap, llkv_probe_value_info *value);
 /* The integer literal bank and the CodeBits bitmaps (wide Utf8 leaves, back to back) of the plan the calling thread lowered
  * last with llkv_plan_lower: up to the caps are copied, the full counts are returned.  Host only.                    */
 llkv_status llkv_plan_last_banks(int64_t *lit_i, uint32_t lit_cap, uint32_t *n_lit, uint64_t *code_bits, uint64_t bits_cap, uint64_t *n_bits);

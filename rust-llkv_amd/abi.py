@@ -219,6 +219,19 @@ class CJoinGroupRow(C.Structure):
                 ("group_index", C.c_uint64)]
 
 
+class CJoinGroupExactRow(C.Structure):
+    """llkv_join_group_exact_row: a row of llkv_hip_join_groupby_topk_exact (the sum as a finalized cell)."""
+    _fields_ = [("key", C.c_int64), ("sum", CValue), ("count", C.c_uint64), ("payload", C.c_int64 * 4),
+                ("group_index", C.c_uint64)]
+
+
+class CProbeValueInfo(C.Structure):
+    """llkv_probe_value_info: what llkv_plan_lower_probe reports about the SUM argument."""
+    _fields_ = [("is_f64", C.c_int32), ("is_decimal", C.c_int32), ("scale", C.c_int32), ("bounded", C.c_int32),
+                ("min_i", C.c_int64), ("max_i", C.c_int64), ("rows", C.c_uint64), ("typed_by_first_value", C.c_int32),
+                ("sum_precision", C.c_int32)]
+
+
 class CArr0Desc(C.Structure):
     _fields_ = [("layout", C.c_int32), ("type_code", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32), ("len", C.c_uint64),
                 ("payload_offset", C.c_uint64), ("values_offset", C.c_uint64), ("values_len", C.c_uint64), ("offsets_len", C.c_uint64)]

@@ -532,6 +532,7 @@ hipError_t hj_launch_run_sums(const uint32_t *group, const uint64_t *val, uint64
 // pairs.  One wave per stripe; the first pair of a run walks it to its end, across stripes.  counts[s] carries the
 // predicate-error mark of the probe (kPredErrorBit): it is raised into flags[1]; flags[0] as `multi_run` above.
 __device__ __forceinline__ uint64_t desc_order_key(double v); // (top-k section below)
+__device__ __forceinline__ uint64_t desc_order_key(double lane, uint32_t int_sums);
 // key-bit position → group id (RankCols, join.hpp)
 __device__ __forceinline__ uint32_t rank_of_keybit(const RankCols &r, uint32_t d) {
   const uint32_t word = d >> 6;
@@ -669,6 +670,117 @@ hipError_t hj_launch_run_sums_dev(const uint32_t *group, const uint64_t *val, co
   hipLaunchKernelGGL(hj_run_sums_dev_kernel, dim3(grid), dim3(256), 0, s, group, val, n_dev, sum_by_group, (unsigned long long *)count_by_group, multi_run, descending);
   return hipGetLastError();
 }
+
+// ---- exact integer sums (llkv_hip_join_groupby_topk_exact) --------------------------------------------------------------------
+// The values are Int64 / the raw 64-bit images of decimals: their sum does not depend on the order of the additions, so nothing
+// of the run walk above is needed — no walk into later stripes, no second-run flag, no sort.  Every kL-lane group stages a chunk
+// of its stripe in the LDS as above; the head of each run INSIDE the chunk adds the run's lanes and issues one agent-scope
+// atomic add (no return value) to the group's sum and one to its row count, which must both start from zero.
+// `first_by_group` (computed decimal arguments: the cell is typed by the group's first value): one word per group, zero = empty,
+// else ~((pair position << 8) | decimal digits of the value) under an atomic max — the largest word is the first pair's.
+__device__ __forceinline__ uint32_t decimal_digits(long long v) { // digit_count of |v|: 1 for zero (fused_scan.hip.h: DecDigits)
+  const uint64_t m = v < 0 ? 0ull - (uint64_t)v : (uint64_t)v;
+  uint32_t d = 1;
+  uint64_t p = 10;
+#pragma unroll
+  for (int k = 1; k <= 19; ++k) { d += m >= p ? 1u : 0u; p *= 10ull; } // (10^19 < 2^64; the 20th product wraps and is not compared)
+  return d;
+}
+__device__ __forceinline__ void int_sum_add(const IntSumLanes &out, uint32_t gid, unsigned long long acc, unsigned long long rows, uint64_t first_pos, long long first_val) {
+  (void)__hip_atomic_fetch_add(&out.sum[gid], acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  (void)__hip_atomic_fetch_add(&out.count[gid], rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (out.first) (void)__hip_atomic_fetch_max(&out.first[gid], ~((first_pos << 8) | (unsigned long long)decimal_digits(first_val)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__global__ __launch_bounds__(256) void hj_int_sums_stripes_kernel(const uint32_t *stripe_group, const uint64_t *stripe_val, const uint64_t *counts, uint32_t n_slots,
+                                                                   uint32_t stripe, IntSumLanes out, uint32_t *flags, RankCols rank) {
+  constexpr uint32_t kL = 64 / kRunSumSlots;
+  __shared__ uint32_t lg[4][64];
+  __shared__ uint64_t lv[4][64];
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6, sl = lane & (kL - 1), l0 = lane - sl;
+  const uint32_t slot = (blockIdx.x * (blockDim.x >> 6) + w) * kRunSumSlots + lane / kL;
+  uint32_t cnt = 0;
+  if (slot < n_slots) {
+    const uint64_t raw = counts[slot];
+    if (raw >= kPredErrorBit && sl == 0) atomicOr(&flags[1], 1u);
+    cnt = (uint32_t)(raw & (kPredErrorBit - 1));
+  }
+  // the group of the pair before this stripe's first one (the key-order flag only: a run that goes on here is added where it lies)
+  uint32_t before = 0xFFFFFFFFu;
+  if (cnt)
+    for (long long s = (long long)slot - 1; s >= 0; --s) {
+      const uint32_t c = (uint32_t)(counts[s] & (kPredErrorBit - 1));
+      if (c) { before = stripe_group[(uint64_t)s * stripe + c - 1]; break; }
+    }
+  const uint32_t *grp = stripe_group + (uint64_t)slot * stripe;
+  const uint64_t *val = stripe_val + (uint64_t)slot * stripe;
+  for (uint32_t base = 0; __any(base < cnt); base += kL) {
+    const uint32_t i = base + sl;
+    const bool live = i < cnt;
+    const uint32_t g = live ? grp[i] : 0xFFFFFFFFu;
+    lg[w][lane] = g;
+    lv[w][lane] = live ? val[i] : 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint32_t left = sl ? lg[w][lane - 1] : (base && live ? grp[base - 1] : before);
+    if (live && left != 0xFFFFFFFFu && left > g) atomicOr(&flags[3], 1u); // the pair stream is not in key order
+    if (live && (sl == 0 || left != g)) { // the first pair of its run inside the chunk
+      unsigned long long acc = 0, n = 0;
+      const uint32_t m = cnt - base < kL ? cnt - base : kL; // pairs of this stripe in the chunk
+      for (uint32_t j = sl; j < m && lg[w][l0 + j] == g; ++j) { acc += lv[w][l0 + j]; ++n; }
+      const uint32_t gid = rank.bits ? rank_of_keybit(rank, g) : g;
+      int_sum_add(out, gid, acc, n, (uint64_t)slot * stripe + i, (long long)lv[w][lane]);
+      if (rank.pos_out) rank.pos_out[gid] = g;
+    }
+    __builtin_amdgcn_wave_barrier(); // the chunk is overwritten next
+  }
+}
+hipError_t hj_launch_int_sums_stripes(const uint32_t *stripe_group, const uint64_t *stripe_val, const uint64_t *counts, uint32_t n_slots, uint32_t stripe,
+                                      IntSumLanes out, uint32_t *flags, hipStream_t s, RankCols rank) {
+  if (n_slots == 0) return hipSuccess;
+  hipLaunchKernelGGL(hj_int_sums_stripes_kernel, dim3((n_slots + 4 * kRunSumSlots - 1) / (4 * kRunSumSlots)), dim3(256), 0, s, stripe_group, stripe_val, counts, n_slots, stripe,
+                     out, flags, rank);
+  return hipGetLastError();
+}
+// The same over compacted pairs (the pair count still on the device; nothing runs when it carries the predicate-error mark): the
+// pairs are cut into chunks of 64, the head of each run inside a chunk adds it.  The pair position is the pair's index.
+__global__ __launch_bounds__(256) void hj_int_sums_pairs_kernel(const uint32_t *group, const uint64_t *val, const uint64_t *n_dev, IntSumLanes out, uint32_t *descending) {
+  const uint64_t n = *n_dev;
+  if (n >= kPredErrorBit) return;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t g = group[i];
+    const uint32_t left = i ? group[i - 1] : 0xFFFFFFFFu;
+    if (descending && i != 0 && left > g) atomicOr(descending, 1u); // the pair stream is not in group (= key) order
+    if ((i & 63) != 0 && left == g) continue;
+    const uint64_t end = (i | 63) + 1 < n ? (i | 63) + 1 : n;
+    unsigned long long acc = 0;
+    uint64_t j = i;
+    for (; j < end && group[j] == g; ++j) acc += val[j];
+    int_sum_add(out, g, acc, j - i, i, (long long)val[i]);
+  }
+}
+hipError_t hj_launch_int_sums_pairs(const uint32_t *group, const uint64_t *val, const uint64_t *n_dev, uint64_t n_max, IntSumLanes out, hipStream_t s, uint32_t *descending) {
+  if (n_max == 0) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((n_max + 255) / 256, 2048);
+  hipLaunchKernelGGL(hj_int_sums_pairs_kernel, dim3(grid), dim3(256), 0, s, group, val, n_dev, out, descending);
+  return hipGetLastError();
+}
+// A computed decimal argument: a group whose first value has fewer digits than the (positive) scale fails the whole query, whether
+// it would be delivered or not.  *flag (zero before): ~((group << 8) | digits) of the first such group, by an atomic max.
+__global__ __launch_bounds__(256) void hj_first_digits_check_kernel(IntSumLanes lanes, uint64_t n, const uint32_t *n_dev, uint32_t scale, unsigned long long *flag) {
+  if (n_dev) n = *n_dev < n ? *n_dev : n;
+  for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (uint64_t)gridDim.x * blockDim.x) {
+    if (lanes.count[g] == 0) continue;
+    const unsigned long long digits = ~lanes.first[g] & 0xFFull;
+    if (digits < scale) (void)__hip_atomic_fetch_max(flag, ~((g << 8) | digits), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+hipError_t hj_launch_first_digits_check(IntSumLanes lanes, uint64_t n, const uint32_t *n_dev, uint32_t scale, uint64_t *flag, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 1024);
+  hipLaunchKernelGGL(hj_first_digits_check_kernel, dim3(grid), dim3(256), 0, s, lanes, n, n_dev, scale, (unsigned long long *)flag);
+  return hipGetLastError();
+}
 hipError_t hj_launch_segment_sums(const uint32_t *sorted_slot, const uint64_t *sorted_val, uint64_t n, double *sum_by_slot,
                                   uint64_t *count_by_slot, hipStream_t s) {
   if (n == 0) return hipSuccess;
@@ -677,7 +789,7 @@ hipError_t hj_launch_segment_sums(const uint32_t *sorted_slot, const uint64_t *s
 }
 
 __global__ __launch_bounds__(256) void hj_topk_keys_kernel(const double *sum_by_slot, const uint64_t *count_by_slot, uint64_t cap, uint64_t *keys,
-                                                            uint32_t *slots, unsigned long long *n_groups) {
+                                                            uint32_t *slots, unsigned long long *n_groups, uint32_t int_sums) {
   // 8 elements per thread, one atomic per workgroup: same-address atomics serialize at ~10 ns each, so a
   // per-wave atomic over millions of slots costs more than the rest of the kernel
   __shared__ uint32_t block_count;
@@ -693,9 +805,8 @@ __global__ __launch_bounds__(256) void hj_topk_keys_kernel(const double *sum_by_
     mine += has ? 1u : 0u;
     slots[i] = (uint32_t)i;
     if (!has) { keys[i] = ~0ull; continue; } // no group in this slot: sorts last
-    long long bits = __double_as_longlong(sum_by_slot[i]);
-    const uint64_t asc = bits < 0 ? ~(uint64_t)bits : ((uint64_t)bits | 0x8000000000000000ull); // ascending order key of an f64
-    keys[i] = ~asc == ~0ull ? ~asc - 1 : ~asc;                                                   // descending; never the sentinel
+    const uint64_t desc = desc_order_key(sum_by_slot[i], int_sums); // (declared with the top-k selection below)
+    keys[i] = desc == ~0ull ? desc - 1 : desc;                     // descending; never the sentinel
   }
   for (int o = 32; o; o >>= 1) mine += __shfl_xor(mine, o);
   if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&block_count, mine);
@@ -703,9 +814,9 @@ __global__ __launch_bounds__(256) void hj_topk_keys_kernel(const double *sum_by_
   if (threadIdx.x == 0 && block_count) atomicAdd(n_groups, (unsigned long long)block_count);
 }
 hipError_t hj_launch_topk_keys(const double *sum_by_slot, const uint64_t *count_by_slot, uint64_t cap, uint64_t *keys, uint32_t *slots,
-                               unsigned long long *n_groups, hipStream_t s) {
+                               unsigned long long *n_groups, hipStream_t s, bool int_sums) {
   if (cap == 0) return hipSuccess;
-  hipLaunchKernelGGL(hj_topk_keys_kernel, dim3((uint32_t)((cap + 2047) / 2048)), dim3(256), 0, s, sum_by_slot, count_by_slot, cap, keys, slots, n_groups);
+  hipLaunchKernelGGL(hj_topk_keys_kernel, dim3((uint32_t)((cap + 2047) / 2048)), dim3(256), 0, s, sum_by_slot, count_by_slot, cap, keys, slots, n_groups, int_sums ? 1u : 0u);
   return hipGetLastError();
 }
 
@@ -1108,6 +1219,13 @@ __device__ __forceinline__ uint64_t desc_order_key(double v) {
   const uint64_t asc = bits < 0 ? ~(uint64_t)bits : ((uint64_t)bits | 0x8000000000000000ull);
   return ~asc;
 }
+__device__ __forceinline__ uint64_t desc_order_key(long long v) { return ~((uint64_t)v ^ (1ull << 63)); } // an integer sum
+// … of a sum lane as the handle holds it: an f64, or (int_sums) the i64 in the same 8 bytes
+__device__ __forceinline__ uint64_t desc_order_key(double lane, uint32_t int_sums) { return int_sums ? desc_order_key(__double_as_longlong(lane)) : desc_order_key(lane); }
+// a candidate record's row count; exact sums typed by the group's first value carry that value's digits in the top byte (counts stay below 2^40)
+__device__ __forceinline__ uint64_t count_with_digits(const uint64_t *counts, const uint64_t *first, uint32_t g) {
+  return first ? counts[g] | ((~first[g] & 0xFFull) << 56) : counts[g];
+}
 // ---- top-k by selection in two launches (join.hpp: hj_launch_topk_select2) ---------------------------------------------
 // state words: [0] bound, [1] candidate counter (u32), [2] groups with rows, [3] / [4] workgroups done with launch 1 / 2
 // What a workgroup leaves for the last one travels as agent-scope atomic stores (they go to the point all XCDs share),
@@ -1294,7 +1412,7 @@ hipError_t hj_launch_boundary_runs(const uint32_t *group, const uint64_t *val, u
 }
 // Both launches: one 1024-thread workgroup per slice (as much in flight as 4× the workgroups, a quarter of the tickets).
 __global__ __launch_bounds__(1024) void hj_topk_bound_kernel(const double *sums, const uint64_t *counts, uint64_t n, uint64_t per, uint32_t want, uint64_t *best,
-                                                              uint64_t *state, const uint32_t *n_dev) {
+                                                              uint64_t *state, const uint32_t *n_dev, uint32_t int_sums) {
   __shared__ uint64_t wave_best[16];
   __shared__ uint32_t wave_count[16];
   __shared__ uint64_t v[kTopkSlices];
@@ -1316,7 +1434,7 @@ __global__ __launch_bounds__(1024) void hj_topk_bound_kernel(const double *sums,
     for (int u = 0; u < 4; ++u) {
       if (c[u] == 0) continue;
       ++have;
-      const uint64_t k = desc_order_key(x[u]);
+      const uint64_t k = desc_order_key(x[u], int_sums);
       mine = k < mine ? k : mine;
     }
   }
@@ -1365,7 +1483,7 @@ __global__ __launch_bounds__(1024) void hj_topk_bound_kernel(const double *sums,
 }
 __global__ __launch_bounds__(1024) void hj_topk_collect2_kernel(const double *sums, const uint64_t *counts, uint64_t n, uint64_t *state, uint32_t cap, uint32_t *groups,
                                                                 const uint64_t *dim_rows, CandidateCols cols, uint64_t *host_out, GatherItems extra, uint32_t *extra_host,
-                                                                const uint32_t *n_dev, const uint64_t *slice_best, uint32_t want_m1) {
+                                                                const uint32_t *n_dev, const uint64_t *slice_best, uint32_t want_m1, uint32_t int_sums, const uint64_t *first) {
   if (n_dev) n = *n_dev;
   __shared__ uint64_t sv[kTopkSlices];
   __shared__ uint64_t s_bound, s_total;
@@ -1416,7 +1534,7 @@ __global__ __launch_bounds__(1024) void hj_topk_collect2_kernel(const double *su
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      if (c[u] == 0 || desc_order_key(x[u]) > bound) continue;
+      if (c[u] == 0 || desc_order_key(x[u], int_sums) > bound) continue;
       const uint32_t at = atomicAdd(counter, 1u);
       if (at < cap) __hip_atomic_store(&groups[at], (uint32_t)(i0 + (uint64_t)u * 1024), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1433,7 +1551,7 @@ __global__ __launch_bounds__(1024) void hj_topk_collect2_kernel(const double *su
     to_host(&o[0], g);
     to_host(&o[1], (uint64_t)load_key(cols.key, owner));
     to_host(&o[2], (uint64_t)__double_as_longlong(sums[g]));
-    to_host(&o[3], counts[g]);
+    to_host(&o[3], count_with_digits(counts, first, g));
     for (uint32_t k = 0; k < 4; ++k) to_host(&o[4 + k], k < cols.n_payload ? (uint64_t)load_key(cols.payload[k], owner) : 0);
   }
   readback_gather(extra, extra_host);
@@ -1442,14 +1560,14 @@ __global__ __launch_bounds__(1024) void hj_topk_collect2_kernel(const double *su
 }
 hipError_t hj_launch_topk_select2(const double *sums, const uint64_t *counts, uint64_t n, uint32_t want, uint32_t cap, const uint64_t *dim_rows, CandidateCols cols,
                                   uint64_t *best, uint64_t *state, uint32_t *groups, uint64_t *host_out, const GatherItems &extra, uint32_t *extra_host,
-                                  hipStream_t s, const uint32_t *n_dev, const uint64_t *slice_best) {
+                                  hipStream_t s, const uint32_t *n_dev, const uint64_t *slice_best, bool int_sums, const uint64_t *first) {
   if (n == 0 || want == 0 || want > kTopkSlices) return hipErrorInvalidValue;
   const uint64_t per = (n + kTopkSlices - 1) / kTopkSlices;
   const uint32_t n_slices = n_dev ? kTopkSlices : (uint32_t)((n + per - 1) / per);
-  if (!slice_best) hipLaunchKernelGGL(hj_topk_bound_kernel, dim3(n_slices), dim3(1024), 0, s, sums, counts, n, per, want, best, state, n_dev);
+  if (!slice_best) hipLaunchKernelGGL(hj_topk_bound_kernel, dim3(n_slices), dim3(1024), 0, s, sums, counts, n, per, want, best, state, n_dev, int_sums ? 1u : 0u);
   const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 4095) / 4096, 256);
   hipLaunchKernelGGL(hj_topk_collect2_kernel, dim3(grid), dim3(1024), 0, s, sums, counts, n, state, cap, groups, dim_rows, cols, host_out, extra, extra_host, n_dev, slice_best,
-                     want - 1);
+                     want - 1, int_sums ? 1u : 0u, first);
   return hipGetLastError();
 }
 
@@ -1506,7 +1624,7 @@ hipError_t hj_launch_rank_words(const uint64_t *bits, uint64_t n_words, uint32_t
 
 __global__ __launch_bounds__(128) void hj_gather_group_candidates_kernel(const uint64_t *sorted_keys, const uint64_t *keys_by_group, const uint32_t *sorted_groups, uint32_t n,
                                                                          const uint64_t *dim_rows, const double *sum_by_group,
-                                                                         const uint64_t *count_by_group, CandidateCols cols, uint64_t *out) {
+                                                                         const uint64_t *count_by_group, CandidateCols cols, uint64_t *out, const uint64_t *first) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint64_t *o = out + (uint64_t)i * 8;
@@ -1517,15 +1635,15 @@ __global__ __launch_bounds__(128) void hj_gather_group_candidates_kernel(const u
   const uint64_t owner = group_owner_row(dim_rows, cols, g);
   o[1] = (uint64_t)load_key(cols.key, owner);
   o[2] = (uint64_t)__double_as_longlong(sum_by_group[g]);
-  o[3] = count_by_group[g];
+  o[3] = count_with_digits(count_by_group, first, g);
   for (uint32_t k = 0; k < 4; ++k) o[4 + k] = k < cols.n_payload ? (uint64_t)load_key(cols.payload[k], owner) : 0;
 }
 hipError_t hj_launch_gather_group_candidates(const uint64_t *sorted_keys, const uint64_t *keys_by_group, const uint32_t *sorted_groups, uint32_t n, const uint64_t *dim_rows,
                                              const double *sum_by_group, const uint64_t *count_by_group, CandidateCols cols, uint64_t *out,
-                                             hipStream_t s) {
+                                             hipStream_t s, const uint64_t *first) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(hj_gather_group_candidates_kernel, dim3((n + 127) / 128), dim3(128), 0, s, sorted_keys, keys_by_group, sorted_groups, n, dim_rows,
-                     sum_by_group, count_by_group, cols, out);
+                     sum_by_group, count_by_group, cols, out, first);
   return hipGetLastError();
 }
 

@@ -205,8 +205,25 @@ hipError_t hj_launch_run_sums_dev(const uint32_t *group, const uint64_t *val, co
                                   uint64_t *count_by_group, uint32_t *multi_run, hipStream_t s, uint32_t *descending = nullptr);
 hipError_t hj_launch_run_sums(const uint32_t *group, const uint64_t *val, uint64_t n, double *sum_by_group, uint64_t *count_by_group,
                               uint32_t *multi_run, hipStream_t s);
+// Exact integer sums (llkv_hip_join_groupby_topk_exact): the pairs' values are Int64 / raw decimal images, added in no particular
+// order with one atomic add per run of a group's pairs inside a chunk — all three arrays must start from zero.
+struct IntSumLanes {
+  unsigned long long *sum;   // per group: the i64 sum (wrapping; the lowering excluded overflow)
+  unsigned long long *count; // … its rows
+  unsigned long long *first; // optional: ~((position of the group's first pair << 8) | decimal digits of its value), 0 = no pair
+};
+// straight from the probe's stripes (flags[1]: predicate-error mark, flags[3]: pairs not in key order; rank / pos_out as above) …
+hipError_t hj_launch_int_sums_stripes(const uint32_t *stripe_group, const uint64_t *stripe_val, const uint64_t *counts, uint32_t n_slots, uint32_t stripe,
+                                      IntSumLanes out, uint32_t *flags, hipStream_t s, RankCols rank = RankCols{nullptr, nullptr, nullptr, 0});
+// … and over compacted pairs (group ids), the pair count still on the device
+hipError_t hj_launch_int_sums_pairs(const uint32_t *group, const uint64_t *val, const uint64_t *n_dev, uint64_t n_max, IntSumLanes out, hipStream_t s,
+                                    uint32_t *descending = nullptr);
+// *flag (zero before) = ~((group << 8) | digits) of the first group with rows whose first value has fewer digits than `scale`
+hipError_t hj_launch_first_digits_check(IntSumLanes lanes, uint64_t n, const uint32_t *n_dev /* optional: the group count on the device */, uint32_t scale,
+                                        uint64_t *flag, hipStream_t s);
+// `int_sums` (here and in the top-k selection): the sum lane holds i64 sums, ordered as integers
 hipError_t hj_launch_topk_keys(const double *sum_by_slot, const uint64_t *count_by_slot, uint64_t cap, uint64_t *keys, uint32_t *slots,
-                               unsigned long long *n_groups /* += groups */, hipStream_t s);
+                               unsigned long long *n_groups /* += groups */, hipStream_t s, bool int_sums = false);
 // One record per candidate slot: {sort key, dim key, sum bits, count, payload[4]} (8 × 8 bytes).
 struct CandidateCols {
   JoinKeyColumn key;
@@ -287,7 +304,8 @@ constexpr uint32_t kTopkSlices = 256;
 // `n_dev` (optional): the number of groups is still on the device (then `n` only bounds it).
 hipError_t hj_launch_topk_select2(const double *sums, const uint64_t *counts, uint64_t n, uint32_t want, uint32_t cap, const uint64_t *dim_rows, CandidateCols cols,
                                   uint64_t *best, uint64_t *state, uint32_t *groups /*[cap]*/, uint64_t *host_out, const GatherItems &extra, uint32_t *extra_host,
-                                  hipStream_t s, const uint32_t *n_dev = nullptr, const uint64_t *slice_best = nullptr /* filled by hj_launch_run_sums_stripes: no first launch */);
+                                  hipStream_t s, const uint32_t *n_dev = nullptr, const uint64_t *slice_best = nullptr /* filled by hj_launch_run_sums_stripes: no first launch */,
+                                  bool int_sums = false, const uint64_t *first = nullptr /* IntSumLanes::first: its digits ride in the top byte of a record's count */);
 hipError_t hj_launch_high_halves(const uint64_t *keys, uint64_t n, uint32_t *out, hipStream_t s);
 // Range form of a sharded fact table: the first and the last run of a pair stream with their key bits and raw values
 // (join.hip: hj_boundary_runs_kernel; out = 8 + 2 · cap words of device memory)
@@ -298,7 +316,7 @@ hipError_t hj_launch_boundary_runs_stripes(const uint32_t *stripe_group, const u
                                            CandidateCols cols, RankCols rank, uint64_t *out, hipStream_t s);
 hipError_t hj_launch_gather_group_candidates(const uint64_t *sorted_keys, const uint64_t *keys_by_group, const uint32_t *sorted_groups, uint32_t n, const uint64_t *dim_rows,
                                              const double *sum_by_group, const uint64_t *count_by_group, CandidateCols cols,
-                                             uint64_t *out /*[n][8]*/, hipStream_t s);
+                                             uint64_t *out /*[n][8]*/, hipStream_t s, const uint64_t *first = nullptr /* as in hj_launch_topk_select2 */);
 
 // ---- sort-based GROUP BY (group_sort.cpp): generic key handling -------------------------------------------
 // keys[i] = value − base (as u64) of column `col` at selected row perm[i]: order preserving when base is the

@@ -4,6 +4,8 @@
 //   dim  (orders)   filter ⋉ dim2 → hash table  select + semi flags + scan/compact + claim
 //   fact (lineitem) filter ⋈ dim → (group, value) pairs in scan order   probe-emit (count/scan/write)
 //   stable sort by group → per-group left-to-right f64 sums (the reference's order) → top-k
+// llkv_hip_join_groupby_topk_exact is the same pipeline over an Int64 / decimal argument (JoinAgg::int_sums): the pairs carry i64
+// values, the sums are order-free atomic adds (no run walk, no sort), the delivered cells are finalized as the GROUP BY's SUM cells.
 // Group id = position of the dim row in the qualifying-dim-row list (row order): the same on every rank that
 // holds the replicated dimension tables, unlike hash-table slots, whose assignment depends on CAS timing.
 //
@@ -115,8 +117,11 @@ struct DirectTable {
 
 // ORDER BY sum DESC, payload[0] ASC (arrow lexsort, llkv-executor/src/lib.rs:13847-13864); ties beyond that
 // are left in an unspecified order by the reference — here: dim row order, so every rank count agrees.
-bool row_before(const llkv_join_group_row &a, const llkv_join_group_row &b, uint32_t n_payload) {
-  if (a.sum != b.sum) return a.sum > b.sum;
+// `int_sums`: the rows of an exact handle carry the i64 sum in the 8 bytes of `sum`.
+int64_t sum_bits(const llkv_join_group_row &r) { int64_t v; std::memcpy(&v, &r.sum, 8); return v; }
+bool row_before(const llkv_join_group_row &a, const llkv_join_group_row &b, uint32_t n_payload, bool int_sums = false) {
+  if (int_sums) { if (sum_bits(a) != sum_bits(b)) return sum_bits(a) > sum_bits(b); }
+  else if (a.sum != b.sum) return a.sum > b.sum;
   if (n_payload && a.payload[0] != b.payload[0]) return a.payload[0] < b.payload[0];
   return a.group_index < b.group_index;
 }
@@ -134,6 +139,17 @@ struct JoinAgg {
   struct View { void *p = nullptr; };
   DB group_state;                    // one block, one memset:
   View sums, cnts, gcnts, report;    // per group: local f64 sum, local rows, exchanged rows (int64), rows this rank reports
+  // Integer sums (llkv_hip_join_groupby_topk_exact; one rank): `sums` holds i64 sums that atomic adds build in no particular order
+  // — sums, counts and the first-value lane (in the gcnts slot, which one rank does not use) all start from zero, no group has a
+  // "second run", nothing is ever sorted.  `value`: what the argument is and how SUM over it is typed (plan.hpp).
+  bool int_sums = false;
+  ProbeValue value;
+  bool typed_by_first() const { return int_sums && value.sum.digits_lane >= 0; }
+  IntSumLanes int_lanes() const { return IntSumLanes{(unsigned long long *)sums.p, (unsigned long long *)cnts.p, typed_by_first() ? (unsigned long long *)gcnts.p : nullptr}; }
+  const uint64_t *first_lane() const { return typed_by_first() ? (const uint64_t *)gcnts.p : nullptr; }
+  uint64_t *digits_flag() const { return static_cast<uint64_t *>(zeros.p) + 24; } // (a free word of the zeroed block)
+  uint64_t digits_err = 0;           // ~((group << 8) | digits): a group's first value has fewer digits than the scale
+  int finalize_row(const llkv_join_group_row &r, llkv_join_group_exact_row *out) const;
   DB s_group, s_val;                 // local (group, value) pairs sorted by group, row order within a group
   DB e_group, e_val;                 // … as emitted (row order), until settle() has looked at the run flag
   uint64_t n_pairs = 0;
@@ -259,6 +275,12 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
   if (td->world != 1 || (t2 && t2->world != 1))
     return set_error(LLKV_INVALID_ARGUMENT, "dimension tables are replicated: stage them whole (world = 1) on every rank; only the fact table is sharded");
   n_payload = n_payload_;
+  if (int_sums) { // what the call refuses does not depend on the dimension side: lowered once up front, over the table as staged
+    if (tf->world != 1) return set_error(LLKV_UNSUPPORTED, "integer sums in the join-aggregate pipeline take an unsharded fact table (world = 1)");
+    LoweredPlan ignore;
+    std::string why;
+    if ((rc = lower_probe(table_resolver(*tf), fact->filters, fact->n_filters, fact->key_field, sum_expr, sum_expr_len, &ignore, &why, false, true, &value))) return set_error(rc, why);
+  }
   epochs.add(tf, "fact ");
   epochs.add(td, "dimension ");
   epochs.add(t2, "second dimension ");
@@ -451,8 +473,10 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
   gcnts.p = (char *)group_state.p + 2 * state_bytes;
   report.p = (char *)group_state.p + 3 * state_bytes;
   // one rank: only the row counts start from zero (a sum is read only where the count is not zero)
+  // (integer sums are accumulated, not stored: counts, sums and the first-value lane)
+  const uint32_t zeroed_arrays = tf->world == 1 && !int_sums ? 1 : 3;
   if (ranked) {
-  } else if (tf->world == 1) HIP_TRY(hj_launch_fill(cnts.p, state_bytes, 0, s));
+  } else if (zeroed_arrays == 1) HIP_TRY(hj_launch_fill(cnts.p, state_bytes, 0, s));
   else HIP_TRY(hj_launch_fill(group_state.p, 3 * state_bytes, 0, s));
 
   // ---- dim hash table, slot → group id -----------------------------------------------------
@@ -516,11 +540,11 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
   if (ranked && (rc = img_f.add(fact->key_field, fact->filters, fact->n_filters, sum_expr, sum_expr_len))) return rc;
   auto resolve = [&](uint32_t fid) -> const ColumnInfo * { return img_f.resolve(fid); };
   LoweredPlan plan;
-  if ((rc = lower_probe(resolve, fact->filters, fact->n_filters, fact->key_field, sum_expr, sum_expr_len, &plan, &err, keybit_stripes))) return set_error(rc, err);
+  if ((rc = lower_probe(resolve, fact->filters, fact->n_filters, fact->key_field, sum_expr, sum_expr_len, &plan, &err, keybit_stripes, int_sums))) return set_error(rc, err);
   if (plan.always_false || tf->local_rows == 0) {
     if (ranked) { // nothing probes: the group state still starts from zero, and the group count is wanted
       if (rank_in_probe) HIP_TRY(hj_launch_rank_words((const uint64_t *)dt.bits.p, dt.n_words, rank_shift, (uint32_t *)dt.prefix.p, (uint32_t *)rank_base.p, multi_p() + 2, s));
-      HIP_TRY(hj_launch_fill(group_state.p, (tf->world == 1 ? 1 : 3) * state_bytes, 0, s));
+      HIP_TRY(hj_launch_fill(group_state.p, zeroed_arrays * state_bytes, 0, s));
       if ((rc = rb.add(&n_dim_dev, n_dim_ptr(), 4, s)) || (rc = rb.wait())) return rc;
       n_dim = n_dim_dev;
     }
@@ -558,7 +582,7 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
         stripe_ranks.pos_out = (uint32_t *)((char *)group_state.p + 4 * state_bytes);
         cc.pos_by_group = stripe_ranks.pos_out;
       }
-      p.zero_k = tf->world == 1 ? 1 : 3;
+      p.zero_k = zeroed_arrays;
       p.zero_words = (uint64_t *)group_state.p;
       p.zero_stride = state_bytes / 8;
       p.zero_n = n_dim_ptr();
@@ -597,11 +621,18 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
   // pairs themselves later (the sort, a sharded fact table's straddlers) compacts them then.
   from_stripes = stripes_ok;
   const RankCols stripe_rank_cols = keybit_stripes ? stripe_ranks : RankCols{nullptr, nullptr, nullptr, 0};
-  if (from_stripes) {
+  if (from_stripes && int_sums) {
+    HIP_TRY(hj_launch_int_sums_stripes((const uint32_t *)st_slot.p, (const uint64_t *)st_val.p, (const uint64_t *)counts.p, n_slots, stripe, int_lanes(), multi_p(), s, stripe_rank_cols));
+  } else if (from_stripes) {
     HIP_TRY(hj_launch_run_sums_stripes((const uint32_t *)st_slot.p, (const uint64_t *)st_val.p, (const uint64_t *)counts.p, n_slots, stripe, (double *)sums.p,
                                        (uint64_t *)cnts.p, multi_p(), s, stripe_rank_cols, slice_best(), range_form ? total_pairs_p() : nullptr));
   } else if ((rc = compact_pairs(true))) {
     return rc;
+  }
+  // a computed decimal argument: some group's first value with fewer digits than the scale fails the query — looked for over all groups
+  if (typed_by_first() && value.sum.scale > 0) {
+    HIP_TRY(hj_launch_first_digits_check(int_lanes(), n_dim, ranked ? n_dim_ptr() : nullptr, (uint32_t)value.sum.scale, digits_flag(), s));
+    if ((rc = rb.add(&digits_err, digits_flag(), 8, s))) return rc;
   }
   if (range_form) { // the boundary runs of the pair stream, while the pair count is still on its way to the host
     boundary_raw.assign(8 + 2 * kBoundaryCap, 0);
@@ -647,7 +678,9 @@ int JoinAgg::compact_pairs(bool run_sums) {
   HIP_TRY(hj_launch_compact_stripes((const uint32_t *)st_slot.p, (const uint64_t *)st_val.p, (const uint64_t *)counts.p, (const uint64_t *)offsets.p, n_slots, stripe,
                                     direct_form ? nullptr : (const uint32_t *)slot_group.p, (uint32_t *)e_group.p, (uint64_t *)e_val.p, s, // slot / key bit → group id on the way
                                     keybit_stripes ? stripe_ranks : RankCols{nullptr, nullptr, nullptr, 0}));
-  if (run_sums)
+  if (run_sums && int_sums)
+    HIP_TRY(hj_launch_int_sums_pairs((const uint32_t *)e_group.p, (const uint64_t *)e_val.p, (const uint64_t *)offsets.p + n_slots, max_pairs, int_lanes(), s));
+  else if (run_sums)
     HIP_TRY(hj_launch_run_sums_dev((const uint32_t *)e_group.p, (const uint64_t *)e_val.p, (const uint64_t *)offsets.p + n_slots, max_pairs, (double *)sums.p,
                                    (uint64_t *)cnts.p, multi_p(), s, range_form ? multi_p() + 3 : nullptr));
   return LLKV_OK;
@@ -666,6 +699,14 @@ int JoinAgg::settle(bool delivered) {
   if (key_err || pred_err || dim_err) { n_pairs = 0; return set_error(LLKV_INTERNAL, "Arithmetic overflow: Overflow happened in a comparison"); }
   if (ranked) n_dim = n_dim_dev; // the bound that sized the group state → the number of groups
   if (dup_keys) { n_pairs = 0; return set_error(LLKV_UNSUPPORTED, "dimension key is not unique: groups are not identified by the dim row"); }
+  if (int_sums) { // order-free sums: final as they are, whatever the runs (nothing to sort, LLKV_HIP_JOIN_SORT or not)
+    if (!from_stripes && n_pairs >= kPredErrorBit) { n_pairs = 0; return set_error(LLKV_INTERNAL, "Arithmetic overflow: Overflow happened in a comparison"); }
+    if (digits_err) {
+      n_pairs = 0; // (finalize_value's refusal of such a group, as the general route reports it)
+      return set_error(LLKV_INVALID_ARGUMENT, "invalid Decimal128 precision/scale: scale " + std::to_string(value.sum.scale) + " is greater than precision " + std::to_string(~digits_err & 0xFFull));
+    }
+    return LLKV_OK;
+  }
   if (from_stripes) {
     if (!multi_run && !std::getenv("LLKV_HIP_JOIN_SORT")) return LLKV_OK; // sums and counts are final; nobody asked for the pairs
     // the sort needs the pairs: compact them now, and their number
@@ -780,14 +821,14 @@ int JoinAgg::candidates(const uint32_t *f_groups, const double *f_sums, const ui
     if ((rc = rb.reserve(nullptr, 64 + (size_t)kCap * 64, s, &slab)) || (rc = rb.take(&extra, &slab_base))) return rc;
     // (sums straight from the stripes, nothing patched in: the first launch's slice winners came with the run sums — if some
     // group turns out to have had two runs, everything is redone below)
-    const bool winners_known = from_stripes && alone && mg.empty() && !sums_patched && (pending || !multi_run) && !std::getenv("LLKV_HIP_TOPK_TWO_LAUNCHES");
+    const bool winners_known = !int_sums && from_stripes && alone && mg.empty() && !sums_patched && (pending || !multi_run) && !std::getenv("LLKV_HIP_TOPK_TWO_LAUNCHES");
     HIP_TRY(hj_launch_topk_select2((const double *)sums.p, report_p, n_dim, std::max(1u, limit), kCap, d_dim_rows, cc, (uint64_t *)best.p, topk_state(),
                                    (uint32_t *)groups_d.p, (uint64_t *)slab, extra, slab_base, s, ranked && pending ? n_dim_ptr() : nullptr,
-                                   winners_known ? slice_best() : nullptr));
+                                   winners_known ? slice_best() : nullptr, int_sums, first_lane()));
     if ((rc = rb.wait())) return rc;
     if (pending) {
       if ((rc = settle(true))) return rc;
-      if (multi_run || std::getenv("LLKV_HIP_JOIN_SORT")) // the sums were made again: select again
+      if (!int_sums && (multi_run || std::getenv("LLKV_HIP_JOIN_SORT"))) // the sums were made again: select again
         return candidates(f_groups, f_sums, f_counts, f_first_rank, n_folded, rank, limit, out_rows, out_n, out_groups);
     }
     const uint64_t *head = static_cast<const uint64_t *>(slab);
@@ -803,7 +844,8 @@ int JoinAgg::candidates(const uint32_t *f_groups, const double *f_sums, const ui
         g.count = c[3];
         for (int k = 0; k < 4; ++k) g.payload[k] = (int64_t)c[4 + k];
       }
-      std::sort(cand.begin(), cand.end(), [np](const llkv_join_group_row &a, const llkv_join_group_row &b) { return row_before(a, b, np); });
+      const bool ints = int_sums;
+      std::sort(cand.begin(), cand.end(), [np, ints](const llkv_join_group_row &a, const llkv_join_group_row &b) { return row_before(a, b, np, ints); });
       const uint32_t n = std::min<uint32_t>(limit, n_sel);
       for (uint32_t i = 0; i < n; ++i) out_rows[i] = cand[i];
       *out_n = n;
@@ -817,7 +859,7 @@ int JoinAgg::candidates(const uint32_t *f_groups, const double *f_sums, const ui
     return rc;
   HIP_TRY(hipMemsetAsync(n_groups_d.p, 0, 8, s));
   HIP_TRY(hj_launch_topk_keys((const double *)sums.p, report_p, n_dim, (uint64_t *)tk_keys.p, (uint32_t *)tk_groups.p,
-                              (unsigned long long *)n_groups_d.p, s));
+                              (unsigned long long *)n_groups_d.p, s, int_sums));
   // ---- candidates → host: the first (limit + slack) groups by descending sum ------------------------------------
   // The top groups are decided by the high half of the order key almost always: sort on bits 32..63 first (half
   // the radix passes) and fall back to all 64 bits only when the cut falls inside a run of equal high halves.
@@ -845,7 +887,7 @@ int JoinAgg::candidates(const uint32_t *f_groups, const double *f_sums, const ui
       HIP_TRY(hj_sort_u64_u32(tmp.p, &tb, (const uint64_t *)tk_keys.p, (uint64_t *)tk_keys_s.p, (const uint32_t *)tk_groups.p, (uint32_t *)tk_groups_s.p, n_dim, s));
     }
     HIP_TRY(hj_launch_gather_group_candidates(pass == 0 ? nullptr : (const uint64_t *)tk_keys_s.p, (const uint64_t *)tk_keys.p, (const uint32_t *)tk_groups_s.p, want,
-                                              d_dim_rows, (const double *)sums.p, report_p, cc, (uint64_t *)cand_d.p, s));
+                                              d_dim_rows, (const double *)sums.p, report_p, cc, (uint64_t *)cand_d.p, s, first_lane()));
     HIP_TRY(hipMemcpyAsync(hc.data(), cand_d.p, (size_t)want * 64, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(hg.data(), tk_groups_s.p, (size_t)want * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&n_groups, n_groups_d.p, 8, hipMemcpyDeviceToHost, s));
@@ -872,11 +914,36 @@ int JoinAgg::candidates(const uint32_t *f_groups, const double *f_sums, const ui
     for (int k = 0; k < 4; ++k) g.payload[k] = (int64_t)c[4 + k];
     g.group_index = hg[i];
   }
-  std::sort(cand.begin(), cand.end(), [np](const llkv_join_group_row &a, const llkv_join_group_row &b) { return row_before(a, b, np); });
+  const bool ints = int_sums;
+  std::sort(cand.begin(), cand.end(), [np, ints](const llkv_join_group_row &a, const llkv_join_group_row &b) { return row_before(a, b, np, ints); });
   const uint32_t n = std::min<uint32_t>(limit, n_cand);
   for (uint32_t i = 0; i < n; ++i) out_rows[i] = cand[i];
   *out_n = n;
   if (out_groups) *out_groups = n_groups;
+  return LLKV_OK;
+}
+
+// A delivered row of an exact handle → the caller's row: the cell through finalize_value over the lane block the GROUP BY
+// lowering's SUM(argument) reads ([rows][first row][aggregate lanes…], plan.hpp: ProbeValue) — the i64 sum spelled in the lanes of
+// whichever integer-sum form it chose, the first value's digits (the top byte of the record's count) in its digits lane.
+int JoinAgg::finalize_row(const llkv_join_group_row &r, llkv_join_group_exact_row *out) const {
+  const AggOut &a = value.sum;
+  const int64_t sum = sum_bits(r);
+  std::vector<uint64_t> g((size_t)std::max(value.k, 8), 0);
+  g[0] = r.count & ((1ull << 56) - 1);
+  const bool one_lane = a.fin == AggFinal::SumI64Fast || (a.fin == AggFinal::SumDec && a.fast_sum);
+  if (a.lane < 0 || (a.fin != AggFinal::SumI64 && a.fin != AggFinal::SumI64Fast && a.fin != AggFinal::SumDec) || a.wide)
+    return set_error(LLKV_INTERNAL, "exact join-aggregate: SUM over the argument is not an integer-sum form");
+  if (one_lane) g[2 + a.lane] = (uint64_t)sum;
+  else { g[2 + a.lane] = (uint64_t)sum & 0xFFFFFFFFull; g[2 + a.lane + 1] = (uint64_t)(sum >> 32); g[2 + a.lane + 2] = 0; } // (low 32 bits, high part; prefixes: excluded by the lowering)
+  if (a.digits_lane >= 0) g[2 + a.digits_lane] = (r.count >> 56) << a.digits_shift;
+  std::string err;
+  std::memset(out, 0, sizeof *out);
+  if (const int rc = finalize_value(a, g.data(), 2, &out->sum, &err, true)) return set_error(rc, err);
+  out->key = r.key;
+  out->count = g[0];
+  for (int k = 0; k < 4; ++k) out->payload[k] = r.payload[k];
+  out->group_index = r.group_index;
   return LLKV_OK;
 }
 
@@ -1197,6 +1264,28 @@ llkv_status llkv_hip_join_groupby_topk(const llkv_join_side *fact, const llkv_jo
   int rc = j.prepare(fact, dim, dim_fk_field, dim2, payload_fields, n_payload, sum_expr, sum_expr_len, true);
   if (rc) return (llkv_status)rc;
   return (llkv_status)j.candidates(nullptr, nullptr, nullptr, nullptr, 0, 0, limit, out_rows, out_n, out_total_groups);
+}
+
+// … with exact integer / decimal sums: the same prepare → candidates over i64 sum lanes, the delivered rows finalized as the
+// general route's SUM cells.
+llkv_status llkv_hip_join_groupby_topk_exact(const llkv_join_side *fact, const llkv_join_side *dim, uint32_t dim_fk_field,
+                                             const llkv_join_side *dim2, const uint32_t *payload_fields, uint32_t n_payload,
+                                             const llkv_expr_token *sum_expr, uint32_t sum_expr_len, uint32_t limit,
+                                             llkv_join_group_exact_row *out_rows, uint32_t *out_n, uint64_t *out_total_groups) {
+  if (!out_rows || !out_n) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "NULL argument");
+  JoinAgg j;
+  j.int_sums = true;
+  int rc = j.prepare(fact, dim, dim_fk_field, dim2, payload_fields, n_payload, sum_expr, sum_expr_len, true);
+  if (rc) return (llkv_status)rc;
+  std::vector<llkv_join_group_row> rows(std::max(1u, limit));
+  uint32_t n = 0;
+  *out_n = 0;
+  if ((rc = j.candidates(nullptr, nullptr, nullptr, nullptr, 0, 0, limit, rows.data(), &n, out_total_groups))) return (llkv_status)rc;
+  if (j.pending && (rc = j.settle())) return (llkv_status)rc; // (the paths of candidates() that read nothing back: no group, …)
+  for (uint32_t i = 0; i < n; ++i)
+    if ((rc = j.finalize_row(rows[i], &out_rows[i]))) return (llkv_status)rc;
+  *out_n = n;
+  return LLKV_OK;
 }
 
 } // extern "C"

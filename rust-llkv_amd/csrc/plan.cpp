@@ -2274,7 +2274,8 @@ int lower_emit(const ColumnResolver &resolve, const llkv_filter *filters, uint32
 }
 
 int lower_probe(const ColumnResolver &resolve, const llkv_filter *filters, uint32_t n_filters, uint32_t key_field,
-                const llkv_expr_token *expr, uint32_t expr_len, LoweredPlan *out, std::string *err, bool emit_keybit) {
+                const llkv_expr_token *expr, uint32_t expr_len, LoweredPlan *out, std::string *err, bool emit_keybit, bool exact,
+                ProbeValue *value) {
   *out = LoweredPlan{};
   Lowering L{resolve, *out, err, true};
   std::string pred, key;
@@ -2292,7 +2293,38 @@ int lower_probe(const ColumnResolver &resolve, const llkv_filter *filters, uint3
   const size_t early = out->slot_fields.size(); // the slots so far feed the predicate and the key; what the value adds is read late
   Lowered val;
   if ((rc = L.expr_planvalue(expr, expr_len, &val))) return rc;
-  if (!val.is_f64) return L.fail(LLKV_UNSUPPORTED, "integer SUM in the join-aggregate pipeline");
+  if (!val.is_f64 && !exact) return L.fail(LLKV_UNSUPPORTED, "integer SUM in the join-aggregate pipeline");
+  if (val.is_f64 && exact) return L.fail(LLKV_UNSUPPORTED, "Float64 SUM in the exact join-aggregate pipeline: llkv_hip_join_groupby_topk sums Float64 arguments (in row order)");
+  ProbeValue pv;
+  pv.is_f64 = val.is_f64;
+  pv.is_decimal = val.pv.is_decimal;
+  pv.scale = val.pv.scale;
+  pv.bounded = val.pv.bounded;
+  pv.lo = val.pv.iv.lo;
+  pv.hi = val.pv.iv.hi;
+  pv.rows = ci->rows;
+  for (uint32_t i = 0; i < expr_len; ++i)
+    if (expr[i].kind == LLKV_TOK_COLUMN) pv.rows = std::max(pv.rows, resolve(expr[i].field_id)->rows); // (expr_planvalue resolved them all)
+  if (exact) {
+    // integer sums are atomic adds in no particular order: only when no partial sum can leave i64 (AggLowering::decimal64 `fast_sum`)
+    for (uint32_t i = 0; i < expr_len; ++i)
+      if (expr[i].kind == LLKV_TOK_COLUMN && resolve(expr[i].field_id)->wide128)
+        return L.fail(LLKV_UNSUPPORTED, "Decimal128 values beyond 64 bits in the exact join-aggregate pipeline");
+    if (!pv.bounded) return L.fail(LLKV_UNSUPPORTED, "the column statistics do not bound the SUM argument: possible i64 overflow of an integer sum in the exact join-aggregate pipeline");
+    if ((u128)val.pv.iv.mag() * (u128)pv.rows > (u128)INT64_MAX)
+      return L.fail(LLKV_UNSUPPORTED, "possible i64 overflow of an integer sum in the exact join-aggregate pipeline (rows · max|v| exceeds i64)");
+    // the cell's type: SUM(argument) as the GROUP BY lowering types it — one copy of that rule
+    llkv_aggregate_spec spec;
+    std::memset(&spec, 0, sizeof spec);
+    spec.kind = LLKV_AGG_SUM;
+    spec.expr = expr;
+    spec.expr_len = expr_len;
+    LoweredPlan reduce;
+    if ((rc = lower_reduce(resolve, &spec, 1, &reduce, err))) return rc;
+    pv.sum = reduce.aggs[0];
+    pv.k = reduce.k;
+  }
+  if (value) *value = pv;
   const bool late = early < out->slot_fields.size() && !std::getenv("LLKV_HIP_JOIN_NO_LATE");
   // (the direct-table probe of a plan with KEYBIT = 1 emits the key's bit position instead of its rank: join_agg.cpp)
   const std::string tail = emit_keybit ? "," + std::to_string(late ? early : out->slot_fields.size()) + ",1" : late ? "," + std::to_string(early) : "";

@@ -190,9 +190,25 @@ int lower_projection(const ColumnResolver &resolve, const llkv_projection *proje
                      LoweredPlan *out, std::string *err, bool pad_rows = false);
 
 // Fact side of a join → aggregate pipeline → "ProbePlan<Cols<…>,pred,KeyExpr,ValExpr>" (select.hip.h).
-// The aggregate argument follows the GROUP BY (PlanValue) semantics and must be Float64.
+// The aggregate argument follows the GROUP BY (PlanValue) semantics.  Without `exact` it must be Float64 (the row-order f64
+// sums of llkv_hip_join_groupby_topk); with it an Int64 or decimal value whose statistics exclude i64 overflow of any partial
+// sum (rows · max|v| ≤ i64::MAX, the rule of the GROUP BY lowering's one-lane sums): the order-free integer sums of
+// llkv_hip_join_groupby_topk_exact.  `value`, when given, reports what the argument is.
+struct ProbeValue {
+  bool is_f64 = false;
+  bool is_decimal = false;          // a decimal value (a bare Decimal128 column or decimal arithmetic): raw 64-bit images
+  int32_t scale = 0;
+  bool bounded = false;             // the interval below holds for every row (column statistics through interval arithmetic)
+  __int128 lo = 0, hi = 0;
+  uint64_t rows = 0;                // most rows the argument can take (the table's)
+  // SUM(argument) as the GROUP BY lowering types it (lower_reduce): what finalize_value needs, over a lane block of `k` lanes
+  // per group laid out [rows][first row][aggregate lanes…] (base 2).  Filled for integer / decimal values only.
+  AggOut sum{AggFinal::CountRows, -1};
+  int k = 0;
+};
 int lower_probe(const ColumnResolver &resolve, const llkv_filter *filters, uint32_t n_filters, uint32_t key_field,
-                const llkv_expr_token *expr, uint32_t expr_len, LoweredPlan *out, std::string *err, bool emit_keybit = false);
+                const llkv_expr_token *expr, uint32_t expr_len, LoweredPlan *out, std::string *err, bool emit_keybit = false,
+                bool exact = false, ProbeValue *value = nullptr);
 
 // Selected argument values in row order → "EmitPlan<Cols<…>,pred,ValExpr>" (exact SUM(Int64) overflow check).
 // `allow_f64`: Float64 arguments are emitted as bit images (DISTINCT aggregates); *is_f64 reports the type.

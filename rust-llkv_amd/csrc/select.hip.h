@@ -234,6 +234,12 @@ __device__ __forceinline__ void probe_zero_slices(const ScanParams &p) {
 #ifndef LLKV_PROBE_LEAN
 #define LLKV_PROBE_LEAN 1 // (0: the general loop for every probe form — A/B, profiles/r04/q3_probe_lean.txt)
 #endif
+// What a joining row leaves in its stripe: the bit image of an f64 value, or the value itself when the plan's argument is an
+// Int64 / decimal expression (the exact sums of llkv_hip_join_groupby_topk_exact add the integers as they are).
+template <class P, class C> __device__ __forceinline__ uint64_t probe_value(C &c, int parity) {
+  if constexpr (P::ValE::Type::is_float) return (uint64_t)__double_as_longlong((double)P::ValE::eval(c, parity));
+  else return (uint64_t)(int64_t)P::ValE::eval(c, parity);
+}
 template <class P, bool DIRECT> __device__ __forceinline__ void probe_emit_body(const ScanParams &p) {
   const TileDesc td = p.tiles[blockIdx.x];
   if (p.rk_chunks) { // (uniform) piggy-backed: the word ranks of the dimension bitmap, chunk by chunk
@@ -282,7 +288,7 @@ template <class P, bool DIRECT> __device__ __forceinline__ void probe_emit_body(
         Loaded lv;
         load_range<typename P::ColList, 0, P::ColList::N>(p, td.dev_row + (row & ~1u), lv);
         Ctx c{p, lv, 0u, td.logical_row + row};
-        p.aux_out[base0 + at] = (uint64_t)__double_as_longlong((double)P::ValE::eval(c, (int)(row & 1u)));
+        p.aux_out[base0 + at] = probe_value<P>(c, (int)(row & 1u));
       }
       __builtin_amdgcn_wave_barrier(); // the queue is refilled next
       queued = 0;
@@ -367,7 +373,7 @@ template <class P, bool DIRECT> __device__ __forceinline__ void probe_emit_body(
                 load_range<typename P::ColList, 0, P::ColList::N>(p, td.dev_row + ((row + j) & ~1u), lv);
                 Ctx c{p, lv, 0u, td.logical_row + row + j};
                 p.aux_out32[base0 + at + off] = d32[u * R + j];
-                p.aux_out[base0 + at + off] = (uint64_t)__double_as_longlong((double)P::ValE::eval(c, (int)((row + j) & 1u)));
+                p.aux_out[base0 + at + off] = probe_value<P>(c, (int)((row + j) & 1u));
                 ++off;
               }
           } else {
@@ -411,7 +417,7 @@ template <class P, bool DIRECT> __device__ __forceinline__ void probe_emit_body(
         perr |= row < sub1 ? c.perr : 0u;
         d[e] = (uint64_t)(long long)P::KeyE::eval(c, e & 1) - (uint64_t)p.bm_min; // k < min wraps to a huge value
         f[e] = pass && d[e] <= p.bm_span;
-        if constexpr (!LATE) val[e] = (uint64_t)__double_as_longlong((double)P::ValE::eval(c, e & 1));
+        if constexpr (!LATE) val[e] = probe_value<P>(c, e & 1);
       }
 #pragma unroll
       for (int e = 0; e < kE; ++e) w[e] = p.bm_bits[f[e] ? d[e] >> 6 : 0];
@@ -455,7 +461,7 @@ template <class P, bool DIRECT> __device__ __forceinline__ void probe_emit_body(
         perr |= row < sub1 ? c.perr : 0u;
         hit[e] = pass ? ht_find(p, (long long)P::KeyE::eval(c, e & 1)) : 0xFFFFFFFFu; // probe only for surviving rows
         f[e] = hit[e] != 0xFFFFFFFFu;
-        if constexpr (!LATE) val[e] = (uint64_t)__double_as_longlong((double)P::ValE::eval(c, e & 1));
+        if constexpr (!LATE) val[e] = probe_value<P>(c, e & 1);
       }
     }
     if constexpr (LATE) { // the value columns of the pairs that hold a joining row, then the values
@@ -465,7 +471,7 @@ template <class P, bool DIRECT> __device__ __forceinline__ void probe_emit_body(
 #pragma unroll
       for (int e = 0; e < kE; ++e) {
         Ctx c{p, lds[e >> 1], 0u, td.logical_row + r0 + (e >> 1) * 128 + lane * 2 + (e & 1)};
-        val[e] = (uint64_t)__double_as_longlong((double)P::ValE::eval(c, e & 1));
+        val[e] = probe_value<P>(c, e & 1);
       }
     }
 #pragma unroll

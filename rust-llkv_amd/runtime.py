@@ -981,6 +981,31 @@ def join_groupby_topk(fact: HipTable, fact_filters, fact_key: int, dim: HipTable
     return JoinTopk(fact, fact_filters, fact_key, dim, dim_filters, dim_key, sum_expr, payload_fields, limit, dim_fk, dim2, dim2_filters, dim2_key).run()
 
 
+class JoinTopkExact(JoinTopk):
+    """The arguments of llkv_hip_join_groupby_topk_exact (an Int64 or decimal SUM argument, exact cells), marshalled once."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._rows = (abi.CJoinGroupExactRow * max(1, self._limit))()
+        self._fn = lib().llkv_hip_join_groupby_topk_exact
+
+    def run(self):
+        n, total = C.c_uint32(), C.c_uint64()
+        check(self._fn(C.byref(self._f), C.byref(self._d), C.c_uint32(self._dim_fk), C.byref(self._d2) if self._d2 is not None else None, self._pay,
+                       C.c_uint32(self._n_payload), self._toks, C.c_uint32(self._n_toks), C.c_uint32(self._limit), self._rows, C.byref(n), C.byref(total)))
+        out = [(r.key, Value.from_c(r.sum), r.count) + tuple(r.payload[i] for i in range(self._n_payload)) for r in self._rows[:n.value]]
+        return out, total.value
+
+
+def join_groupby_topk_exact(fact: HipTable, fact_filters, fact_key: int, dim: HipTable, dim_filters, dim_key: int, sum_expr,
+                            payload_fields: Sequence[int] = (), limit: int = 10, dim_fk: int = 0, dim2: Optional[HipTable] = None,
+                            dim2_filters=(), dim2_key: int = 0):
+    """join_groupby_topk for an Int64 or decimal ``sum_expr`` (llkv_hip_join_groupby_topk_exact): the sums are exact and come
+    back as the cells SUM(expr) has on the general route (JoinGroupBy) — Int64, or Decimal128 with its precision and scale.
+    Returns (rows, total_groups); rows = (key, Value, count, payload...)."""
+    return JoinTopkExact(fact, fact_filters, fact_key, dim, dim_filters, dim_key, sum_expr, payload_fields, limit, dim_fk, dim2, dim2_filters, dim2_key).run()
+
+
 class JoinRow:
     """One result row of a join → GROUP BY: the group key (dim.key), the payload cells (None = NULL), the aggregates' finalized
     cells and the dimension row's position among the qualifying rows (the last tie-break of the order)."""
@@ -1185,3 +1210,20 @@ def lower_plan(column_descs, predicate, aggs: Sequence[AggregateSpec], keys: Seq
     if rc != 0:
         raise LlkvError(rc, L.llkv_plan_last_error().decode(errors="replace"))
     return buf.value.decode(), lanes.value, bpr.value
+
+
+def lower_probe(column_descs, filters, key_field: int, sum_expr, exact: bool = False, keybit: bool = False, plan_lib=None):
+    """llkv_plan_lower_probe (host only): the fact side of the join → GROUP BY → top-k calls as their prepare lowers it.
+    Returns (type_string, abi.CProbeValueInfo) or raises LlkvError."""
+    L = plan_lib or lib()
+    L.llkv_plan_last_error.restype = C.c_char_p
+    p = CPlan(list(filters or []))
+    keep = []
+    toks = sum_expr.to_c(keep)
+    buf = C.create_string_buffer(16384)
+    info = abi.CProbeValueInfo()
+    rc = L.llkv_plan_lower_probe(column_descs, C.c_uint32(len(column_descs)), p.filters, p.n_filters, C.c_uint32(key_field), toks, C.c_uint32(len(sum_expr.tokens)),
+                                 C.c_int32((1 if exact else 0) | (2 if keybit else 0)), buf, C.c_uint64(len(buf)), C.byref(info))
+    if rc != 0:
+        raise LlkvError(rc, L.llkv_plan_last_error().decode(errors="replace"))
+    return buf.value.decode(), info

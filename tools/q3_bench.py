@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """TPC-H Q3 shape at SF10 on one GPU (BASELINE.json configs[4], single-GPU form): time of
-llkv_hip_join_groupby_topk with all inputs resident in HBM; algorithmic bytes per SURVEY.md §8(d)."""
+llkv_hip_join_groupby_topk with all inputs resident in HBM; algorithmic bytes per SURVEY.md §8(d).
+Options: --general (the general join → GROUP BY route over the same star), --decimal (the money columns as DECIMAL(15,2):
+llkv_hip_join_groupby_topk_exact and the general route over them), --sharded (configs[4] emulated on one device)."""
 import importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -57,6 +59,45 @@ if "--general" in sys.argv:
         res["general"][name] = {"groups": total_, "seconds_prepare_and_run_best": min(cold), "seconds_prepared_run_best": min(warm),
                                 "top_keys": [r.key for r in rows_[:3]], "same_top_keys_as_the_q3_pipeline": [r.key for r in rows_] == [o[0] for o in out]}
         jq.close()
+# ---- Q3 over the reference's own DDL: the money columns as DECIMAL(15,2) (tpch.lineitem_as_decimal).  The exact call
+# (llkv_hip_join_groupby_topk_exact: integer sums of the scale-4 products, every cell bit-equal to the general route's) and, for
+# comparison, the general route those queries took before it (a sort-based GROUP BY of the fact key plus host ordering).
+if "--decimal" in sys.argv:
+    A = abi.AggregateSpec
+    lid = tpch.lineitem_as_decimal(li)
+    ltd = rt.HipTable(4, tpch.chunk_rows(rows))
+    for c in lid:
+        fid, dt = tpch.LINEITEM_SCHEMA[c][0], tpch.lineitem_dtype(c, True)
+        if dt == abi.DT_DECIMAL128: ltd.append_decimal128_column(fid, tpch.DECIMAL_PRECISION, tpch.DECIMAL_SCALE, lid[c])
+        else: ltd.append_column(fid, dt, lid[c])
+    star = dict(fact_filters=[F(tpch.L_SHIPDATE, O.GreaterThan(D))], fact_key=tpch.L_ORDERKEY, dim=ot, dim_filters=[F(tpch.O_ORDERDATE, O.LessThan(D))], dim_key=tpch.O_ORDERKEY,
+                dim_fk=tpch.O_CUSTKEY, dim2=ct, dim2_filters=[F(tpch.C_MKTSEGMENT, O.Equals("BUILDING"))], dim2_key=tpch.C_CUSTKEY)
+    exact = rt.JoinTopkExact(ltd, sum_expr=rev, payload_fields=[tpch.O_ORDERDATE, tpch.O_SHIPPRIORITY], limit=10, **star)
+    dout, dtotal = exact.run()
+    dts = []
+    for _ in range(7):
+        t0 = time.perf_counter(); dout, dtotal = exact.run(); dts.append(time.perf_counter() - t0)
+
+    def general(prepared=None):
+        jq = prepared or rt.JoinGroupBy(ltd, star["fact_filters"], star["fact_key"], ot, star["dim_filters"], star["dim_key"], [A.sum(rev), A.count_star()],
+                                        dim_fk=star["dim_fk"], dim2=ct, dim2_filters=star["dim2_filters"], dim2_key=star["dim2_key"])
+        jq.launch(); jq.finish_only()
+        rows_, total_ = jq.result([tpch.O_ORDERDATE, tpch.O_SHIPPRIORITY], [(abi.JOIN_ORDER_AGGREGATE, 0, True), (abi.JOIN_ORDER_PAYLOAD, 0, False)], 10)
+        return jq, rows_, total_
+    res["decimal"] = {"groups": dtotal, "exact_seconds_best": min(dts), "exact_seconds_all": dts, "ratio_to_f64_pipeline": min(dts) / best,
+                      "same_top_keys_as_the_f64_pipeline": [o[0] for o in dout] == [o[0] for o in out],
+                      "top": [(o[0], o[1].value, o[1].precision, o[1].scale, o[2]) for o in dout[:3]]}
+    if "--exact-only" not in sys.argv:  # (a profile of the exact call alone leaves the comparison out)
+        jq, grows, gtotal = general()
+        cold, warm = [], []
+        for _ in range(3):
+            t0 = time.perf_counter(); j2, grows, gtotal = general(); cold.append(time.perf_counter() - t0); j2.close()
+        for _ in range(3):
+            t0 = time.perf_counter(); general(jq); warm.append(time.perf_counter() - t0)
+        jq.close()
+        same = [(o[0], o[1], o[2], o[3], o[4]) for o in dout] == [(g.key, g.values[0], g.values[1].value, g.payload[0], g.payload[1]) for g in grows] and dtotal == gtotal
+        res["decimal"].update({"general_route_seconds_prepare_and_run_best": min(cold), "general_route_seconds_prepared_run_best": min(warm),
+                               "same_cells_as_the_general_route": same})
 # ---- configs[4] sharded over `world` ranks, emulated on this one device: what ONE rank runs per query (prepare: its dimension
 # work + the probe of its 1/world of lineitem + the run sums; then its share of the exchange) in the general form (dimension
 # selection replicated, per-group counts all-reduced) and in the range form (orders of the rank's own key range only, boundary
