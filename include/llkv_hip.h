@@ -582,7 +582,73 @@ typedef struct llkv_group_order_key {
 } llkv_group_order_key;
 llkv_status llkv_hip_query_set_group_order(llkv_hip_query *query, const llkv_group_order_key *order, uint32_t n_order,
                                            uint64_t offset, uint64_t limit /* UINT64_MAX = no limit */);
-uint64_t llkv_hip_query_total_groups(const llkv_hip_query *query); /* groups of the last finish before OFFSET / LIMIT */
+uint64_t llkv_hip_query_total_groups(const llkv_hip_query *query); /* groups of the last finish after HAVING, before OFFSET / LIMIT */
+
+/* HAVING over the OUTPUT cells of a prepared GROUP BY — evaluate_having_expr llkv-executor/src/lib.rs:6667-7006, applied
+ * between the output rows and ORDER BY / OFFSET / LIMIT (:5305-5355).  A group is kept iff the predicate is TRUE (neither
+ * FALSE nor NULL keeps it).  The program is postfix, like llkv_expr_token: leaves push one three-valued truth, AND / OR
+ * pop `n_children` (>= 1) and push one, NOT pops one and pushes one; exactly one value is left at the end.
+ * An operand is a key cell, an aggregate cell (an aggregate used only in HAVING is one more entry of the query's `aggs`)
+ * or a literal.  Cell → value: Int64 / Boolean (0 / 1) → Integer, Float64 → Float, Decimal128 → Decimal, Utf8 → String,
+ * Date32 → Date32, NULL → Null (key cells are typed by the key COLUMN's type); literals: Int128 `as i64` (wraps),
+ * Boolean → Integer 0 / 1 (:7019-7028).
+ *   COMPARE   either side Null → NULL; Integer/Integer exact; Integer/Float: the integer `as f64`; Float/Float by the IEEE
+ *             operators (a NaN operand: every operator false but !=); every other pairing — String, Decimal, Date32 cells or
+ *             literals, same type or not — is FALSE (:6716-6791)
+ *   IN_LIST   Null test value → NULL; a match is Int=Int, Float=Float, mixed through `as f64`, String=String; no match and
+ *             a Null item → NULL; `negated` flips TRUE and FALSE only (:6806-6884)
+ *   IS_NULL   always boolean;  LITERAL  its boolean;  AND / OR / NOT three-valued (:6793-6805,6902-6937)
+ * Not expressible here (the binding keeps such plans and says has_having = 1 to llkv_hip_select_route): arithmetic over
+ * aggregates, the `Expr::Pred` leaf form, EXISTS.
+ * Errors come before the filter: a finalize failure (SUM(Int64) "integer overflow", "AVG aggregate sum exceeds i64 range")
+ * in a group the predicate would drop still fails the query, with the unfiltered query's status and message.
+ * The sort-based and partitioned routes filter on the device before the copy-out when every operand is an Int64 key, an
+ * aggregate with an Int64 / Float64 cell or an Int / Float / Boolean / NULL literal (flags → scan → stable compaction;
+ * survivors keep their unordered position); other programs, the dense routes and the merged groups of a sharded table
+ * filter on the host with the same rules.  The route note says which: "; having: device" or "; having: host (<reason>)",
+ * before the order note.
+ * Takes effect from the next finish / collect / finish_from_host / merge_groups; num_groups / group_key / value then read
+ * the surviving groups, ORDER BY / OFFSET / LIMIT (set_group_order) apply after it and total_groups counts the survivors.
+ * n_nodes = 0 clears it.  LLKV_INVALID_ARGUMENT (the message names the node) for a malformed program (stack underflow, more
+ * than one value left, n_children = 0), an index out of range, an ungrouped query, a join → GROUP BY query and executions
+ * in flight.  A sharded table filters after the exchange: finish → partial_groups → all-gather → set_having /
+ * set_group_order → merge_groups; partial_groups refuses a query with a HAVING set (partial states must arrive unfiltered). */
+typedef enum llkv_having_kind {
+  LLKV_HAVING_COMPARE = 1, /* cmp_op, lhs, rhs                  */
+  LLKV_HAVING_IN_LIST = 2, /* lhs, negated, list[n_list]        */
+  LLKV_HAVING_IS_NULL = 3, /* lhs, negated                      */
+  LLKV_HAVING_LITERAL = 4, /* literal (0 / 1)                   */
+  LLKV_HAVING_AND = 5,     /* pops n_children                   */
+  LLKV_HAVING_OR = 6,      /* pops n_children                   */
+  LLKV_HAVING_NOT = 7
+} llkv_having_kind;
+typedef enum llkv_having_operand_kind {
+  LLKV_HAVING_OPERAND_KEY = 0,       /* index = position in key_fields */
+  LLKV_HAVING_OPERAND_AGGREGATE = 1, /* index = position in aggs       */
+  LLKV_HAVING_OPERAND_LITERAL = 2    /* literal                        */
+} llkv_having_operand_kind;
+typedef struct llkv_having_operand {
+  int32_t kind; /* llkv_having_operand_kind */
+  uint32_t index;
+  llkv_literal literal;
+} llkv_having_operand;
+typedef struct llkv_having_node {
+  int32_t kind;    /* llkv_having_kind  */
+  int32_t cmp_op;  /* llkv_compare_op   */
+  int32_t negated; /* IN_LIST / IS_NULL */
+  int32_t literal; /* LITERAL: 0 / 1    */
+  uint32_t n_children;
+  uint32_t n_list;
+  llkv_having_operand lhs, rhs;
+  const llkv_having_operand *list; /* borrowed: copied by set_having */
+} llkv_having_node;
+llkv_status llkv_hip_query_set_having(llkv_hip_query *query, const llkv_having_node *nodes, uint32_t n_nodes);
+/* The rules alone, host only (no device needed): the truth of the program over one row of cells — the evaluator the
+ * query's host path runs.  `key_dtypes[k]`: the key column's llkv_dtype (a Date32 / Boolean key cell arrives as
+ * LLKV_DT_INT64); *truth = 1 TRUE, 0 FALSE, -1 NULL.                                                                  */
+llkv_status llkv_hip_having_eval(const llkv_having_node *nodes, uint32_t n_nodes, const llkv_value *key_cells,
+                                 const int32_t *key_dtypes, uint32_t n_keys, const llkv_value *agg_cells, uint32_t n_aggs,
+                                 int32_t *truth);
 /* Status a finalize step produced for one aggregate (e.g. "integer overflow"
  * is LLKV_INVALID_ARGUMENT, llkv-aggregate/src/lib.rs:816-829).              */
 
@@ -1130,6 +1196,8 @@ typedef struct llkv_select_shape {
   int32_t has_computed_aggregates;     /* Self::has_computed_aggregates(&plan): an aggregate inside a projection    */
   uint32_t n_joins;                    /* plan.joins.len(): explicit JOIN … ON between the tables                   */
   int32_t has_having, has_distinct, has_scalar_subqueries; /* SQL breadth the GPU path leaves to the CPU routes     */
+  /* has_having: a HAVING the binding could NOT lower into llkv_hip_query_set_having (arithmetic over aggregates, `Pred`
+   * leaves, EXISTS).  A binding that lowers its HAVING there passes has_having = 0.                                   */
 } llkv_select_shape;
 /* `*route_out`: the route the reference takes.  Returns LLKV_OK when the GPU path serves it, LLKV_UNSUPPORTED when
  * the caller keeps its CPU route (message: why), LLKV_INVALID_ARGUMENT for a shape the reference rejects.          */

@@ -202,6 +202,122 @@ class GroupOrder:
         return CGroupOrderKey(self.kind, self.index, int(bool(self.descending)), int(bool(self.nulls_first)))
 
 
+# ----------------------------------------------------------------------------- HAVING
+HAVING_COMPARE, HAVING_IN_LIST, HAVING_IS_NULL, HAVING_LITERAL, HAVING_AND, HAVING_OR, HAVING_NOT = range(1, 8)
+HAVING_OPERAND_KEY, HAVING_OPERAND_AGGREGATE, HAVING_OPERAND_LITERAL = range(3)
+
+
+class CHavingOperand(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("index", C.c_uint32), ("literal", CLiteral)]
+
+
+class CHavingNode(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("cmp_op", C.c_int32), ("negated", C.c_int32), ("literal", C.c_int32),
+                ("n_children", C.c_uint32), ("n_list", C.c_uint32), ("lhs", CHavingOperand), ("rhs", CHavingOperand),
+                ("list", C.POINTER(CHavingOperand))]
+
+
+@dataclass(frozen=True)
+class HavingOperand:
+    """One operand of a HAVING leaf (llkv_having_operand): an output key cell, an output aggregate cell or a literal."""
+    kind: int
+    index: int = 0
+    literal: Optional["Literal"] = None
+
+    @staticmethod
+    def of(v) -> "HavingOperand":
+        return v if isinstance(v, HavingOperand) else HavingOperand(HAVING_OPERAND_LITERAL, 0, Literal.of(v))
+
+    def to_c(self, keep: list) -> CHavingOperand:
+        c = CHavingOperand()
+        c.kind, c.index = self.kind, self.index
+        if self.literal is not None:
+            c.literal = self.literal.to_c(keep)
+        return c
+
+
+@dataclass(frozen=True)
+class Having:
+    """A HAVING predicate over the output cells of a GROUP BY (llkv_having_node; evaluate_having_expr
+    llkv-executor/src/lib.rs:6667-7006).  Built as a tree with the static methods and flattened to the postfix program
+    by ``postfix()``; a node without ``children`` but with ``n_children`` set is one raw node of a program written out
+    by hand (``PreparedQuery.set_having`` takes a tree or such a sequence)."""
+    kind: int
+    cmp_op: int = 0
+    negated: bool = False
+    literal: bool = False
+    lhs: Optional[HavingOperand] = None
+    rhs: Optional[HavingOperand] = None
+    items: Tuple[HavingOperand, ...] = ()
+    children: Tuple["Having", ...] = ()
+    n_children: int = 0
+
+    @staticmethod
+    def key(index: int) -> HavingOperand:
+        return HavingOperand(HAVING_OPERAND_KEY, index)
+
+    @staticmethod
+    def agg(index: int) -> HavingOperand:
+        return HavingOperand(HAVING_OPERAND_AGGREGATE, index)
+
+    @staticmethod
+    def compare(lhs, op: int, rhs) -> "Having":
+        return Having(HAVING_COMPARE, cmp_op=op, lhs=HavingOperand.of(lhs), rhs=HavingOperand.of(rhs))
+
+    @staticmethod
+    def in_list(lhs, items, negated: bool = False) -> "Having":
+        return Having(HAVING_IN_LIST, negated=negated, lhs=HavingOperand.of(lhs), items=tuple(HavingOperand.of(i) for i in items))
+
+    @staticmethod
+    def is_null(lhs, negated: bool = False) -> "Having":
+        return Having(HAVING_IS_NULL, negated=negated, lhs=HavingOperand.of(lhs))
+
+    @staticmethod
+    def lit(value: bool) -> "Having":
+        return Having(HAVING_LITERAL, literal=bool(value))
+
+    @staticmethod
+    def and_(*children: "Having") -> "Having":
+        return Having(HAVING_AND, children=tuple(children), n_children=len(children))
+
+    @staticmethod
+    def or_(*children: "Having") -> "Having":
+        return Having(HAVING_OR, children=tuple(children), n_children=len(children))
+
+    @staticmethod
+    def not_(child: "Having") -> "Having":
+        return Having(HAVING_NOT, children=(child,), n_children=1)
+
+    def postfix(self) -> List["Having"]:
+        out: List[Having] = []
+        for c in self.children:
+            out.extend(c.postfix())
+        out.append(self)
+        return out
+
+    def to_c(self, keep: list) -> CHavingNode:
+        c = CHavingNode()
+        c.kind, c.cmp_op, c.negated, c.literal = self.kind, self.cmp_op, int(bool(self.negated)), int(bool(self.literal))
+        c.n_children, c.n_list = self.n_children, len(self.items)
+        if self.lhs is not None:
+            c.lhs = self.lhs.to_c(keep)
+        if self.rhs is not None:
+            c.rhs = self.rhs.to_c(keep)
+        if self.items:
+            arr = (CHavingOperand * len(self.items))(*[i.to_c(keep) for i in self.items])
+            keep.append(arr)
+            c.list = arr
+        return c
+
+
+def having_program(having, keep: list):
+    """(CHavingNode array, n) of a Having tree, a sequence of raw nodes, or None / () (n = 0: clears the HAVING)."""
+    nodes = [] if having is None else having.postfix() if isinstance(having, Having) else list(having)
+    arr = (CHavingNode * max(1, len(nodes)))(*[n.to_c(keep) for n in nodes])
+    keep.append(arr)
+    return arr, len(nodes)
+
+
 class CColumnDesc(C.Structure):
     _fields_ = [("field_id", C.c_uint32), ("dtype", C.c_int32), ("rows", C.c_uint64), ("has_stats", C.c_int32),
                 ("min_i", C.c_int64), ("max_i", C.c_int64), ("dict_size", C.c_uint32),
@@ -609,6 +725,26 @@ class Value:
     value: object
     precision: int = 0  # Decimal128(precision, scale); value = raw i128
     scale: int = 0
+
+    def to_c(self, keep: list) -> CValue:
+        c = CValue()
+        c.dtype, c.is_null, c.precision, c.scale = self.dtype, int(bool(self.is_null)), self.precision, self.scale
+        if self.is_null or self.value is None:
+            return c
+        if self.dtype == DT_DECIMAL128:
+            v = int(self.value) & ((1 << 128) - 1)
+            lo, hi = v & 0xFFFFFFFFFFFFFFFF, v >> 64
+            c.i64 = lo - (1 << 64) if lo >= (1 << 63) else lo
+            c.i64_hi = hi - (1 << 64) if hi >= (1 << 63) else hi
+        elif self.dtype == DT_FLOAT64:
+            c.f64 = float(self.value)
+        elif self.dtype == DT_UTF8:
+            b = str(self.value).encode()
+            keep.append(b)
+            c.str = b
+        else:
+            c.i64 = int(self.value)
+        return c
 
     @staticmethod
     def from_c(c: CValue) -> "Value":

@@ -337,12 +337,12 @@ int Query::launch(hipStream_t stream) {
   if (sorted) { // the sort-based route runs to completion here; submit / collect only hand the result over
     if (n_launched != n_collected) return set_error(LLKV_INVALID_ARGUMENT, "a sort-based GROUP BY keeps one execution in flight");
     // (a sharded table orders the merged groups: llkv_hip_query_merge_groups / finish_sharded)
-    const bool local_order = order.active() && table->world == 1;
+    const bool local_order = order.active() && table->world == 1, local_having = having.active() && table->world == 1;
     row_mapped = false;
     row_map.clear();
     GroupOrderDone done;
-    int rc = sorted_groupby_run(sorted, &lazy, local_order ? &order : nullptr, &done);
-    if (!rc && local_order) rc = apply_order(&done);
+    int rc = sorted_groupby_run(sorted, &lazy, local_order ? &order : nullptr, &done, local_having ? &having : nullptr);
+    if (!rc && (local_order || local_having)) rc = apply_order(&done);
     else if (!rc) { row_mapped = false; row_map.clear(); order_note.clear(); total_groups = lazy.n; }
     if (rc) return rc;
     n_launched++;
@@ -964,26 +964,75 @@ int Query::finish_from_exchange(const uint64_t *exchange) {
   return apply_order(nullptr);
 }
 
-// The order of llkv_hip_query_set_group_order over the result of the latest finish: the device top-k already left only the
-// returned rows (`done->device`); otherwise the rows are sorted here and read through row_map.  done = nullptr: a dense route.
+// The HAVING of llkv_hip_query_set_having, then the order of llkv_hip_query_set_group_order, over the result of the latest finish.
+// A sort-based / partitioned run may have done either on the device: `done->having_device` — the result holds the survivors only —
+// and `done->device` — the top-k left only the returned rows.  Otherwise the groups are filtered (having_eval over the finalized
+// cells) and sorted here and read through row_map.  done = nullptr: a dense route.
 int Query::apply_order(const GroupOrderDone *done) {
   row_mapped = false;
   row_map.clear();
   order_note.clear();
   total_groups = result_rows();
-  if (!order.active() || !plan_grouped()) return LLKV_OK;
+  if (!plan_grouped()) return LLKV_OK;
+  bool filtered = false; // row_map = the surviving rows of the result, in their unordered position
+  if (having.active()) {
+    if (done && done->having_device) {
+      total_groups = done->total;
+      order_note = "; having: device";
+    } else {
+      // errors come before the filter: every group's fallible aggregates are finalized first (a dense route has finalized them all;
+      // the copied-out groups of a sort-based run too, the merged groups of a sharded table not yet)
+      std::string err;
+      llkv_value v;
+      if (lazy.active)
+        for (size_t a = 0; a < lazy.plan->aggs.size(); ++a) {
+          if (lazy.plan->aggs[a].fin != AggFinal::SumI64 && lazy.plan->aggs[a].fin != AggFinal::AvgI64) continue;
+          for (uint64_t g = 0; g < lazy.n; ++g)
+            if (int rc = finalize_value(lazy.plan->aggs[a], lazy.lanes + g * (size_t)lazy.k, 2, &v, &err, false)) return set_error(rc, err);
+        }
+      const uint64_t n = result_rows();
+      for (uint64_t r = 0; r < n; ++r) {
+        int32_t truth = 0;
+        const int rc = having_eval(having.nodes.data(), (uint32_t)having.nodes.size(), [&](const llkv_having_operand &o, llkv_value *cell, int32_t *key_dtype) {
+          if (o.kind != LLKV_HAVING_OPERAND_KEY) return cell_value(r, o.index, cell);
+          *key_dtype = key_dtype_of(o.index);
+          return cell_key(r, o.index, cell);
+        }, &truth);
+        if (rc) { row_map.clear(); return rc; }
+        if (truth == 1) row_map.push_back(r);
+      }
+      filtered = true;
+      row_mapped = true;
+      total_groups = row_map.size();
+      order_note = "; having: host (" + (!done ? std::string("dense route") : done->having_why_host.empty() ? std::string("no groups") : done->having_why_host) + ")";
+    }
+  }
+  if (!order.active()) return LLKV_OK;
   if (done && done->device) {
     total_groups = done->total;
-    order_note = "; order: device top-k";
+    order_note += "; order: device top-k";
     return LLKV_OK;
   }
+  std::vector<uint64_t> ordered;
   const int rc = group_order_host(order, total_groups, [&](uint64_t r, const llkv_group_order_key &t, llkv_value *v) {
-    return t.kind == LLKV_GROUP_ORDER_KEY ? cell_key(r, t.index, v) : cell_value(r, t.index, v);
-  }, &row_map);
-  if (rc) { row_map.clear(); return rc; }
+    const uint64_t row = filtered ? row_map[r] : r;
+    return t.kind == LLKV_GROUP_ORDER_KEY ? cell_key(row, t.index, v) : cell_value(row, t.index, v);
+  }, &ordered);
+  if (rc) { row_map.clear(); row_mapped = false; return rc; }
+  if (filtered)
+    for (uint64_t &r : ordered) r = row_map[r];
+  row_map.swap(ordered);
   row_mapped = true;
-  order_note = "; order: host (" + (!done ? std::string("dense route") : done->why_host.empty() ? std::string("no groups") : done->why_host) + ")";
+  order_note += "; order: host (" + (!done ? std::string("dense route") : done->why_host.empty() ? std::string("no groups") : done->why_host) + ")";
   return LLKV_OK;
+}
+
+// The dtype of key column `key` (what types a key cell under HAVING: cell_key hands Date32 / Boolean cells over as LLKV_DT_INT64).
+int32_t Query::key_dtype_of(uint32_t key) const {
+  if (lazy.active) return key < lazy.key_cols.size() ? lazy.key_cols[key]->dtype : (int32_t)LLKV_DT_INT64;
+  if (key >= plan.key_fields.size()) return LLKV_DT_INT64;
+  auto it = table->cols.find(plan.key_fields[key]);
+  return it == table->cols.end() ? (int32_t)LLKV_DT_INT64 : it->second.info.dtype;
 }
 
 // One cell of the result before the order (row = its position in the unordered output).
@@ -1282,6 +1331,21 @@ llkv_status llkv_hip_query_set_group_order(llkv_hip_query *query, const llkv_gro
   return LLKV_OK;
 }
 
+llkv_status llkv_hip_query_set_having(llkv_hip_query *query, const llkv_having_node *nodes, uint32_t n_nodes) {
+  Query *q = reinterpret_cast<Query *>(query);
+  if (!q) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "query is NULL");
+  if (n_nodes && !nodes) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "nodes is NULL");
+  if (q->join_state) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "a join → GROUP BY query takes no HAVING");
+  if (!q->plan_grouped()) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "HAVING needs a GROUP BY query (this one is ungrouped)");
+  if (q->n_launched != q->n_collected) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "executions in flight");
+  if (n_nodes) {
+    std::string err;
+    if (int rc = having_validate(nodes, n_nodes, q->n_user_keys, q->n_user_aggs, &err)) return (llkv_status)set_error(rc, err);
+  }
+  q->having.assign(nodes, n_nodes);
+  return LLKV_OK;
+}
+
 uint64_t llkv_hip_query_total_groups(const llkv_hip_query *query) {
   const Query *q = reinterpret_cast<const Query *>(query);
   return q ? q->total_groups : 0;
@@ -1293,6 +1357,8 @@ llkv_status llkv_hip_query_partial_groups(const llkv_hip_query *query, uint64_t 
   if (!q || !q->sorted || !q->lazy.active) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "not a finished sort-based GROUP BY");
   if (q->order.active())
     return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "partial groups of a query with an ORDER BY / LIMIT: order the merged groups (set_group_order before merge_groups)");
+  if (q->having.active())
+    return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "partial groups of a query with a HAVING: filter the merged groups (set_having before merge_groups)");
   if (n_groups) *n_groups = q->lazy.n;
   if (n_keys) *n_keys = q->lazy.n_keys;
   if (lanes_per_group) *lanes_per_group = (uint32_t)q->lazy.k;

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <map>
 #include <memory>
@@ -411,9 +412,42 @@ struct GroupOrderSpec {
 // LazyGroups (`device`), or it copied out every group and `why_host` says why (the caller sorts them on the host).
 struct GroupOrderDone {
   bool device = false;
-  uint64_t total = 0; // groups before OFFSET / LIMIT
+  uint64_t total = 0; // groups after HAVING, before OFFSET / LIMIT
   std::string why_host;
+  bool having_device = false; // the HAVING was applied on the device: the LazyGroups hold survivors only
+  std::string having_why_host;
 };
+
+// HAVING over the output cells of a GROUP BY (llkv_hip_query_set_having; evaluate_having_expr llkv-executor/src/lib.rs:6667-7006;
+// the rules: having_rules.h).  An owned copy of the caller's program: IN lists and string literals live in the object.
+struct HavingProgram {
+  std::vector<llkv_having_node> nodes;
+  std::deque<std::vector<llkv_having_operand>> lists;
+  std::deque<std::string> strings;
+  HavingProgram() = default;
+  HavingProgram(const HavingProgram &) = delete;
+  HavingProgram &operator=(const HavingProgram &) = delete;
+  bool active() const { return !nodes.empty(); }
+  void assign(const llkv_having_node *src, uint32_t n);
+};
+// LLKV_OK, or LLKV_INVALID_ARGUMENT with *err naming the node: unknown kinds, operators and literal tags, indices out of range,
+// stack underflow, n_children = 0, more or fewer than one value left, a stack deeper than kHavingMaxDepth.
+int having_validate(const llkv_having_node *nodes, uint32_t n, uint32_t n_keys, uint32_t n_aggs, std::string *err);
+// The host evaluator (the one of llkv_hip_having_eval and of Query::apply_order): cell(operand, &v, &key_dtype) yields the
+// finalized cell of a KEY / AGGREGATE operand and, for a key, its column's dtype (what types the cell).  *truth: HavingTruth.
+using HavingCell = std::function<int(const llkv_having_operand &, llkv_value *, int32_t *)>;
+int having_eval(const llkv_having_node *nodes, uint32_t n, const HavingCell &cell, int32_t *truth);
+// Whether the flag kernel can evaluate the program over the groups of `lz` (else *why): every operand an Int64 key column, an
+// aggregate with an i64 / f64 cell, or an Int / Float / Boolean / NULL literal, within the kernel's caps.
+bool having_device_ok(const HavingProgram &h, const LazyGroups &lz, std::string *why);
+// Device HAVING over `n` groups in unordered output order: the flag kernel (keep flags + the first failing group of every
+// aggregate whose finalize can fail, over ALL groups), an exclusive scan, the stable compaction into c_lanes / c_kv / c_kvalid.
+// One round trip brings back the survivor count, the error records and the route's unread error word `d_error` (nullptr: read
+// already).  A finalize failure returns the host's status and message for that group.
+int having_device(const HavingProgram &h, const LazyGroups &lz, const uint64_t *d_lanes, const int64_t *d_kv, const uint8_t *d_kvalid, uint64_t n,
+                  const uint32_t *d_error, hipStream_t s, Scratch *c_lanes, Scratch *c_kv, Scratch *c_kvalid, uint64_t *n_kept);
+// The host's status and message for group `g` of aggregate `agg` whose device finalize check failed (the group's lanes are fetched).
+int group_finalize_failure(const LoweredPlan &plan, int agg, const uint64_t *d_lanes, uint64_t g, int k, hipStream_t s);
 // Whether every term has a bit-exact device twin of its host finalize and the rows fit the device bound (else *why).
 bool group_order_device_ok(const GroupOrderSpec &o, const LazyGroups &lz, std::string *why);
 // Device top-k over `n` groups in unordered output order ([n][k] lanes, [n_keys][n] key cells and validity in HBM): error-flag
@@ -430,11 +464,12 @@ int group_order_host(const GroupOrderSpec &o, uint64_t n, const std::function<in
 // What the sort-based and the partitioned run share (group_sort.cpp).  Head: the empty result over the keys `key_fields` of `t`.
 void lazy_groups_begin(LazyGroups *out, const LoweredPlan &plan, const Table &t, const std::vector<uint32_t> &key_fields);
 // Tail: delivers the `n_groups` groups of the device arrays ([n][k] lanes, [n_keys][n] key cells and validity, in unordered output
-// order) through `h` — the device top-k when an order is asked for and group_order_device_ok, else every group copied out — then
-// groups_host_pass.  `d_error`: the route's device error word when it has not been read yet (it is, in the round trip the tail
+// order) through `h` — first the device HAVING when one is set and having_device_ok (the tail then sees the survivors), then the
+// device top-k when an order is asked for and group_order_device_ok, else every group copied out — then groups_host_pass.  A
+// HAVING without a device form leaves filter and order to the caller (done->having_why_host).  `d_error`: the route's device error word when it has not been read yet (it is, in the round trip the tail
 // makes anyway), nullptr when the caller has.
 int deliver_groups(const uint64_t *d_lanes, const int64_t *d_kv, const uint8_t *d_kvalid, uint64_t n_groups, const GroupOrderSpec *order, GroupOrderDone *done,
-                   const uint32_t *d_error, hipStream_t s, GroupResultBuffers *h, PhaseTrace *trace, LazyGroups *out);
+                   const uint32_t *d_error, hipStream_t s, GroupResultBuffers *h, PhaseTrace *trace, LazyGroups *out, const HavingProgram *having = nullptr);
 // … from the copied-out arrays on: the host pass over the aggregates whose finalize can fail, then out->n / lanes / key_vals / key_valid
 int groups_host_pass(const GroupResultBuffers &h, uint64_t n_groups, PhaseTrace *trace, LazyGroups *out);
 
@@ -448,7 +483,7 @@ inline const char *arith_error_message(uint64_t code) {
 struct PartGroupBy;
 int part_groupby_prepare(const Table *table, const llkv_filter *filters, uint32_t n_filters, const llkv_eval_op *ops, uint32_t n_ops,
                          const uint32_t *key_fields, uint32_t n_keys, const llkv_aggregate_spec *aggs, uint32_t n_aggs, bool order_by_keys, PartGroupBy **out);
-int part_groupby_run(PartGroupBy *p, LazyGroups *out, const GroupOrderSpec *order = nullptr, GroupOrderDone *done = nullptr);
+int part_groupby_run(PartGroupBy *p, LazyGroups *out, const GroupOrderSpec *order = nullptr, GroupOrderDone *done = nullptr, const HavingProgram *having = nullptr);
 void part_groupby_free(PartGroupBy *p);
 const LoweredPlan *part_groupby_plan(const PartGroupBy *p);
 
@@ -463,7 +498,7 @@ struct KeySetView;
 int sorted_groupby_prepare(const Table *table, const llkv_filter *filters, uint32_t n_filters, const llkv_eval_op *ops, uint32_t n_ops,
                            const uint32_t *key_fields, uint32_t n_keys, const llkv_aggregate_spec *aggs, uint32_t n_aggs,
                            bool order_by_keys, SortedGroupBy **out, const KeySetView *key_set = nullptr, uint32_t key_set_field = 0);
-int sorted_groupby_run(SortedGroupBy *s, LazyGroups *out, const GroupOrderSpec *order = nullptr, GroupOrderDone *done = nullptr);
+int sorted_groupby_run(SortedGroupBy *s, LazyGroups *out, const GroupOrderSpec *order = nullptr, GroupOrderDone *done = nullptr, const HavingProgram *having = nullptr);
 void sorted_groupby_free(SortedGroupBy *s);
 // Sharded table: the ranks' partial groups ([n_keys][n] key cells and validity, [n][k] lanes per rank, rank order)
 // become the table-wide groups of `out` (group_sort.cpp).
@@ -527,14 +562,16 @@ struct Query {
   // ORDER BY / OFFSET / LIMIT over the groups (llkv_hip_query_set_group_order): applied by the device top-k of the sort-based and
   // partitioned routes, or on the host — then output row i reads the result's row row_map[i]
   GroupOrderSpec order;
+  HavingProgram having; // llkv_hip_query_set_having: filters the groups before the order
   bool row_mapped = false;
   std::vector<uint64_t> row_map;
   uint64_t total_groups = 0;
-  std::string order_note;           // "; order: …" — which path served the order at the last finish
+  std::string order_note;           // "; having: …" and "; order: …" — which paths served the HAVING and the order at the last finish
   mutable std::string note_buf;     // route_note + order_note
   uint64_t result_rows() const { return lazy.active ? lazy.n : groups.size(); } // before the order
   int apply_order(const GroupOrderDone *done);
-  int apply_merged_order() { GroupOrderDone d; d.why_host = "merged groups"; return apply_order(&d); } // a sharded table's groups after the merge
+  int32_t key_dtype_of(uint32_t key) const;
+  int apply_merged_order() { GroupOrderDone d; d.why_host = d.having_why_host = "merged groups"; return apply_order(&d); } // a sharded table's groups after the merge
   bool plan_grouped() const { return sorted != nullptr || plan.grouped; }
   int cell_key(uint64_t group, uint32_t key, llkv_value *out) const;     // the result before the order
   int cell_value(uint64_t group, uint32_t agg, llkv_value *out) const;

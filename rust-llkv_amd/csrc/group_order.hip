@@ -21,6 +21,7 @@
 // Host order (group_order_host): the same images from the finalized cells, std::partial_sort — the dense routes, the merged
 // groups of a sharded table, larger limits and terms without a device form (a computed DECIMAL argument's precision check).
 #include "engine.hpp"
+#include "group_cell.hip.h"
 
 #include <algorithm>
 #include <cstring>
@@ -31,24 +32,17 @@ namespace llkv {
 
 namespace {
 
-typedef __int128 i128;
-typedef unsigned __int128 u128;
-
 constexpr int kMaxTerms = 8;
 constexpr int kMaxWords = 16;   // order-key words of the terms (a term: its NULL word and one or two value words)
-constexpr int kMaxErrAggs = 16; // aggregates whose finalize can fail
 constexpr uint32_t kOrderBlock = 256;
 
 enum TermKind : int32_t { kTermKeyInt = 0, kTermKeyUtf8 = 1, kTermAgg = 2 };
 
 struct OrderTerm {
   int32_t kind, key;        // key terms: the key's index
-  int32_t fin;              // aggregate terms: AggFinal
-  int32_t lane, count_lane; // relative to the group's aggregate lanes (after rows and first row id)
   int32_t word;             // first key word of the term
   int32_t desc, nulls_first;
-  int32_t typed_by_first_value, fast_sum, wide, plain_minmax, null_without_values, fixed_point, fixed_exp, exact_levels, wide_delta, nan_default;
-  uint64_t wide_base_hi, wide_base_lo;
+  AggCell a;                // aggregate terms: what the device finalize needs
   const uint32_t *rank; // Utf8 keys: dictionary code → position in byte order
 };
 
@@ -72,139 +66,17 @@ struct SelectState {
   unsigned long long prefix[kMaxWords + 1], mask[kMaxWords + 1];
 };
 
-__device__ inline double as_f64(uint64_t b) { return __longlong_as_double((long long)b); }
-__device__ inline uint64_t as_u64(double d) { return (uint64_t)__double_as_longlong(d); }
 __device__ inline uint64_t i64_image(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }
 __device__ inline uint64_t f64_image(uint64_t b) { return (b >> 63) ? ~b : (b | 0x8000000000000000ull); } // f64::total_cmp
 
-// The host's (x86-64 SSE2) NaN results, so that a NaN orders where the host's would: an operand NaN comes back quieted, the
-// first one first; an invalid operation yields the default NaN, sign bit set.
-constexpr uint64_t kQuiet = 0x0008000000000000ull;
-__device__ inline double host_add(double a, double b) {
-  if (__builtin_isnan(a)) return as_f64(as_u64(a) | kQuiet);
-  if (__builtin_isnan(b)) return as_f64(as_u64(b) | kQuiet);
-  const double r = a + b;
-  return __builtin_isnan(r) ? as_f64(0xFFF8000000000000ull) : r;
-}
-__device__ inline double host_div_rows(double a, int64_t rows) { // rows > 0
-  if (__builtin_isnan(a)) return as_f64(as_u64(a) | kQuiet);
-  return a / (double)rows;
-}
-
-// (double) of an i128, rounded to nearest even like the host's conversion
-__device__ double i128_to_f64(i128 v) {
-  const bool neg = v < 0;
-  const u128 m = neg ? (u128)0 - (u128)v : (u128)v;
-  const uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
-  if (!hi && !(lo >> 53)) { const double r = (double)lo; return neg ? -r : r; } // exact
-  const int msb = hi ? 127 - __builtin_clzll(hi) : 63 - __builtin_clzll(lo);
-  const int sh = msb - 52; // keep 53 bits
-  u128 q = m >> sh;
-  const u128 rem = m & (((u128)1 << sh) - 1), half = (u128)1 << (sh - 1);
-  if (rem > half || (rem == half && (q & 1))) q += 1; // (a carry to 2^53 is still exact)
-  const double r = ldexp((double)(uint64_t)q, sh);
-  return neg ? -r : r;
-}
-
-// |m| / d and its remainder (d > 0): AVG over Decimal128
-__device__ void udiv128(u128 m, uint64_t d, u128 *q, uint64_t *r) {
-  if (!(uint64_t)(m >> 64)) { *q = (uint64_t)m / d; *r = (uint64_t)m % d; return; }
-  u128 quo = 0, rem = 0;
-  for (int i = 127; i >= 0; --i) {
-    rem = (rem << 1) | ((m >> i) & 1);
-    if (rem >= d) { rem -= d; quo |= (u128)1 << i; }
-  }
-  *q = quo;
-  *r = (uint64_t)rem;
-}
-
-__device__ inline i128 exact_total(const uint64_t *l) { return ((i128)(int64_t)l[1] << 32) + (i128)(u128)l[0]; }
-
-// finalize_value (engine.cpp) of one aggregate, as an image: *null, or the value's words (one, two for Decimal128)
-__device__ void agg_image(const OrderTerm &t, const uint64_t *g, bool *null, uint64_t *w0, uint64_t *w1) {
-  const int64_t rows = t.count_lane >= 0 ? (int64_t)g[2 + t.count_lane] : (int64_t)g[0];
-  const uint64_t *l = g + 2 + (t.lane >= 0 ? t.lane : 0);
-  const AggFinal fin = (AggFinal)t.fin;
-  *null = false;
-  *w0 = *w1 = 0;
-  if (t.typed_by_first_value && rows == 0 &&
-      (fin == AggFinal::SumF64 || fin == AggFinal::MinF64 || fin == AggFinal::MaxF64 || fin == AggFinal::SumDec || fin == AggFinal::MinDec || fin == AggFinal::MaxDec)) {
-    *null = true;
-    return;
-  }
-  auto f64_sum = [&]() -> double {
-    if (t.fixed_point) return ldexp(i128_to_f64(exact_total(l)), t.fixed_exp);
-    double v = as_f64(l[t.exact_levels <= 1 ? 0 : t.exact_levels - 1]);
-    for (int j = t.exact_levels - 2; j >= 0; --j) v = host_add(v, as_f64(l[j]));
-    return t.nan_default && __builtin_isnan(v) ? as_f64(0xFFF8000000000000ull) : v; // (AggOut::nan_default)
-  };
-  auto dec = [&](i128 v) {
-    *w0 = (uint64_t)(v >> 64) ^ 0x8000000000000000ull;
-    *w1 = (uint64_t)v;
-  };
-  switch (fin) {
-  case AggFinal::MinDec: case AggFinal::MaxDec: {
-    if (rows == 0) { *null = true; return; }
-    if (t.wide_delta) {
-      const i128 base = (i128)(((u128)t.wide_base_hi << 64) | t.wide_base_lo);
-      dec(t.wide_delta == 1 ? base + (i128)(u128)l[0] : base - (i128)(u128)l[0]);
-    } else dec((i128)(int64_t)l[0]);
-    return;
-  }
-  case AggFinal::SumDec: case AggFinal::TotalDec: case AggFinal::AvgDec: {
-    const i128 sum = t.wide ? (i128)((u128)l[0] + ((u128)l[1] << 32) + ((u128)l[2] << 64) + ((u128)l[3] << 96))
-                            : t.fast_sum ? (i128)(int64_t)l[0] : exact_total(l);
-    if (fin == AggFinal::AvgDec) {
-      if (rows <= 0) { *null = true; return; }
-      const bool neg = sum < 0;
-      u128 q;
-      uint64_t r;
-      udiv128(neg ? (u128)0 - (u128)sum : (u128)sum, (uint64_t)rows, &q, &r);
-      i128 v = neg ? -(i128)q : (i128)q;
-      if ((u128)r * 2 >= (u128)(uint64_t)rows) v += neg ? -1 : 1; // half away from zero
-      dec(v);
-      return;
-    }
-    if (t.null_without_values && rows == 0) { *null = true; return; }
-    dec(sum);
-    return;
-  }
-  case AggFinal::CountRows: *w0 = i64_image(rows); return;
-  case AggFinal::CountNullsZero: *w0 = i64_image(0); return;
-  case AggFinal::CountValid: *w0 = i64_image((int64_t)l[0]); return;
-  case AggFinal::CountNulls: *w0 = i64_image((int64_t)g[0] - (int64_t)l[0]); return;
-  case AggFinal::SumI64Fast: case AggFinal::MinI64: case AggFinal::MaxI64:
-    if (rows == 0) { *null = true; return; }
-    *w0 = i64_image((int64_t)l[0]);
-    return;
-  case AggFinal::SumI64:
-    if (rows == 0) { *null = true; return; }
-    *w0 = i64_image((int64_t)exact_total(l)); // (a total outside i64 fails the query: order_key_kernel's error record)
-    return;
-  case AggFinal::SumF64: if (rows == 0) { *null = true; return; } *w0 = f64_image(as_u64(f64_sum())); return;
-  case AggFinal::TotalF64: *w0 = f64_image(as_u64(f64_sum())); return;
-  case AggFinal::AvgI64Fast:
-    if (rows == 0) { *null = true; return; }
-    *w0 = f64_image(as_u64((double)(int64_t)l[0] / (double)rows));
-    return;
-  case AggFinal::AvgI64:
-    if (rows == 0) { *null = true; return; }
-    *w0 = f64_image(as_u64((double)(int64_t)exact_total(l) / (double)rows));
-    return;
-  case AggFinal::AvgF64: if (rows == 0) { *null = true; return; } *w0 = f64_image(as_u64(host_div_rows(f64_sum(), rows))); return;
-  case AggFinal::MinF64: case AggFinal::MaxF64: {
-    if (rows == 0) { *null = true; return; }
-    const uint64_t nan = 0x7FF8000000000000ull; // std::nan("")
-    auto key_to_f64 = [](int64_t key) { return (uint64_t)(key < 0 ? (key ^ 0x7FFFFFFFFFFFFFFFll) : key); };
-    if (t.plain_minmax) { *w0 = f64_image(key_to_f64((int64_t)l[0])); return; }
-    if (l[2] & 1u) { *w0 = f64_image(nan); return; }
-    const uint64_t none = fin == AggFinal::MinF64 ? 0x7FFFFFFFFFFFFFFFull : 0x8000000000000000ull;
-    if (l[0] == none) { *w0 = f64_image(nan); return; }
-    uint64_t v = key_to_f64((int64_t)l[0]);
-    if (as_f64(v) == 0.0 && l[1] != 0x7FFFFFFFFFFFFFFFull && (l[1] & 1u)) v = 0x8000000000000000ull; // −0.0
-    *w0 = f64_image(v);
-    return;
-  }
+// order-preserving unsigned image of a finalized cell (group_cell.hip.h: agg_cell): *null, or the value's words (one, two for Decimal128)
+__device__ inline void agg_image(const AggCell &a, const uint64_t *g, bool *null, uint64_t *w0, uint64_t *w1) {
+  agg_cell(a, g, null, w0, w1);
+  if (*null) return;
+  switch (agg_cell_type((AggFinal)a.fin)) {
+  case kCellI64: *w0 = i64_image((int64_t)*w0); break;
+  case kCellF64: *w0 = f64_image(*w0); break;
+  default: *w0 ^= 0x8000000000000000ull; break; // Decimal128: the high word's sign
   }
 }
 
@@ -212,20 +84,13 @@ __global__ __launch_bounds__(kOrderBlock) void order_key_kernel(OrderParams p) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += stride) {
     const uint64_t *g = p.lanes + i * (uint64_t)p.k;
-    for (int e = 0; e < p.n_err; ++e) { // SUM / AVG over i64: the total outside i64, or a prefix that may have left it
-      const int64_t rows = p.err_count_lane[e] >= 0 ? (int64_t)g[2 + p.err_count_lane[e]] : (int64_t)g[0];
-      if (rows == 0) continue;
-      const uint64_t *l = g + 2 + p.err_lane[e];
-      const i128 total = exact_total(l);
-      const bool bad = total > (i128)INT64_MAX || total < (i128)INT64_MIN || __umul64hi(l[2], (uint64_t)rows) != 0 ||
-                       l[2] * (uint64_t)rows > (uint64_t)INT64_MAX;
-      if (bad) atomicMin(p.first_bad + e, (unsigned long long)i);
-    }
+    for (int e = 0; e < p.n_err; ++e)
+      if (agg_finalize_fails(g, p.err_lane[e], p.err_count_lane[e])) atomicMin(p.first_bad + e, (unsigned long long)i);
     for (int j = 0; j < p.n_terms; ++j) {
       const OrderTerm &t = p.t[j];
       bool null;
       uint64_t w0, w1 = 0;
-      if (t.kind == kTermAgg) agg_image(t, g, &null, &w0, &w1);
+      if (t.kind == kTermAgg) agg_image(t.a, g, &null, &w0, &w1);
       else {
         null = !p.kvalid[(uint64_t)t.key * p.n + i];
         const int64_t v = p.kv[(uint64_t)t.key * p.n + i];
@@ -233,8 +98,7 @@ __global__ __launch_bounds__(kOrderBlock) void order_key_kernel(OrderParams p) {
       }
       if (null) w0 = w1 = 0;
       else if (t.desc) { w0 = ~w0; w1 = ~w1; }
-      const bool two = t.kind == kTermAgg && ((AggFinal)t.fin == AggFinal::SumDec || (AggFinal)t.fin == AggFinal::TotalDec || (AggFinal)t.fin == AggFinal::AvgDec ||
-                                              (AggFinal)t.fin == AggFinal::MinDec || (AggFinal)t.fin == AggFinal::MaxDec);
+      const bool two = t.kind == kTermAgg && agg_cell_type((AggFinal)t.a.fin) == kCellDec;
       p.keys[(uint64_t)t.word * p.n + i] = null == (bool)t.nulls_first ? 0u : 1u;
       p.keys[(uint64_t)(t.word + 1) * p.n + i] = w0;
       if (two) p.keys[(uint64_t)(t.word + 2) * p.n + i] = w1;
@@ -356,9 +220,7 @@ __global__ __launch_bounds__(kOrderBlock) void order_gather_kernel(const uint64_
   }
 }
 
-bool is_decimal_fin(AggFinal f) {
-  return f == AggFinal::SumDec || f == AggFinal::TotalDec || f == AggFinal::AvgDec || f == AggFinal::MinDec || f == AggFinal::MaxDec;
-}
+bool is_decimal_fin(AggFinal f) { return agg_cell_type(f) == kCellDec; }
 
 uint32_t grid_for(uint64_t n) {
   const uint64_t want = (n + kOrderBlock - 1) / kOrderBlock;
@@ -374,7 +236,7 @@ bool group_order_device_ok(const GroupOrderSpec &o, const LazyGroups &lz, std::s
   if (o.terms.size() > (size_t)kMaxTerms) { *why = "more than " + std::to_string(kMaxTerms) + " terms"; return false; }
   if (lz.n >= (1ull << 32)) { *why = "2^32 groups or more"; return false; }
   int words = 0, n_err = 0;
-  for (const AggOut &a : lz.plan->aggs) n_err += a.fin == AggFinal::SumI64 || a.fin == AggFinal::AvgI64;
+  for (const AggOut &a : lz.plan->aggs) n_err += agg_finalize_can_fail(a.fin);
   if (n_err > kMaxErrAggs) { *why = "more than " + std::to_string(kMaxErrAggs) + " i64 SUM / AVG aggregates"; return false; }
   for (const llkv_group_order_key &t : o.terms) {
     if (t.kind == LLKV_GROUP_ORDER_KEY) {
@@ -408,7 +270,7 @@ int group_order_device(const GroupOrderSpec &o, const LazyGroups &lz, const uint
   std::vector<int> err_agg;
   for (size_t a = 0; a < plan.aggs.size(); ++a) {
     const AggOut &ao = plan.aggs[a];
-    if (ao.fin != AggFinal::SumI64 && ao.fin != AggFinal::AvgI64) continue;
+    if (!agg_finalize_can_fail(ao.fin)) continue;
     p.err_lane[err_agg.size()] = ao.lane;
     p.err_count_lane[err_agg.size()] = ao.count_lane;
     err_agg.push_back((int)a);
@@ -434,21 +296,7 @@ int group_order_device(const GroupOrderSpec &o, const LazyGroups &lz, const uint
     }
     const AggOut &a = plan.aggs[k.index];
     t.kind = kTermAgg;
-    t.fin = (int32_t)a.fin;
-    t.lane = a.lane;
-    t.count_lane = a.count_lane;
-    t.typed_by_first_value = a.typed_by_first_value;
-    t.fast_sum = a.fast_sum;
-    t.wide = a.wide;
-    t.plain_minmax = a.plain_minmax;
-    t.null_without_values = a.null_without_values;
-    t.fixed_point = a.fixed_point;
-    t.fixed_exp = a.fixed_exp;
-    t.exact_levels = a.exact_levels;
-    t.wide_delta = a.wide_delta;
-    t.nan_default = a.nan_default;
-    t.wide_base_hi = a.wide_base_hi;
-    t.wide_base_lo = a.wide_base_lo;
+    agg_cell_of(a, &t.a);
     words += is_decimal_fin(a.fin) ? 3 : 2;
   }
   p.n_terms = (int32_t)o.terms.size();
@@ -495,13 +343,7 @@ int group_order_device(const GroupOrderSpec &o, const LazyGroups &lz, const uint
     if ((rc = rb.add(bad, p.first_bad, (size_t)p.n_err * 8, s)) || (rc = rb.wait())) return rc;
     for (int e = 0; e < p.n_err; ++e) {
       if (bad[e] == ~0ull) continue;
-      std::vector<uint64_t> g((size_t)K);
-      HIP_TRY(hipMemcpyAsync(g.data(), d_lanes + bad[e] * (uint64_t)K, (size_t)K * 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      llkv_value v;
-      std::string err;
-      if ((rc = finalize_value(plan.aggs[(size_t)err_agg[(size_t)e]], g.data(), 2, &v, &err, false))) return set_error(rc, err);
-      return set_error(LLKV_INTERNAL, "device finalize check disagrees with the host's for aggregate " + std::to_string(err_agg[(size_t)e]));
+      return group_finalize_failure(plan, err_agg[(size_t)e], d_lanes, bad[e], K, s);
     }
   }
   if (rows_out == 0) return LLKV_OK;
@@ -538,6 +380,16 @@ int group_order_device(const GroupOrderSpec &o, const LazyGroups &lz, const uint
   if (selected != m) return set_error(LLKV_INTERNAL, "device top-k selected " + std::to_string(selected) + " groups, not " + std::to_string(m));
   *n_out = rows_out;
   return LLKV_OK;
+}
+
+int group_finalize_failure(const LoweredPlan &plan, int agg, const uint64_t *d_lanes, uint64_t group, int k, hipStream_t s) {
+  std::vector<uint64_t> g((size_t)k);
+  HIP_TRY(hipMemcpyAsync(g.data(), d_lanes + group * (uint64_t)k, (size_t)k * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  llkv_value v;
+  std::string err;
+  if (int rc = finalize_value(plan.aggs[(size_t)agg], g.data(), 2, &v, &err, false)) return set_error(rc, err);
+  return set_error(LLKV_INTERNAL, "device finalize check disagrees with the host's for aggregate " + std::to_string(agg));
 }
 
 // ---- host order ----------------------------------------------------------------------------------------------------------

@@ -50,7 +50,7 @@ struct PartGroupBy {
   Stream copy_stream;
   Event range_done[kRanges];
   PinnedArray h_counts; // uint32_t, pinned: groups with rows per range, then the scatter's error word
-  int run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done);
+  int run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done, const HavingProgram *having);
 };
 
 // Threads of one scatter workgroup.  The scatter is a chain of LDS phases between barriers with the record stores at its
@@ -145,7 +145,7 @@ int part_groupby_prepare(const Table *table, const llkv_filter *filters, uint32_
   return LLKV_OK;
 }
 
-int PartGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done) {
+int PartGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done, const HavingProgram *having) {
   lazy_groups_begin(out, plan, *table, key_fields);
   if (plan.always_false || table->local_rows == 0) return LLKV_OK;
   hipStream_t s = g_ctx.stream;
@@ -193,8 +193,9 @@ int PartGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrde
   // eight of 61: 3.72, against 2.77 one after the other)
   const uint32_t per_range = std::max<uint32_t>(g_ctx.cu_count, (np + kRanges - 1) / kRanges);
   const uint32_t n_ranges = (np + per_range - 1) / per_range;
-  const bool ordered = out_order && done && out_order->active(); // ORDER BY / LIMIT over the groups: no streamed key-order copy-out
-  const bool ranges = !ordered && order_by_keys && ids_in_key_order && n_keys == 1 && n_ranges >= 2 && (uint64_t)ng * (k * 8 + 9) <= (256ull << 20) &&
+  const bool filtered = having && done && having->active();       // HAVING …
+  const bool ordered = out_order && done && out_order->active(); // … ORDER BY / LIMIT over the groups: no streamed key-order copy-out
+  const bool ranges = !ordered && !filtered && order_by_keys && ids_in_key_order && n_keys == 1 && n_ranges >= 2 && (uint64_t)ng * (k * 8 + 9) <= (256ull << 20) &&
                       !std::getenv("LLKV_HIP_PART_NO_OVERLAP");
   if (ranges) {
     // ---- key order, one integer key: ascending group ids are the output order, so the groups of partitions [p0, p1) can leave
@@ -301,11 +302,11 @@ int PartGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrde
                                       kvalid_d.as<uint8_t>(), s));
   trace.mark("emit groups");
   // (the scatter's error word was read with the group count)
-  return deliver_groups(lanes_d.as<uint64_t>(), kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), n_groups, ordered ? out_order : nullptr, done, nullptr, s, &h, &trace, out);
+  return deliver_groups(lanes_d.as<uint64_t>(), kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), n_groups, ordered ? out_order : nullptr, done, nullptr, s, &h, &trace, out, filtered ? having : nullptr);
   }
   return groups_host_pass(h, n_groups, &trace, out); // (the streamed key-order copy-out joins the shared tail here)
 }
 
-int part_groupby_run(PartGroupBy *p, LazyGroups *out, const GroupOrderSpec *order, GroupOrderDone *done) { return p->run(out, order, done); }
+int part_groupby_run(PartGroupBy *p, LazyGroups *out, const GroupOrderSpec *order, GroupOrderDone *done, const HavingProgram *having) { return p->run(out, order, done, having); }
 
 } // namespace llkv

@@ -39,7 +39,7 @@ struct SortedGroupBy {
   // key set of the dimension rows that qualify (a bitmap the caller owns, alive as long as this object)
   bool has_key_set = false;
   KeySetView key_set{nullptr, 0, 0};
-  int run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done);
+  int run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done, const HavingProgram *having);
   ~SortedGroupBy() { if (part) part_groupby_free(part); }
 };
 
@@ -78,12 +78,31 @@ int groups_host_pass(const GroupResultBuffers &h, uint64_t n_groups, PhaseTrace 
 }
 
 int deliver_groups(const uint64_t *d_lanes, const int64_t *d_kv, const uint8_t *d_kvalid, uint64_t n_groups, const GroupOrderSpec *order, GroupOrderDone *done,
-                   const uint32_t *d_error, hipStream_t s, GroupResultBuffers *h, PhaseTrace *trace, LazyGroups *out) {
+                   const uint32_t *d_error, hipStream_t s, GroupResultBuffers *h, PhaseTrace *trace, LazyGroups *out, const HavingProgram *having) {
   int rc;
   const size_t K = (size_t)out->k, n_keys = out->n_keys;
   uint32_t errflag = 0;
+  Scratch c_lanes, c_kv, c_kvalid; // the survivors of a device HAVING
+  bool host_having = false;        // a HAVING the caller applies: every group leaves, unordered
+  if (having && done && having->active()) { // HAVING: filter in HBM, the tail below then sees the survivors only
+    if (n_groups >= (1ull << 32) - 1) done->having_why_host = "2^32 groups or more";
+    if (done->having_why_host.empty() && having_device_ok(*having, *out, &done->having_why_host)) {
+      uint64_t kept = 0;
+      if ((rc = having_device(*having, *out, d_lanes, d_kv, d_kvalid, n_groups, d_error, s, &c_lanes, &c_kv, &c_kvalid, &kept))) return rc;
+      d_error = nullptr; // (read with the survivor count)
+      done->having_device = true;
+      d_lanes = c_lanes.as<uint64_t>();
+      d_kv = c_kv.as<int64_t>();
+      d_kvalid = c_kvalid.as<uint8_t>();
+      n_groups = kept;
+      trace->mark("having");
+    } else {
+      host_having = true;
+      done->why_host = "HAVING on the host";
+    }
+  }
   if (done) done->total = n_groups;
-  if (order && done && order->active()) { // ORDER BY / LIMIT: the device top-k copies out only the rows returned
+  if (!host_having && n_groups && order && done && order->active()) { // ORDER BY / LIMIT: the device top-k copies out only the rows returned
     if (group_order_device_ok(*order, *out, &done->why_host)) {
       if (d_error) {
         Readback rb;
@@ -102,9 +121,11 @@ int deliver_groups(const uint64_t *d_lanes, const int64_t *d_kv, const uint8_t *
     }
   }
   if ((rc = h->reserve(n_groups * K * 8, n_groups * n_keys * 8, n_groups * n_keys))) return rc;
-  HIP_TRY(hipMemcpyAsync(h->lanes.p, d_lanes, n_groups * K * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(h->kv.p, d_kv, n_groups * n_keys * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(h->kvalid.p, d_kvalid, n_groups * n_keys, hipMemcpyDeviceToHost, s));
+  if (n_groups) {
+    HIP_TRY(hipMemcpyAsync(h->lanes.p, d_lanes, n_groups * K * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h->kv.p, d_kv, n_groups * n_keys * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h->kvalid.p, d_kvalid, n_groups * n_keys, hipMemcpyDeviceToHost, s));
+  }
   if (d_error) HIP_TRY(hipMemcpyAsync(&errflag, d_error, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (errflag) return set_error(LLKV_INTERNAL, arith_error_message(errflag));
@@ -245,8 +266,8 @@ int sorted_groupby_prepare(const Table *table, const llkv_filter *filters, uint3
   return LLKV_OK;
 }
 
-int SortedGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done) {
-  if (part) return part_groupby_run(part, out, out_order, done);
+int SortedGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done, const HavingProgram *having) {
+  if (part) return part_groupby_run(part, out, out_order, done, having);
   lazy_groups_begin(out, red_plan, *table, key_fields);
   hipStream_t s = g_ctx.stream;
   int rc;
@@ -458,9 +479,9 @@ int SortedGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOr
   HIP_TRY(hj_launch_group_keys(ks, sel.d_dev, perm, seg.as<uint64_t>(), order, n_groups, kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), s));
   trace.mark("group reduce");
   // (the reduce's error word is still unread: it travels with the copy-out, or is read before the top-k)
-  return deliver_groups(lanes_d.as<uint64_t>(), kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), n_groups, out_order, done, err_d.as<uint32_t>(), s, &h, &trace, out);
+  return deliver_groups(lanes_d.as<uint64_t>(), kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), n_groups, out_order, done, err_d.as<uint32_t>(), s, &h, &trace, out, having);
 }
 
-int sorted_groupby_run(SortedGroupBy *s, LazyGroups *out, const GroupOrderSpec *order, GroupOrderDone *done) { return s->run(out, order, done); }
+int sorted_groupby_run(SortedGroupBy *s, LazyGroups *out, const GroupOrderSpec *order, GroupOrderDone *done, const HavingProgram *having) { return s->run(out, order, done, having); }
 
 } // namespace llkv

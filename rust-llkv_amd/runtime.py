@@ -56,6 +56,9 @@ def lib():
     L.llkv_hip_free.argtypes = [C.c_void_p]
     L.llkv_hip_free.restype = None
     L.llkv_hip_query_set_group_order.argtypes = [C.c_void_p, C.POINTER(abi.CGroupOrderKey), C.c_uint32, C.c_uint64, C.c_uint64]
+    L.llkv_hip_query_set_having.argtypes = [C.c_void_p, C.POINTER(abi.CHavingNode), C.c_uint32]
+    L.llkv_hip_having_eval.argtypes = [C.POINTER(abi.CHavingNode), C.c_uint32, C.POINTER(abi.CValue), C.POINTER(C.c_int32), C.c_uint32,
+                                       C.POINTER(abi.CValue), C.c_uint32, C.POINTER(C.c_int32)]
     L.llkv_hip_query_total_groups.restype = C.c_uint64
     L.llkv_hip_query_total_groups.argtypes = [C.c_void_p]
     L.llkv_plan_last_error.restype = C.c_char_p
@@ -690,9 +693,16 @@ class PreparedQuery:
         lim = (1 << 64) - 1 if limit is None else int(limit)
         check(lib().llkv_hip_query_set_group_order(self._h, terms, C.c_uint32(len(order)), C.c_uint64(int(offset)), C.c_uint64(lim)))
 
+    def set_having(self, having=None):
+        """HAVING over the output cells (llkv_hip_query_set_having): an ``abi.Having`` tree or a sequence of raw postfix nodes,
+        from the next finish / collect / merge_groups on — before the order of set_group_order.  None or () clears it."""
+        keep: list = []
+        nodes, n = abi.having_program(having, keep)
+        check(lib().llkv_hip_query_set_having(self._h, nodes, C.c_uint32(n)))
+
     @property
     def total_groups(self) -> int:
-        """Groups of the last finish before OFFSET / LIMIT."""
+        """Groups of the last finish after HAVING, before OFFSET / LIMIT."""
         return int(lib().llkv_hip_query_total_groups(self._h))
 
     def merge_groups(self, parts):
@@ -735,12 +745,28 @@ def aggregate(table: HipTable, predicate, aggs: Sequence[AggregateSpec]) -> List
         q.close()
 
 
+def having_eval(having, key_cells: Sequence["abi.Value"] = (), key_dtypes: Sequence[int] = (), agg_cells: Sequence["abi.Value"] = ()):
+    """The HAVING rules over one row of cells, host only (llkv_hip_having_eval — the evaluator of the query's host path): True,
+    False or None (NULL).  ``key_dtypes``: the key COLUMNS' dtypes (a Date32 / Boolean key cell arrives as Int64)."""
+    keep: list = []
+    nodes, n = abi.having_program(having, keep)
+    kc = (abi.CValue * max(1, len(key_cells)))(*[v.to_c(keep) for v in key_cells])
+    kd = (C.c_int32 * max(1, len(key_cells)))(*[int(d) for d in key_dtypes])
+    ac = (abi.CValue * max(1, len(agg_cells)))(*[v.to_c(keep) for v in agg_cells])
+    truth = C.c_int32(0)
+    check(lib().llkv_hip_having_eval(nodes, C.c_uint32(n), kc, kd, C.c_uint32(len(key_cells)), ac, C.c_uint32(len(agg_cells)), C.byref(truth)))
+    return None if truth.value < 0 else bool(truth.value)
+
+
 def groupby(table: HipTable, predicate, keys: Sequence[int], aggs: Sequence[AggregateSpec], order_by_keys: bool = False,
-            order: Sequence["abi.GroupOrder"] = (), offset: int = 0, limit: Optional[int] = None) -> List[GroupRow]:
-    """execute_group_by_single_table (llkv-executor/src/lib.rs:4405); ``order`` / ``offset`` / ``limit``: ORDER BY output
-    columns then OFFSET / LIMIT over the groups (sort_record_batch_with_order :13762)."""
+            order: Sequence["abi.GroupOrder"] = (), offset: int = 0, limit: Optional[int] = None, having=None) -> List[GroupRow]:
+    """execute_group_by_single_table (llkv-executor/src/lib.rs:4405); ``having``: an ``abi.Having`` over the output cells
+    (evaluate_having_expr :6667); ``order`` / ``offset`` / ``limit``: ORDER BY output columns then OFFSET / LIMIT over the
+    surviving groups (sort_record_batch_with_order :13762)."""
     q = PreparedQuery(table, predicate, aggs, keys, order_by_keys)
     try:
+        if having is not None:
+            q.set_having(having)
         if order or offset or limit is not None:
             q.set_group_order(order, offset, limit)
         return q.run()
