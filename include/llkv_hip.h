@@ -598,8 +598,11 @@ uint64_t llkv_hip_query_total_groups(const llkv_hip_query *query); /* groups of 
  *   IN_LIST   Null test value → NULL; a match is Int=Int, Float=Float, mixed through `as f64`, String=String; no match and
  *             a Null item → NULL; `negated` flips TRUE and FALSE only (:6806-6884)
  *   IS_NULL   always boolean;  LITERAL  its boolean;  AND / OR / NOT three-valued (:6793-6805,6902-6937)
- * Not expressible here (the binding keeps such plans and says has_having = 1 to llkv_hip_select_route): arithmetic over
- * aggregates, the `Expr::Pred` leaf form, EXISTS.
+ * An operand may also be a small VALUE EXPRESSION over such cells (LLKV_HAVING_OPERAND_EXPR, set_having_ex) — arithmetic
+ * over aggregates, `SUM(a) / COUNT(*) > 3`: see llkv_having_token below.
+ * Not expressible here (the binding keeps such plans and says has_having = 1 to llkv_hip_select_route): CASE, a compare /
+ * NOT / IS NULL / AND / OR used as a VALUE inside an expression, the `Expr::Pred` leaf form, EXISTS, and expressions
+ * set_having_ex refuses statically (LLKV_UNSUPPORTED: a Decimal128 / Utf8 / Date32 leaf inside an expression).
  * Errors come before the filter: a finalize failure (SUM(Int64) "integer overflow", "AVG aggregate sum exceeds i64 range")
  * in a group the predicate would drop still fails the query, with the unfiltered query's status and message.
  * The sort-based and partitioned routes filter on the device before the copy-out when every operand is an Int64 key, an
@@ -625,7 +628,8 @@ typedef enum llkv_having_kind {
 typedef enum llkv_having_operand_kind {
   LLKV_HAVING_OPERAND_KEY = 0,       /* index = position in key_fields */
   LLKV_HAVING_OPERAND_AGGREGATE = 1, /* index = position in aggs       */
-  LLKV_HAVING_OPERAND_LITERAL = 2    /* literal                        */
+  LLKV_HAVING_OPERAND_LITERAL = 2,   /* literal                        */
+  LLKV_HAVING_OPERAND_EXPR = 3       /* index = entry of the expression table (set_having_ex / having_eval_ex only) */
 } llkv_having_operand_kind;
 typedef struct llkv_having_operand {
   int32_t kind; /* llkv_having_operand_kind */
@@ -649,6 +653,63 @@ llkv_status llkv_hip_query_set_having(llkv_hip_query *query, const llkv_having_n
 llkv_status llkv_hip_having_eval(const llkv_having_node *nodes, uint32_t n_nodes, const llkv_value *key_cells,
                                  const int32_t *key_dtypes, uint32_t n_keys, const llkv_value *agg_cells, uint32_t n_aggs,
                                  int32_t *truth);
+
+/* Value expressions as HAVING operands — evaluate_expr_with_plan_value_aggregates_and_row llkv-executor/src/lib.rs:7177-7516
+ * (Binary, Cast) and COALESCE.  An operand of kind LLKV_HAVING_OPERAND_EXPR names entry `index` of an expression table passed
+ * beside the nodes; it may stand as the lhs / rhs of COMPARE, the test value and the items of IN_LIST and the operand of
+ * IS_NULL.  An expression is a postfix program over a value stack (at most LLKV_HAVING_MAX_VALUE_DEPTH pending values, on the
+ * host and the device alike); exactly one value is left.  Values are Null, Integer (i64) and Float (f64):
+ *   PUSH        the leaf: a KEY, AGGREGATE or LITERAL operand (never EXPR), cell → value as above
+ *   ADD SUB MUL DIV MOD   a Null side → Null.  DIV of Integer by Integer: divisor 0 → Null; i64::MIN / -1 → Float
+ *               (MIN as f64 / -1.0); else the truncating Integer quotient.  Everything else: both sides `as f64` (an
+ *               integer rounds to nearest even), the operation in f64 (MOD: fmod, sign of the dividend); DIV / MOD by
+ *               ±0.0 → Null; DIV yields Float; the others Float if either side was Float, else Integer(result `as i64`:
+ *               saturating, NaN → 0) — NOT checked integer arithmetic: i64::MAX * 2 = i64::MAX, (2^62 + 1) % 2 = 0
+ *   SHL SHR     a Null side → Null; each side an Integer (a Float through the saturating `as i64`); wrapping shifts by the
+ *               low 6 bits of the count, SHR arithmetic; Integer
+ *   CAST_INT    Null → Null; Integer as is; Float through the saturating `as i64` (the Int32 / 16 / 8 targets do not narrow)
+ *   CAST_FLOAT  Null → Null; Integer `as f64`; Float as is (a Float32 target does not narrow)
+ *   COALESCE    pops `arg` (>= 1) values, pushes the first non-Null one in source order (Null when there is none)
+ * A leaf INSIDE an expression that is statically not Integer / Float / Boolean / Null — a Decimal128, Utf8 or Date32 key
+ * column, an aggregate with a Decimal128 cell or a computed DECIMAL argument, a Decimal128 / String / Date32 literal — makes
+ * set_having_ex answer LLKV_UNSUPPORTED (the message names the leaf): the reference raises "Non-numeric value …" or switches
+ * to exact decimal arithmetic there (:7229-7332), which the binding's CPU route produces (has_having = 1).  having_eval_ex,
+ * which sees cells only, answers the same for such a cell.  Bare operands of those types behave as before.
+ * LLKV_INVALID_ARGUMENT (the message names the node and the token): value-stack underflow, more than one value left, an
+ * empty expression, COALESCE with arg = 0, an unknown op, an expression index out of range, a leaf of kind EXPR, more than
+ * LLKV_HAVING_MAX_VALUE_DEPTH pending values.  A table entry that no operand names is ignored: neither checked nor evaluated.
+ * The old calls are the n_exprs = 0 case: an EXPR operand is out of range there.
+ * The device filter takes expression programs under the same operand rule (Int64 keys, Int64 / Float64 aggregate cells,
+ * Int / Float / Boolean / NULL literals) within its caps on nodes, operands and tokens; beyond them the host filters and
+ * the route note says why.                                                                                             */
+#define LLKV_HAVING_MAX_VALUE_DEPTH 8
+typedef enum llkv_having_token_op {
+  LLKV_HAVING_TOKEN_PUSH = 1, /* leaf */
+  LLKV_HAVING_TOKEN_ADD = 2,
+  LLKV_HAVING_TOKEN_SUB = 3,
+  LLKV_HAVING_TOKEN_MUL = 4,
+  LLKV_HAVING_TOKEN_DIV = 5,
+  LLKV_HAVING_TOKEN_MOD = 6,
+  LLKV_HAVING_TOKEN_SHL = 7,
+  LLKV_HAVING_TOKEN_SHR = 8,
+  LLKV_HAVING_TOKEN_CAST_INT = 9,
+  LLKV_HAVING_TOKEN_CAST_FLOAT = 10,
+  LLKV_HAVING_TOKEN_COALESCE = 11 /* arg = values popped (>= 1) */
+} llkv_having_token_op;
+typedef struct llkv_having_token {
+  int32_t op; /* llkv_having_token_op */
+  uint32_t arg;
+  llkv_having_operand leaf; /* PUSH */
+} llkv_having_token;
+typedef struct llkv_having_expr {
+  const llkv_having_token *tokens; /* borrowed: copied by set_having_ex */
+  uint32_t n_tokens;
+} llkv_having_expr;
+llkv_status llkv_hip_query_set_having_ex(llkv_hip_query *query, const llkv_having_node *nodes, uint32_t n_nodes,
+                                         const llkv_having_expr *exprs, uint32_t n_exprs);
+llkv_status llkv_hip_having_eval_ex(const llkv_having_node *nodes, uint32_t n_nodes, const llkv_having_expr *exprs,
+                                    uint32_t n_exprs, const llkv_value *key_cells, const int32_t *key_dtypes, uint32_t n_keys,
+                                    const llkv_value *agg_cells, uint32_t n_aggs, int32_t *truth);
 /* Status a finalize step produced for one aggregate (e.g. "integer overflow"
  * is LLKV_INVALID_ARGUMENT, llkv-aggregate/src/lib.rs:816-829).              */
 
@@ -1196,8 +1257,9 @@ typedef struct llkv_select_shape {
   int32_t has_computed_aggregates;     /* Self::has_computed_aggregates(&plan): an aggregate inside a projection    */
   uint32_t n_joins;                    /* plan.joins.len(): explicit JOIN … ON between the tables                   */
   int32_t has_having, has_distinct, has_scalar_subqueries; /* SQL breadth the GPU path leaves to the CPU routes     */
-  /* has_having: a HAVING the binding could NOT lower into llkv_hip_query_set_having (arithmetic over aggregates, `Pred`
-   * leaves, EXISTS).  A binding that lowers its HAVING there passes has_having = 0.                                   */
+  /* has_having: a HAVING the binding could NOT lower into llkv_hip_query_set_having / _ex (CASE; a compare / NOT / AND / OR
+   * used as a value; `Pred` leaves; EXISTS; an expression over Decimal128 / Utf8 / Date32 leaves, which set_having_ex
+   * refuses).  A binding that lowers its HAVING there passes has_having = 0.                                          */
 } llkv_select_shape;
 /* `*route_out`: the route the reference takes.  Returns LLKV_OK when the GPU path serves it, LLKV_UNSUPPORTED when
  * the caller keeps its CPU route (message: why), LLKV_INVALID_ARGUMENT for a shape the reference rejects.          */

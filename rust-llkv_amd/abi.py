@@ -204,7 +204,10 @@ class GroupOrder:
 
 # ----------------------------------------------------------------------------- HAVING
 HAVING_COMPARE, HAVING_IN_LIST, HAVING_IS_NULL, HAVING_LITERAL, HAVING_AND, HAVING_OR, HAVING_NOT = range(1, 8)
-HAVING_OPERAND_KEY, HAVING_OPERAND_AGGREGATE, HAVING_OPERAND_LITERAL = range(3)
+HAVING_OPERAND_KEY, HAVING_OPERAND_AGGREGATE, HAVING_OPERAND_LITERAL, HAVING_OPERAND_EXPR = range(4)
+(HAVING_TOKEN_PUSH, HAVING_TOKEN_ADD, HAVING_TOKEN_SUB, HAVING_TOKEN_MUL, HAVING_TOKEN_DIV, HAVING_TOKEN_MOD, HAVING_TOKEN_SHL,
+ HAVING_TOKEN_SHR, HAVING_TOKEN_CAST_INT, HAVING_TOKEN_CAST_FLOAT, HAVING_TOKEN_COALESCE) = range(1, 12)
+HAVING_MAX_VALUE_DEPTH = 8
 
 
 class CHavingOperand(C.Structure):
@@ -217,21 +220,61 @@ class CHavingNode(C.Structure):
                 ("list", C.POINTER(CHavingOperand))]
 
 
+class CHavingToken(C.Structure):
+    _fields_ = [("op", C.c_int32), ("arg", C.c_uint32), ("leaf", CHavingOperand)]
+
+
+class CHavingExpr(C.Structure):
+    _fields_ = [("tokens", C.POINTER(CHavingToken)), ("n_tokens", C.c_uint32)]
+
+
 @dataclass(frozen=True)
 class HavingOperand:
-    """One operand of a HAVING leaf (llkv_having_operand): an output key cell, an output aggregate cell or a literal."""
+    """One operand of a HAVING leaf (llkv_having_operand): an output key cell, an output aggregate cell, a literal — or, with
+    ``op`` set, a value expression over such operands (``Having.add`` … ``Having.coalesce``; llkv_having_expr): ``args`` are
+    its operands in source order.  A raw EXPR operand (``op`` 0, kind HAVING_OPERAND_EXPR) names entry ``index`` of a table
+    passed by hand."""
     kind: int
     index: int = 0
     literal: Optional["Literal"] = None
+    op: int = 0
+    args: Tuple["HavingOperand", ...] = ()
 
     @staticmethod
     def of(v) -> "HavingOperand":
         return v if isinstance(v, HavingOperand) else HavingOperand(HAVING_OPERAND_LITERAL, 0, Literal.of(v))
 
-    def to_c(self, keep: list) -> CHavingOperand:
+    @staticmethod
+    def value(op: int, *args) -> "HavingOperand":
+        return HavingOperand(HAVING_OPERAND_EXPR, 0, None, op, tuple(HavingOperand.of(a) for a in args))
+
+    def tokens(self) -> List[tuple]:
+        """The postfix tokens (op, arg, leaf operand or None) of a value expression; a leaf is one PUSH."""
+        if not self.op:
+            return [(HAVING_TOKEN_PUSH, 0, self)]
+        out: List[tuple] = []
+        for a in self.args:
+            out.extend(a.tokens())
+        out.append((self.op, len(self.args) if self.op == HAVING_TOKEN_COALESCE else 0, None))
+        return out
+
+    def to_c(self, keep: list, exprs: Optional[list] = None) -> CHavingOperand:
+        """``exprs``: the expression table under construction (a list of CHavingExpr) — a value expression appends its entry."""
         c = CHavingOperand()
         c.kind, c.index = self.kind, self.index
-        if self.literal is not None:
+        if self.op:
+            if exprs is None:
+                raise ValueError("a HAVING value expression needs an expression table (having_program)")
+            toks = self.tokens()
+            arr = (CHavingToken * len(toks))()
+            for t, (op, arg, leaf) in zip(arr, toks):
+                t.op, t.arg = op, arg
+                if leaf is not None:
+                    t.leaf = leaf.to_c(keep)
+            keep.append(arr)
+            c.index = len(exprs)
+            exprs.append(CHavingExpr(arr, len(toks)))
+        elif self.literal is not None:
             c.literal = self.literal.to_c(keep)
         return c
 
@@ -259,6 +302,48 @@ class Having:
     @staticmethod
     def agg(index: int) -> HavingOperand:
         return HavingOperand(HAVING_OPERAND_AGGREGATE, index)
+
+    # value expressions over key / aggregate cells and literals (llkv_having_token): usable wherever compare / in_list / is_null
+    # take an operand
+    @staticmethod
+    def add(a, b) -> HavingOperand:
+        return HavingOperand.value(HAVING_TOKEN_ADD, a, b)
+
+    @staticmethod
+    def sub(a, b) -> HavingOperand:
+        return HavingOperand.value(HAVING_TOKEN_SUB, a, b)
+
+    @staticmethod
+    def mul(a, b) -> HavingOperand:
+        return HavingOperand.value(HAVING_TOKEN_MUL, a, b)
+
+    @staticmethod
+    def div(a, b) -> HavingOperand:
+        return HavingOperand.value(HAVING_TOKEN_DIV, a, b)
+
+    @staticmethod
+    def mod(a, b) -> HavingOperand:
+        return HavingOperand.value(HAVING_TOKEN_MOD, a, b)
+
+    @staticmethod
+    def shl(a, b) -> HavingOperand:
+        return HavingOperand.value(HAVING_TOKEN_SHL, a, b)
+
+    @staticmethod
+    def shr(a, b) -> HavingOperand:
+        return HavingOperand.value(HAVING_TOKEN_SHR, a, b)
+
+    @staticmethod
+    def cast_int(x) -> HavingOperand:
+        return HavingOperand.value(HAVING_TOKEN_CAST_INT, x)
+
+    @staticmethod
+    def cast_float(x) -> HavingOperand:
+        return HavingOperand.value(HAVING_TOKEN_CAST_FLOAT, x)
+
+    @staticmethod
+    def coalesce(*xs) -> HavingOperand:
+        return HavingOperand.value(HAVING_TOKEN_COALESCE, *xs)
 
     @staticmethod
     def compare(lhs, op: int, rhs) -> "Having":
@@ -295,27 +380,40 @@ class Having:
         out.append(self)
         return out
 
-    def to_c(self, keep: list) -> CHavingNode:
+    def to_c(self, keep: list, exprs: Optional[list] = None) -> CHavingNode:
         c = CHavingNode()
         c.kind, c.cmp_op, c.negated, c.literal = self.kind, self.cmp_op, int(bool(self.negated)), int(bool(self.literal))
         c.n_children, c.n_list = self.n_children, len(self.items)
         if self.lhs is not None:
-            c.lhs = self.lhs.to_c(keep)
+            c.lhs = self.lhs.to_c(keep, exprs)
         if self.rhs is not None:
-            c.rhs = self.rhs.to_c(keep)
+            c.rhs = self.rhs.to_c(keep, exprs)
         if self.items:
-            arr = (CHavingOperand * len(self.items))(*[i.to_c(keep) for i in self.items])
+            arr = (CHavingOperand * len(self.items))(*[i.to_c(keep, exprs) for i in self.items])
             keep.append(arr)
             c.list = arr
         return c
 
 
-def having_program(having, keep: list):
-    """(CHavingNode array, n) of a Having tree, a sequence of raw nodes, or None / () (n = 0: clears the HAVING)."""
+def having_program(having, keep: list, exprs=None):
+    """(CHavingNode array, n, CHavingExpr array, n_exprs) of a Having tree, a sequence of raw nodes, or None / () (n = 0: clears
+    the HAVING).  The expression table holds one entry per value expression among the operands, in the order met; ``exprs``: a
+    table written out by hand (a sequence of token lists ``[(op, arg, leaf operand or None), …]``) that raw EXPR operands
+    index — it comes first."""
     nodes = [] if having is None else having.postfix() if isinstance(having, Having) else list(having)
-    arr = (CHavingNode * max(1, len(nodes)))(*[n.to_c(keep) for n in nodes])
-    keep.append(arr)
-    return arr, len(nodes)
+    table: list = []
+    for toks in exprs or ():
+        arr = (CHavingToken * max(1, len(toks)))()
+        for t, (op, arg, leaf) in zip(arr, toks):
+            t.op, t.arg = op, arg
+            if leaf is not None:
+                t.leaf = HavingOperand.of(leaf).to_c(keep)
+        keep.append(arr)
+        table.append(CHavingExpr(arr, len(toks)))
+    arr = (CHavingNode * max(1, len(nodes)))(*[n.to_c(keep, table) for n in nodes])
+    ex = (CHavingExpr * max(1, len(table)))(*table)
+    keep.extend((arr, ex))
+    return arr, len(nodes), ex, len(table)
 
 
 class CColumnDesc(C.Structure):

@@ -993,7 +993,7 @@ int Query::apply_order(const GroupOrderDone *done) {
       const uint64_t n = result_rows();
       for (uint64_t r = 0; r < n; ++r) {
         int32_t truth = 0;
-        const int rc = having_eval(having.nodes.data(), (uint32_t)having.nodes.size(), [&](const llkv_having_operand &o, llkv_value *cell, int32_t *key_dtype) {
+        const int rc = having_eval(having.nodes.data(), (uint32_t)having.nodes.size(), having.exprs.data(), (uint32_t)having.exprs.size(), [&](const llkv_having_operand &o, llkv_value *cell, int32_t *key_dtype) {
           if (o.kind != LLKV_HAVING_OPERAND_KEY) return cell_value(r, o.index, cell);
           *key_dtype = key_dtype_of(o.index);
           return cell_key(r, o.index, cell);
@@ -1030,8 +1030,9 @@ int Query::apply_order(const GroupOrderDone *done) {
 // The dtype of key column `key` (what types a key cell under HAVING: cell_key hands Date32 / Boolean cells over as LLKV_DT_INT64).
 int32_t Query::key_dtype_of(uint32_t key) const {
   if (lazy.active) return key < lazy.key_cols.size() ? lazy.key_cols[key]->dtype : (int32_t)LLKV_DT_INT64;
-  if (key >= plan.key_fields.size()) return LLKV_DT_INT64;
-  auto it = table->cols.find(plan.key_fields[key]);
+  const std::vector<uint32_t> &fields = sorted ? sorted_groupby_key_fields(sorted) : plan.key_fields; // (before the first finish)
+  if (key >= fields.size()) return LLKV_DT_INT64;
+  auto it = table->cols.find(fields[key]);
   return it == table->cols.end() ? (int32_t)LLKV_DT_INT64 : it->second.info.dtype;
 }
 
@@ -1331,7 +1332,48 @@ llkv_status llkv_hip_query_set_group_order(llkv_hip_query *query, const llkv_gro
   return LLKV_OK;
 }
 
-llkv_status llkv_hip_query_set_having(llkv_hip_query *query, const llkv_having_node *nodes, uint32_t n_nodes) {
+// A leaf inside a HAVING expression that is statically not Integer / Float / Boolean / Null: the reference raises "Non-numeric
+// value …" or switches to exact decimal arithmetic there (llkv-executor/src/lib.rs:7229-7357); the binding's CPU route produces that.
+// Only the entries an operand of a node names are looked at (having_validate has checked exactly those).
+static int having_expr_leaves_numeric(const Query *q, const llkv_having_node *nodes, uint32_t n_nodes, const llkv_having_expr *exprs, uint32_t n_exprs, std::string *err) {
+  const LoweredPlan &plan = q->sorted ? *sorted_groupby_plan(q->sorted) : q->plan;
+  std::vector<uint8_t> named(n_exprs, 0);
+  auto name = [&](const llkv_having_operand &o) { if (o.kind == LLKV_HAVING_OPERAND_EXPR && o.index < n_exprs) named[o.index] = 1; };
+  for (uint32_t i = 0; i < n_nodes; ++i) {
+    const llkv_having_node &nd = nodes[i];
+    if (nd.kind != LLKV_HAVING_COMPARE && nd.kind != LLKV_HAVING_IN_LIST && nd.kind != LLKV_HAVING_IS_NULL) continue;
+    name(nd.lhs);
+    if (nd.kind == LLKV_HAVING_COMPARE) name(nd.rhs);
+    for (uint32_t j = 0; nd.kind == LLKV_HAVING_IN_LIST && j < nd.n_list; ++j) name(nd.list[j]);
+  }
+  for (uint32_t x = 0; x < n_exprs; ++x)
+    for (uint32_t t = 0; named[x] && t < exprs[x].n_tokens; ++t) {
+      const llkv_having_token &tk = exprs[x].tokens[t];
+      if (tk.op != LLKV_HAVING_TOKEN_PUSH) continue;
+      const llkv_having_operand &o = tk.leaf;
+      std::string what;
+      if (o.kind == LLKV_HAVING_OPERAND_KEY && o.index < q->n_user_keys) {
+        const int32_t dt = q->key_dtype_of(o.index);
+        if (dt == LLKV_DT_DECIMAL128 || dt == LLKV_DT_UTF8 || dt == LLKV_DT_DATE32) what = "key " + std::to_string(o.index) + " is a " + dtype_name(dt) + " column";
+      } else if (o.kind == LLKV_HAVING_OPERAND_AGGREGATE && o.index < q->n_user_aggs && o.index < plan.aggs.size()) {
+        const AggOut &a = plan.aggs[o.index];
+        if (a.digits_lane >= 0) what = "aggregate " + std::to_string(o.index) + " has a computed DECIMAL argument";
+        else if (a.fin == AggFinal::SumDec || a.fin == AggFinal::TotalDec || a.fin == AggFinal::AvgDec || a.fin == AggFinal::MinDec || a.fin == AggFinal::MaxDec)
+          what = "aggregate " + std::to_string(o.index) + " is a Decimal128 cell";
+      } else if (o.kind == LLKV_HAVING_OPERAND_LITERAL) {
+        if (o.literal.tag == LLKV_LIT_DECIMAL128) what = "a Decimal128 literal";
+        else if (o.literal.tag == LLKV_LIT_STRING) what = "a string literal";
+        else if (o.literal.tag == LLKV_LIT_DATE32) what = "a Date32 literal";
+      }
+      if (!what.empty()) {
+        *err = "HAVING expression " + std::to_string(x) + " token " + std::to_string(t) + " (PUSH): " + what + " inside an expression (not Integer / Float / Boolean / NULL)";
+        return LLKV_UNSUPPORTED;
+      }
+    }
+  return LLKV_OK;
+}
+
+llkv_status llkv_hip_query_set_having_ex(llkv_hip_query *query, const llkv_having_node *nodes, uint32_t n_nodes, const llkv_having_expr *exprs, uint32_t n_exprs) {
   Query *q = reinterpret_cast<Query *>(query);
   if (!q) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "query is NULL");
   if (n_nodes && !nodes) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "nodes is NULL");
@@ -1340,10 +1382,15 @@ llkv_status llkv_hip_query_set_having(llkv_hip_query *query, const llkv_having_n
   if (q->n_launched != q->n_collected) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "executions in flight");
   if (n_nodes) {
     std::string err;
-    if (int rc = having_validate(nodes, n_nodes, q->n_user_keys, q->n_user_aggs, &err)) return (llkv_status)set_error(rc, err);
+    if (int rc = having_validate(nodes, n_nodes, exprs, n_exprs, q->n_user_keys, q->n_user_aggs, &err)) return (llkv_status)set_error(rc, err);
+    if (int rc = having_expr_leaves_numeric(q, nodes, n_nodes, exprs, n_exprs, &err)) return (llkv_status)set_error(rc, err);
   }
-  q->having.assign(nodes, n_nodes);
+  q->having.assign(nodes, n_nodes, exprs, n_exprs);
   return LLKV_OK;
+}
+
+llkv_status llkv_hip_query_set_having(llkv_hip_query *query, const llkv_having_node *nodes, uint32_t n_nodes) {
+  return llkv_hip_query_set_having_ex(query, nodes, n_nodes, nullptr, 0);
 }
 
 uint64_t llkv_hip_query_total_groups(const llkv_hip_query *query) {

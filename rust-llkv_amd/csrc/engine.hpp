@@ -419,24 +419,28 @@ struct GroupOrderDone {
 };
 
 // HAVING over the output cells of a GROUP BY (llkv_hip_query_set_having; evaluate_having_expr llkv-executor/src/lib.rs:6667-7006;
-// the rules: having_rules.h).  An owned copy of the caller's program: IN lists and string literals live in the object.
+// the rules: having_rules.h).  An owned copy of the caller's program: IN lists, string literals and expressions live in the object.
 struct HavingProgram {
   std::vector<llkv_having_node> nodes;
   std::deque<std::vector<llkv_having_operand>> lists;
   std::deque<std::string> strings;
+  std::vector<llkv_having_expr> exprs; // the expression table of set_having_ex: what an EXPR operand's index names
+  std::deque<std::vector<llkv_having_token>> tokens;
   HavingProgram() = default;
   HavingProgram(const HavingProgram &) = delete;
   HavingProgram &operator=(const HavingProgram &) = delete;
   bool active() const { return !nodes.empty(); }
-  void assign(const llkv_having_node *src, uint32_t n);
+  void assign(const llkv_having_node *src, uint32_t n, const llkv_having_expr *ex = nullptr, uint32_t n_ex = 0);
 };
 // LLKV_OK, or LLKV_INVALID_ARGUMENT with *err naming the node: unknown kinds, operators and literal tags, indices out of range,
 // stack underflow, n_children = 0, more or fewer than one value left, a stack deeper than kHavingMaxDepth.
-int having_validate(const llkv_having_node *nodes, uint32_t n, uint32_t n_keys, uint32_t n_aggs, std::string *err);
+// Expressions (`exprs`, what EXPR operands name): value-stack underflow, more than one value left, COALESCE with arg = 0, unknown
+// ops, an EXPR leaf, an index out of range, more than kHavingMaxValueDepth pending values — the message names the expression and the token.
+int having_validate(const llkv_having_node *nodes, uint32_t n, const llkv_having_expr *exprs, uint32_t n_exprs, uint32_t n_keys, uint32_t n_aggs, std::string *err);
 // The host evaluator (the one of llkv_hip_having_eval and of Query::apply_order): cell(operand, &v, &key_dtype) yields the
 // finalized cell of a KEY / AGGREGATE operand and, for a key, its column's dtype (what types the cell).  *truth: HavingTruth.
 using HavingCell = std::function<int(const llkv_having_operand &, llkv_value *, int32_t *)>;
-int having_eval(const llkv_having_node *nodes, uint32_t n, const HavingCell &cell, int32_t *truth);
+int having_eval(const llkv_having_node *nodes, uint32_t n, const llkv_having_expr *exprs, uint32_t n_exprs, const HavingCell &cell, int32_t *truth);
 // Whether the flag kernel can evaluate the program over the groups of `lz` (else *why): every operand an Int64 key column, an
 // aggregate with an i64 / f64 cell, or an Int / Float / Boolean / NULL literal, within the kernel's caps.
 bool having_device_ok(const HavingProgram &h, const LazyGroups &lz, std::string *why);
@@ -491,6 +495,8 @@ const LoweredPlan *part_groupby_plan(const PartGroupBy *p);
 // handed to it instead (sorted_groupby_partitioned() says so).
 struct SortedGroupBy;
 bool sorted_groupby_partitioned(const SortedGroupBy *s);
+const std::vector<uint32_t> &sorted_groupby_key_fields(const SortedGroupBy *s);
+const LoweredPlan *sorted_groupby_plan(const SortedGroupBy *s); // the plan whose aggs finalize the groups' lanes
 void join_group_state_free(struct JoinGroupState *s); // join_group.cpp
 struct KeySetView;
 // `key_set` / `key_set_field`: one more conjunct of the selection — the integer column must be in the key set (join → GROUP BY,

@@ -2,10 +2,12 @@
 // output order ([n][k] lanes, [n_keys][n] key cells and validity), before ORDER BY / LIMIT and before anything is copied out
 // (evaluate_having_expr llkv-executor/src/lib.rs:6667-7006 between the output rows and the sort, :5305-5355).
 //   flags     having_flag_kernel     one thread per group: the cells the program names (group_cell.hip.h: agg_cell, the device finalize
-//                                    the order keys are made from), the postfix program over two bit stacks (having_rules.h, the rules
-//                                    of the host evaluator), keep = the predicate is TRUE.  The same pass records, per aggregate
-//                                    whose finalize can fail, the first failing group over ALL groups: the reference finalizes every
-//                                    group before HAVING looks at any.
+//                                    the order keys are made from — each named aggregate finalized ONCE per group, however often the
+//                                    program names it), the postfix program over two bit stacks, an expression operand
+//                                    (arithmetic over aggregates, evaluate_expr_with_plan_value_aggregates_and_row :7177-7516) over
+//                                    a value stack of eight named register slots (having_rules.h, the rules of the host evaluator),
+//                                    keep = the predicate is TRUE.  The same pass records, per aggregate whose finalize can fail, the
+//                                    first failing group over ALL groups: the reference finalizes every group before HAVING looks at any.
 //   scan      hj_exclusive_scan_u32  positions of the survivors; the last entry is their count
 //   compact   having_compact_kernel  survivors' lane rows and key cells → compact arrays, relative order kept (ties under ORDER BY and
 //                                    the result without one are those of filtering the plain result)
@@ -29,13 +31,18 @@ namespace {
 constexpr uint32_t kHavingBlock = 256;
 constexpr int kHavingMaxNodes = 32;    // program nodes the flag kernel takes (its kernel-argument block holds the program)
 constexpr int kHavingMaxOperands = 48; // operands of all nodes together (IN lists included)
-constexpr int kHavingMaxAggs = 8;      // distinct aggregates among them
+constexpr int kHavingMaxAggs = 8;      // distinct aggregates among them (the leaves of expressions included)
+constexpr int kHavingMaxTokens = 64;   // tokens of all expressions together
 
-enum DevOperandKind : int32_t { kOpKey = 0, kOpAgg = 1, kOpValue = 2 };
+enum DevOperandKind : int32_t { kOpKey = 0, kOpAgg = 1, kOpValue = 2, kOpExpr = 3 };
 struct DevOperand {
   int32_t kind;
-  int32_t index; // key: the key; aggregate: its entry of HavingParams::agg; value: the literal's HavingTag
-  uint64_t bits; // value: the Integer / Float bits
+  int32_t index; // key: the key; aggregate: its entry of HavingParams::agg; value: the literal's HavingTag; expression: its first token
+  uint64_t bits; // value: the Integer / Float bits; expression: the number of its tokens
+};
+struct DevToken {
+  int32_t op;  // llkv_having_token_op
+  int32_t arg; // PUSH: the leaf's entry of HavingParams::operand; COALESCE: values popped
 };
 struct DevNode {
   int32_t kind;    // llkv_having_kind
@@ -56,7 +63,11 @@ struct HavingParams {
   DevNode node[kHavingMaxNodes];
   DevOperand operand[kHavingMaxOperands];
   AggCell agg[kHavingMaxAggs];
+  DevToken token[kHavingMaxTokens];
 };
+// The expressions travel in the kernel-argument block like the rest of the program (scalar loads, uniform over the wave): 64 tokens
+// of 8 bytes bring it to 2 560 bytes, under the 4 KiB kernel-argument limit, so no device buffer and no copy per launch.
+static_assert(sizeof(HavingParams) <= 4096, "the HAVING program must fit the kernel-argument block");
 
 uint32_t grid_for(uint64_t n) {
   const uint64_t want = (n + kHavingBlock - 1) / kHavingBlock;
@@ -64,39 +75,71 @@ uint32_t grid_for(uint64_t n) {
   return (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
 }
 
-__device__ inline HavingValue operand_value(const HavingParams &p, const DevOperand &o, const uint64_t *g, uint64_t i) {
+// The finalized cells of the aggregates the program names, one per HavingParams::agg entry, so that each is finalized once per
+// group.  The entry is picked at run time, which registers cannot do without a select chain the optimizer turns into a selected
+// address (scratch): the cell bits live in the thread's column of an LDS array ([entry][thread]: consecutive lanes, consecutive
+// banks; 16 KiB per block; only the owning thread touches its column, so no barrier), the eight 2-bit tags in one register.
+struct AggCache {
+  uint64_t *bits; // this thread's column: entry a at bits[a * kHavingBlock]
+  uint32_t tags = 0;
+  __device__ __forceinline__ void set(int a, const HavingValue &v) {
+    bits[a * kHavingBlock] = v.bits;
+    tags |= (uint32_t)v.tag << (2 * a);
+  }
+  __device__ __forceinline__ HavingValue get(int a) const { return {(int32_t)((tags >> (2 * a)) & 3u), bits[a * kHavingBlock]}; }
+};
+static_assert(kHavingMaxAggs == 8 && kHvFloat < 4, "AggCache: eight entries, 2-bit tags");
+static_assert(kHavingMaxValueDepth == 8, "HavingValueStack has eight slots");
+
+__device__ __forceinline__ HavingValue leaf_value(const HavingParams &p, const DevOperand &o, const AggCache &cells, uint64_t i) {
   if (o.kind == kOpValue) return {o.index, o.bits};
   if (o.kind == kOpKey) { // an Int64 key column
     if (!p.kvalid[(uint64_t)o.index * p.n + i]) return {kHvNull, 0};
     return {kHvInteger, (uint64_t)p.kv[(uint64_t)o.index * p.n + i]};
   }
-  const AggCell &a = p.agg[o.index];
-  bool null;
-  uint64_t c0, c1;
-  agg_cell(a, g, &null, &c0, &c1);
-  if (null) return {kHvNull, 0};
-  return {agg_cell_type((AggFinal)a.fin) == kCellF64 ? kHvFloat : kHvInteger, c0};
+  return cells.get(o.index);
+}
+
+__device__ __forceinline__ HavingValue operand_value(const HavingParams &p, const DevOperand &o, const AggCache &cells, uint64_t i) {
+  if (o.kind != kOpExpr) return leaf_value(p, o, cells, i);
+  HavingValueStack st;
+  const int end = o.index + (int)o.bits;
+  for (int t = o.index; t < end; ++t) {
+    const DevToken tk = p.token[t];
+    if (tk.op == LLKV_HAVING_TOKEN_PUSH) st.push(leaf_value(p, p.operand[tk.arg], cells, i));
+    else having_token(st, tk.op, (uint32_t)tk.arg);
+  }
+  return st.pop();
 }
 
 __global__ __launch_bounds__(kHavingBlock) void having_flag_kernel(HavingParams p) {
+  __shared__ uint64_t cell_bits[kHavingMaxAggs * kHavingBlock];
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += stride) {
     const uint64_t *g = p.lanes + i * (uint64_t)p.k;
     for (int e = 0; e < p.n_err; ++e)
       if (agg_finalize_fails(g, p.err_lane[e], p.err_count_lane[e])) atomicMin(p.first_bad + e, (unsigned long long)i);
+    AggCache cells{cell_bits + threadIdx.x};
+#pragma unroll 1
+    for (int a = 0; a < p.n_aggs; ++a) {
+      bool null;
+      uint64_t c0, c1;
+      agg_cell(p.agg[a], g, &null, &c0, &c1);
+      cells.set(a, null ? HavingValue{kHvNull, 0} : HavingValue{agg_cell_type((AggFinal)p.agg[a].fin) == kCellF64 ? kHvFloat : kHvInteger, c0});
+    }
     HavingStack st;
     for (int j = 0; j < p.n_nodes; ++j) {
       const DevNode &nd = p.node[j];
       switch (nd.kind) {
       case LLKV_HAVING_COMPARE:
-        st.push(having_compare(nd.arg, operand_value(p, p.operand[nd.operand], g, i), operand_value(p, p.operand[nd.operand + 1], g, i)));
+        st.push(having_compare(nd.arg, operand_value(p, p.operand[nd.operand], cells, i), operand_value(p, p.operand[nd.operand + 1], cells, i)));
         break;
       case LLKV_HAVING_IN_LIST: {
-        const HavingValue t = operand_value(p, p.operand[nd.operand], g, i);
+        const HavingValue t = operand_value(p, p.operand[nd.operand], cells, i);
         if (t.tag == kHvNull) { st.push(kHavingNull); break; }
         bool found = false, has_null = false;
         for (int x = 0; x < nd.n_list && !found; ++x) {
-          const HavingValue item = operand_value(p, p.operand[nd.operand + 1 + x], g, i);
+          const HavingValue item = operand_value(p, p.operand[nd.operand + 1 + x], cells, i);
           if (item.tag == kHvNull) has_null = true;
           else found = having_in_match(t, item);
         }
@@ -104,7 +147,7 @@ __global__ __launch_bounds__(kHavingBlock) void having_flag_kernel(HavingParams 
         break;
       }
       case LLKV_HAVING_IS_NULL:
-        st.push((operand_value(p, p.operand[nd.operand], g, i).tag == kHvNull) != (nd.arg != 0) ? kHavingTrue : kHavingFalse);
+        st.push((operand_value(p, p.operand[nd.operand], cells, i).tag == kHvNull) != (nd.arg != 0) ? kHavingTrue : kHavingFalse);
         break;
       case LLKV_HAVING_LITERAL: st.push(nd.arg ? kHavingTrue : kHavingFalse); break;
       case LLKV_HAVING_AND: st.push(st.pop_and((uint32_t)nd.arg)); break;
@@ -154,6 +197,7 @@ bool lower_operand(const llkv_having_operand &o, const LazyGroups &lz, std::vect
     out->index = (int32_t)at;
     return true;
   }
+  case LLKV_HAVING_OPERAND_EXPR: *why = "an expression as a leaf"; return false; // (having_validate refuses it)
   default:
     out->kind = kOpValue;
     switch (o.literal.tag) {
@@ -173,10 +217,27 @@ bool lower_program(const HavingProgram &h, const LazyGroups &lz, HavingParams *p
   if (h.nodes.size() > (size_t)kHavingMaxNodes) { *why = "more than " + std::to_string(kHavingMaxNodes) + " nodes"; return false; }
   if (lz.n >= (1ull << 32)) { *why = "2^32 groups or more"; return false; }
   std::vector<int> aggs;
-  int n_ops = 0;
-  auto add = [&](const llkv_having_operand &o) {
+  int n_ops = 0, n_tokens = 0;
+  struct Pending { int token; const llkv_having_expr *e; };
+  std::vector<Pending> pending; // expressions whose tokens and leaves are lowered after the nodes' own operands
+  auto add_leaf = [&](const llkv_having_operand &o) {
     if (n_ops == kHavingMaxOperands) { *why = "more than " + std::to_string(kHavingMaxOperands) + " operands"; return false; }
     return lower_operand(o, lz, &aggs, &p->operand[n_ops++], why);
+  };
+  // an expression operand: its own entry now (a node's operands are consecutive entries: lhs, rhs / list items), its tokens and
+  // their leaves — more entries of p->operand, which only the tokens index — after the nodes
+  auto add = [&](const llkv_having_operand &o) {
+    if (o.kind != LLKV_HAVING_OPERAND_EXPR) return add_leaf(o);
+    if (n_ops == kHavingMaxOperands) { *why = "more than " + std::to_string(kHavingMaxOperands) + " operands"; return false; }
+    const llkv_having_expr &e = h.exprs[o.index];
+    if ((size_t)n_tokens + e.n_tokens > (size_t)kHavingMaxTokens) { *why = "more than " + std::to_string(kHavingMaxTokens) + " expression tokens"; return false; }
+    pending.push_back({n_tokens, &e});
+    DevOperand &d = p->operand[n_ops++];
+    d.kind = kOpExpr;
+    d.index = n_tokens;
+    d.bits = e.n_tokens;
+    n_tokens += (int)e.n_tokens;
+    return true;
   };
   for (size_t j = 0; j < h.nodes.size(); ++j) {
     const llkv_having_node &nd = h.nodes[j];
@@ -205,6 +266,16 @@ bool lower_program(const HavingProgram &h, const LazyGroups &lz, HavingParams *p
     default: d.arg = 0; break;
     }
   }
+  for (const Pending &pd : pending)
+    for (uint32_t t = 0; t < pd.e->n_tokens; ++t) {
+      const llkv_having_token &tk = pd.e->tokens[t];
+      DevToken &d = p->token[pd.token + (int)t];
+      d.op = tk.op;
+      d.arg = (int32_t)tk.arg;
+      if (tk.op != LLKV_HAVING_TOKEN_PUSH) continue;
+      d.arg = n_ops;
+      if (!add_leaf(tk.leaf)) return false;
+    }
   p->n_nodes = (int32_t)h.nodes.size();
   p->n_aggs = (int32_t)aggs.size();
   for (size_t a = 0; a < aggs.size(); ++a) agg_cell_of(lz.plan->aggs[(size_t)aggs[a]], &p->agg[a]);

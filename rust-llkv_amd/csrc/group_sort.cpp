@@ -45,6 +45,8 @@ struct SortedGroupBy {
 
 void sorted_groupby_free(SortedGroupBy *s) { delete s; }
 bool sorted_groupby_partitioned(const SortedGroupBy *s) { return s && s->part; }
+const std::vector<uint32_t> &sorted_groupby_key_fields(const SortedGroupBy *s) { return s->key_fields; }
+const LoweredPlan *sorted_groupby_plan(const SortedGroupBy *s) { return s->part ? part_groupby_plan(s->part) : &s->red_plan; }
 
 // ---- what the sort-based and the partitioned run (group_part.cpp) share ----------------------------------------------------
 void lazy_groups_begin(LazyGroups *out, const LoweredPlan &plan, const Table &t, const std::vector<uint32_t> &key_fields) {

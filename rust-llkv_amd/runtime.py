@@ -57,6 +57,9 @@ def lib():
     L.llkv_hip_free.restype = None
     L.llkv_hip_query_set_group_order.argtypes = [C.c_void_p, C.POINTER(abi.CGroupOrderKey), C.c_uint32, C.c_uint64, C.c_uint64]
     L.llkv_hip_query_set_having.argtypes = [C.c_void_p, C.POINTER(abi.CHavingNode), C.c_uint32]
+    L.llkv_hip_query_set_having_ex.argtypes = [C.c_void_p, C.POINTER(abi.CHavingNode), C.c_uint32, C.POINTER(abi.CHavingExpr), C.c_uint32]
+    L.llkv_hip_having_eval_ex.argtypes = [C.POINTER(abi.CHavingNode), C.c_uint32, C.POINTER(abi.CHavingExpr), C.c_uint32, C.POINTER(abi.CValue),
+                                          C.POINTER(C.c_int32), C.c_uint32, C.POINTER(abi.CValue), C.c_uint32, C.POINTER(C.c_int32)]
     L.llkv_hip_having_eval.argtypes = [C.POINTER(abi.CHavingNode), C.c_uint32, C.POINTER(abi.CValue), C.POINTER(C.c_int32), C.c_uint32,
                                        C.POINTER(abi.CValue), C.c_uint32, C.POINTER(C.c_int32)]
     L.llkv_hip_query_total_groups.restype = C.c_uint64
@@ -693,12 +696,17 @@ class PreparedQuery:
         lim = (1 << 64) - 1 if limit is None else int(limit)
         check(lib().llkv_hip_query_set_group_order(self._h, terms, C.c_uint32(len(order)), C.c_uint64(int(offset)), C.c_uint64(lim)))
 
-    def set_having(self, having=None):
-        """HAVING over the output cells (llkv_hip_query_set_having): an ``abi.Having`` tree or a sequence of raw postfix nodes,
-        from the next finish / collect / merge_groups on — before the order of set_group_order.  None or () clears it."""
+    def set_having(self, having=None, exprs=None, legacy: bool = False):
+        """HAVING over the output cells (llkv_hip_query_set_having_ex): an ``abi.Having`` tree — its operands may be value
+        expressions (``Having.div(Having.agg(0), Having.agg(1))``) — or a sequence of raw postfix nodes (``exprs``: the raw
+        expression table their EXPR operands index), from the next finish / collect / merge_groups on — before the order of
+        set_group_order.  None or () clears it.  ``legacy``: through llkv_hip_query_set_having, which takes no expressions."""
         keep: list = []
-        nodes, n = abi.having_program(having, keep)
-        check(lib().llkv_hip_query_set_having(self._h, nodes, C.c_uint32(n)))
+        nodes, n, ex, n_ex = abi.having_program(having, keep, exprs)
+        if legacy:
+            check(lib().llkv_hip_query_set_having(self._h, nodes, C.c_uint32(n)))
+        else:
+            check(lib().llkv_hip_query_set_having_ex(self._h, nodes, C.c_uint32(n), ex, C.c_uint32(n_ex)))
 
     @property
     def total_groups(self) -> int:
@@ -745,16 +753,22 @@ def aggregate(table: HipTable, predicate, aggs: Sequence[AggregateSpec]) -> List
         q.close()
 
 
-def having_eval(having, key_cells: Sequence["abi.Value"] = (), key_dtypes: Sequence[int] = (), agg_cells: Sequence["abi.Value"] = ()):
-    """The HAVING rules over one row of cells, host only (llkv_hip_having_eval — the evaluator of the query's host path): True,
-    False or None (NULL).  ``key_dtypes``: the key COLUMNS' dtypes (a Date32 / Boolean key cell arrives as Int64)."""
+def having_eval(having, key_cells: Sequence["abi.Value"] = (), key_dtypes: Sequence[int] = (), agg_cells: Sequence["abi.Value"] = (), exprs=None,
+                legacy: bool = False):
+    """The HAVING rules over one row of cells, host only (llkv_hip_having_eval_ex — the evaluator of the query's host path): True,
+    False or None (NULL).  ``key_dtypes``: the key COLUMNS' dtypes (a Date32 / Boolean key cell arrives as Int64).  ``exprs``: a
+    raw expression table (abi.having_program); ``legacy``: through llkv_hip_having_eval, which takes no expressions."""
     keep: list = []
-    nodes, n = abi.having_program(having, keep)
+    nodes, n, ex, n_ex = abi.having_program(having, keep, exprs)
     kc = (abi.CValue * max(1, len(key_cells)))(*[v.to_c(keep) for v in key_cells])
     kd = (C.c_int32 * max(1, len(key_cells)))(*[int(d) for d in key_dtypes])
     ac = (abi.CValue * max(1, len(agg_cells)))(*[v.to_c(keep) for v in agg_cells])
     truth = C.c_int32(0)
-    check(lib().llkv_hip_having_eval(nodes, C.c_uint32(n), kc, kd, C.c_uint32(len(key_cells)), ac, C.c_uint32(len(agg_cells)), C.byref(truth)))
+    if legacy:
+        check(lib().llkv_hip_having_eval(nodes, C.c_uint32(n), kc, kd, C.c_uint32(len(key_cells)), ac, C.c_uint32(len(agg_cells)), C.byref(truth)))
+    else:
+        check(lib().llkv_hip_having_eval_ex(nodes, C.c_uint32(n), ex, C.c_uint32(n_ex), kc, kd, C.c_uint32(len(key_cells)), ac, C.c_uint32(len(agg_cells)),
+                                            C.byref(truth)))
     return None if truth.value < 0 else bool(truth.value)
 
 

@@ -3,9 +3,10 @@
 (2 M groups: partitioned route), l_shipdate (≈2500 groups: shared-image kernel) and the wide-state Q1 shape with every
 aggregate doubled — inputs resident in HBM.  The *_top10 cases add ORDER BY sum(l_quantity) DESC LIMIT 10
 (llkv_hip_query_set_group_order) and print the route note, which says where the order ran.
---having q18|half|all adds the l_orderkey and l_partkey cases with a HAVING (llkv_hip_query_set_having): q18 = TPC-H Q18's
+--having q18|half|avg|all adds the l_orderkey and l_partkey cases with a HAVING (llkv_hip_query_set_having_ex): q18 = TPC-H Q18's
 SUM(l_quantity) > 300 (a few dozen groups of l_orderkey survive), half = key <= the key column's median (about half of the
-groups survive); their route notes say where the HAVING ran."""
+groups survive), avg = arithmetic over aggregates, SUM(l_quantity) / COUNT(*) > c (c = 40 for l_orderkey, 30 for l_partkey: a few
+percent of the groups survive); their route notes say where the HAVING ran."""
 import importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,7 +17,7 @@ having_arg = ""
 if "--having" in sys.argv:
     at = sys.argv.index("--having")
     having_arg = sys.argv[at + 1]
-    assert having_arg in ("q18", "half", "all"), having_arg
+    assert having_arg in ("q18", "half", "avg", "all"), having_arg
     del sys.argv[at:at + 2]
 sf = sys.argv[1] if len(sys.argv) > 1 else "sf10"
 rt.init(0)
@@ -44,9 +45,12 @@ cases = [("by_orderkey", [S["l_orderkey"][0]], narrow, None), ("by_partkey", [S[
          ("q1_wide_state", [S["l_returnflag"][0], S["l_linestatus"][0]], wide, None),
          ("by_orderkey_top10", [S["l_orderkey"][0]], narrow, None), ("by_partkey_top10", [S["l_partkey"][0]], narrow, None)]
 H = getattr(abi, "Having", None)
-for kind in (("q18", "half") if having_arg == "all" else (having_arg,) if having_arg else ()):
+for kind in (("q18", "half", "avg") if having_arg == "all" else (having_arg,) if having_arg else ()):
     for key in ("l_orderkey", "l_partkey"):
-        having = H.compare(H.agg(1), abi.CMP_GT, 300) if kind == "q18" else H.compare(H.key(0), abi.CMP_LT_EQ, int(np.median(li[key])))
+        if kind == "avg":
+            having = H.compare(H.div(H.agg(1), H.agg(0)), abi.CMP_GT, 40 if key == "l_orderkey" else 30)
+        else:
+            having = H.compare(H.agg(1), abi.CMP_GT, 300) if kind == "q18" else H.compare(H.key(0), abi.CMP_LT_EQ, int(np.median(li[key])))
         cases.append((f"by_{key[2:]}_having_{kind}", [S[key][0]], narrow, having))
 for name, keys, aggs, having in cases:
     if only == "image_only" and name not in ("by_shipdate", "by_shipdate_count_only"):
