@@ -1131,7 +1131,40 @@ llkv_status llkv_hip_join_groupby_rows(llkv_hip_query *query, const uint32_t *pa
                                        const llkv_join_order_key *order, uint32_t n_order, uint64_t limit,
                                        llkv_hip_join_rows **out);
 uint64_t llkv_hip_join_rows_len(const llkv_hip_join_rows *rows);
-uint64_t llkv_hip_join_rows_total_groups(const llkv_hip_join_rows *rows); /* groups before LIMIT */
+uint64_t llkv_hip_join_rows_total_groups(const llkv_hip_join_rows *rows); /* groups before LIMIT (tail_rows: after HAVING, before OFFSET / LIMIT) */
+
+/* The result tail of a join → GROUP BY: HAVING, then ORDER BY, then OFFSET / LIMIT, applied BEFORE the groups leave the device, so
+ * that only the returned rows are copied out (a Q18-shaped `… GROUP BY o_orderkey HAVING sum(l_quantity) > 300 ORDER BY … LIMIT 100`).
+ * The output row is (key, payload…, aggregates…); the payload columns are GROUP BY columns of the SQL.
+ *   set_tail   records an owned copy of everything and takes effect from the next llkv_hip_query_launch (the sort-based GROUP BY
+ *              runs to completion inside launch, so the tail must be known before it).  n_payload = n_having = n_order = 0,
+ *              offset = 0 and limit = UINT64_MAX clear the tail.  payload_fields: ≤ 4 integer / Date32 columns of dim, as in _rows.
+ *              HAVING operands (the rules of llkv_hip_query_set_having_ex, unchanged): LLKV_HAVING_OPERAND_KEY index 0 is the group
+ *              key, typed by the dim key column's dtype; index 1 + c is payload column c, typed by its column's dtype as a key cell
+ *              is (a Date32 column is a Date32 value: every compare with it is FALSE); LLKV_HAVING_OPERAND_AGGREGATE indexes the
+ *              aggregate list of `prepare`.  LLKV_INVALID_ARGUMENT: not a join → GROUP BY query, executions in flight, a malformed
+ *              program (the message names the node), indices out of range.  LLKV_UNSUPPORTED, with set_having_ex's message: a
+ *              Decimal128 / Utf8 / Date32 leaf inside a value expression; more than 4 payload columns.
+ *   tail_rows  the rows of the latest finished execution, read with llkv_hip_join_rows_len / _total_groups / _get / _free;
+ *              total_groups = groups after HAVING, before OFFSET / LIMIT.  LLKV_INVALID_ARGUMENT when no tail is set or no
+ *              execution has finished with it.
+ * Order of operations (llkv-executor/src/lib.rs:5305-5355, :13762-13868, :10918-10955): every group's fallible aggregates are
+ * finalized — a failure carries the unfiltered query's status and message, even in a group the HAVING would drop; HAVING keeps a
+ * group iff the predicate is TRUE; ORDER BY, ties broken by the dimension row's position among the qualifying rows, as _rows
+ * breaks them; OFFSET and LIMIT.
+ * With a tail set llkv_hip_join_groupby_rows answers LLKV_INVALID_ARGUMENT (its groups may be filtered or cut) and so does
+ * llkv_hip_query_partial_groups; without one both behave as before.  Clearing a tail that an execution ran with drops that
+ * execution's result: launch again.
+ * Single-rank fact table: the dimension cells of the groups are made on the device (join_tail.hip), HAVING runs on the device for
+ * an Int64 key, Int64 payload columns, Int64 / Float64 aggregate cells and Int / Float / Boolean / NULL literals, the order on the
+ * device when offset + limit ≤ 1 024; otherwise, and for a sharded fact table (llkv_hip_query_finish_sharded / merge_groups, where
+ * the groups are merged on the host), the host filters and orders with the same rules and the same rows.
+ * llkv_hip_query_route_note names the paths taken: "; having: device | host (<reason>)", then "; order: device top-k | host (<reason>)". */
+llkv_status llkv_hip_join_groupby_set_tail(llkv_hip_query *query, const uint32_t *payload_fields, uint32_t n_payload,
+                                           const llkv_having_node *having, uint32_t n_having, const llkv_having_expr *exprs,
+                                           uint32_t n_exprs, const llkv_join_order_key *order, uint32_t n_order, uint64_t offset,
+                                           uint64_t limit /* UINT64_MAX: no limit */);
+llkv_status llkv_hip_join_groupby_tail_rows(llkv_hip_query *query, llkv_hip_join_rows **out);
 /* Row i: the group key, payload[n_payload] (+ payload_is_null), the dimension row's position among the qualifying rows, and a
  * pointer to its n_aggs finalized cells (owned by `rows`).  Any output pointer may be NULL.                                */
 llkv_status llkv_hip_join_rows_get(const llkv_hip_join_rows *rows, uint64_t i, int64_t *key, int64_t *payload,

@@ -345,6 +345,7 @@ int Query::launch(hipStream_t stream) {
     if (!rc && (local_order || local_having)) rc = apply_order(&done);
     else if (!rc) { row_mapped = false; row_map.clear(); order_note.clear(); total_groups = lazy.n; }
     if (rc) return rc;
+    if (join_state) join_tail_after_launch(this);
     n_launched++;
     return LLKV_OK;
   }
@@ -1027,6 +1028,14 @@ int Query::apply_order(const GroupOrderDone *done) {
   return LLKV_OK;
 }
 
+int Query::apply_merged_order() {
+  if (join_state)
+    if (int rc = join_tail_extend_merged(this)) return rc;
+  GroupOrderDone d;
+  d.why_host = d.having_why_host = "merged groups";
+  return apply_order(&d);
+}
+
 // The dtype of key column `key` (what types a key cell under HAVING: cell_key hands Date32 / Boolean cells over as LLKV_DT_INT64).
 int32_t Query::key_dtype_of(uint32_t key) const {
   if (lazy.active) return key < lazy.key_cols.size() ? lazy.key_cols[key]->dtype : (int32_t)LLKV_DT_INT64;
@@ -1335,8 +1344,8 @@ llkv_status llkv_hip_query_set_group_order(llkv_hip_query *query, const llkv_gro
 // A leaf inside a HAVING expression that is statically not Integer / Float / Boolean / Null: the reference raises "Non-numeric
 // value …" or switches to exact decimal arithmetic there (llkv-executor/src/lib.rs:7229-7357); the binding's CPU route produces that.
 // Only the entries an operand of a node names are looked at (having_validate has checked exactly those).
-static int having_expr_leaves_numeric(const Query *q, const llkv_having_node *nodes, uint32_t n_nodes, const llkv_having_expr *exprs, uint32_t n_exprs, std::string *err) {
-  const LoweredPlan &plan = q->sorted ? *sorted_groupby_plan(q->sorted) : q->plan;
+extern "C++" int llkv::having_expr_leaves_numeric(const llkv_having_node *nodes, uint32_t n_nodes, const llkv_having_expr *exprs, uint32_t n_exprs, uint32_t n_keys,
+                                     const std::function<int32_t(uint32_t)> &key_dtype, const LoweredPlan &plan, uint32_t n_aggs, std::string *err) {
   std::vector<uint8_t> named(n_exprs, 0);
   auto name = [&](const llkv_having_operand &o) { if (o.kind == LLKV_HAVING_OPERAND_EXPR && o.index < n_exprs) named[o.index] = 1; };
   for (uint32_t i = 0; i < n_nodes; ++i) {
@@ -1352,10 +1361,10 @@ static int having_expr_leaves_numeric(const Query *q, const llkv_having_node *no
       if (tk.op != LLKV_HAVING_TOKEN_PUSH) continue;
       const llkv_having_operand &o = tk.leaf;
       std::string what;
-      if (o.kind == LLKV_HAVING_OPERAND_KEY && o.index < q->n_user_keys) {
-        const int32_t dt = q->key_dtype_of(o.index);
+      if (o.kind == LLKV_HAVING_OPERAND_KEY && o.index < n_keys) {
+        const int32_t dt = key_dtype(o.index);
         if (dt == LLKV_DT_DECIMAL128 || dt == LLKV_DT_UTF8 || dt == LLKV_DT_DATE32) what = "key " + std::to_string(o.index) + " is a " + dtype_name(dt) + " column";
-      } else if (o.kind == LLKV_HAVING_OPERAND_AGGREGATE && o.index < q->n_user_aggs && o.index < plan.aggs.size()) {
+      } else if (o.kind == LLKV_HAVING_OPERAND_AGGREGATE && o.index < n_aggs && o.index < plan.aggs.size()) {
         const AggOut &a = plan.aggs[o.index];
         if (a.digits_lane >= 0) what = "aggregate " + std::to_string(o.index) + " has a computed DECIMAL argument";
         else if (a.fin == AggFinal::SumDec || a.fin == AggFinal::TotalDec || a.fin == AggFinal::AvgDec || a.fin == AggFinal::MinDec || a.fin == AggFinal::MaxDec)
@@ -1383,7 +1392,9 @@ llkv_status llkv_hip_query_set_having_ex(llkv_hip_query *query, const llkv_havin
   if (n_nodes) {
     std::string err;
     if (int rc = having_validate(nodes, n_nodes, exprs, n_exprs, q->n_user_keys, q->n_user_aggs, &err)) return (llkv_status)set_error(rc, err);
-    if (int rc = having_expr_leaves_numeric(q, nodes, n_nodes, exprs, n_exprs, &err)) return (llkv_status)set_error(rc, err);
+    if (int rc = having_expr_leaves_numeric(nodes, n_nodes, exprs, n_exprs, q->n_user_keys, [q](uint32_t k) { return q->key_dtype_of(k); },
+                                            q->sorted ? *sorted_groupby_plan(q->sorted) : q->plan, q->n_user_aggs, &err))
+      return (llkv_status)set_error(rc, err);
   }
   q->having.assign(nodes, n_nodes, exprs, n_exprs);
   return LLKV_OK;

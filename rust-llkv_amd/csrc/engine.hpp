@@ -497,7 +497,23 @@ struct SortedGroupBy;
 bool sorted_groupby_partitioned(const SortedGroupBy *s);
 const std::vector<uint32_t> &sorted_groupby_key_fields(const SortedGroupBy *s);
 const LoweredPlan *sorted_groupby_plan(const SortedGroupBy *s); // the plan whose aggs finalize the groups' lanes
+// More key cells per group, made on the device from the groups' own key cells before HAVING and ORDER BY look at them (join → GROUP BY:
+// the dimension row's payload cells and position, join_group.cpp).  Called by the sort-based run, when a HAVING or an order is applied
+// locally, with the [n_keys][n] cells of the `n` groups in HBM: it allocates x_kv / x_kvalid as [n_keys'][n], fills them (the launches
+// go on `s`) and sets out->n_keys / key_cols to the extended shape.  HAVING, the top-k and the copy-out then carry every column.
+using GroupKeyExtender = std::function<int(LazyGroups *out, const int64_t *d_kv, const uint8_t *d_kvalid, uint64_t n, hipStream_t s, Scratch *x_kv, Scratch *x_kvalid)>;
+void sorted_groupby_set_key_extender(SortedGroupBy *s, GroupKeyExtender extend); // an empty function clears it
 void join_group_state_free(struct JoinGroupState *s); // join_group.cpp
+struct Query;
+// The result tail of a join → GROUP BY (llkv_hip_join_groupby_set_tail, join_group.cpp).  After a launch: whether the execution ran
+// with the tail.  After the merge of a sharded table's groups: the dimension cells of the merged groups, looked up on the device
+// and kept on the host, so that Query::apply_order filters and orders them (a no-op without a tail).
+void join_tail_after_launch(Query *q);
+int join_tail_extend_merged(Query *q);
+// A leaf of a HAVING value expression that is statically not Integer / Float / Boolean / Null (LLKV_UNSUPPORTED, *err names it):
+// `key_dtype(i)` = the dtype of key column i of `n_keys`, `plan` finalizes the `n_aggs` aggregates.
+int having_expr_leaves_numeric(const llkv_having_node *nodes, uint32_t n_nodes, const llkv_having_expr *exprs, uint32_t n_exprs, uint32_t n_keys,
+                               const std::function<int32_t(uint32_t)> &key_dtype, const LoweredPlan &plan, uint32_t n_aggs, std::string *err);
 struct KeySetView;
 // `key_set` / `key_set_field`: one more conjunct of the selection — the integer column must be in the key set (join → GROUP BY,
 // join_group.cpp: the keys of the qualifying dimension rows; the bitmap belongs to the caller and outlives the object)
@@ -577,7 +593,7 @@ struct Query {
   uint64_t result_rows() const { return lazy.active ? lazy.n : groups.size(); } // before the order
   int apply_order(const GroupOrderDone *done);
   int32_t key_dtype_of(uint32_t key) const;
-  int apply_merged_order() { GroupOrderDone d; d.why_host = d.having_why_host = "merged groups"; return apply_order(&d); } // a sharded table's groups after the merge
+  int apply_merged_order(); // a sharded table's groups after the merge
   bool plan_grouped() const { return sorted != nullptr || plan.grouped; }
   int cell_key(uint64_t group, uint32_t key, llkv_value *out) const;     // the result before the order
   int cell_value(uint64_t group, uint32_t agg, llkv_value *out) const;

@@ -39,6 +39,7 @@ struct SortedGroupBy {
   // key set of the dimension rows that qualify (a bitmap the caller owns, alive as long as this object)
   bool has_key_set = false;
   KeySetView key_set{nullptr, 0, 0};
+  GroupKeyExtender extend_keys; // … and its result tail: more key cells per group, made on the device before HAVING / ORDER BY
   int run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOrderDone *done, const HavingProgram *having);
   ~SortedGroupBy() { if (part) part_groupby_free(part); }
 };
@@ -46,6 +47,7 @@ struct SortedGroupBy {
 void sorted_groupby_free(SortedGroupBy *s) { delete s; }
 bool sorted_groupby_partitioned(const SortedGroupBy *s) { return s && s->part; }
 const std::vector<uint32_t> &sorted_groupby_key_fields(const SortedGroupBy *s) { return s->key_fields; }
+void sorted_groupby_set_key_extender(SortedGroupBy *s, GroupKeyExtender extend) { s->extend_keys = std::move(extend); }
 const LoweredPlan *sorted_groupby_plan(const SortedGroupBy *s) { return s->part ? part_groupby_plan(s->part) : &s->red_plan; }
 
 // ---- what the sort-based and the partitioned run (group_part.cpp) share ----------------------------------------------------
@@ -258,7 +260,7 @@ int sorted_groupby_prepare(const Table *table, const llkv_filter *filters, uint3
     if (n_ops) return set_error(LLKV_UNSUPPORTED, "a key-set conjunct beside a predicate program");
     s->has_key_set = true;
     s->key_set = *key_set;
-    if ((rc = lower_selection_in_set(resolve, filters, n_filters, key_set_field, &s->sel_plan, &err))) return set_error(rc, err);
+    if ((rc = lower_selection_in_set(resolve, filters, n_filters, key_set_field, &s->sel_plan, &err, /*null_key_matches_nothing=*/true))) return set_error(rc, err);
   } else if ((rc = lower_selection(resolve, filters, n_filters, ops, n_ops, nullptr, 0, &s->sel_plan, &err))) return set_error(rc, err);
   if ((rc = lower_reduce(resolve, aggs, n_aggs, &s->red_plan, &err))) return set_error(rc, err);
   if (s->red_plan.has_distinct() && table->world != 1)
@@ -480,6 +482,15 @@ int SortedGroupBy::run(LazyGroups *out, const GroupOrderSpec *out_order, GroupOr
   if ((rc = jit_launch_raw(narrow ? red_kernel.fn2 : red_kernel.fn, (uint32_t)((n_groups + groups_per_block - 1) / groups_per_block), &p, sizeof p, s))) return rc;
   HIP_TRY(hj_launch_group_keys(ks, sel.d_dev, perm, seg.as<uint64_t>(), order, n_groups, kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), s));
   trace.mark("group reduce");
+  Scratch x_kv, x_kvalid; // the key cells with those of the extender behind them
+  if (extend_keys && (out_order || having)) {
+    if ((rc = extend_keys(out, kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), n_groups, s, &x_kv, &x_kvalid))) return rc;
+    std::swap(kv_d.p, x_kv.p);
+    std::swap(kv_d.cap, x_kv.cap);
+    std::swap(kvalid_d.p, x_kvalid.p);
+    std::swap(kvalid_d.cap, x_kvalid.cap);
+    trace.mark("extended keys");
+  }
   // (the reduce's error word is still unread: it travels with the copy-out, or is read before the top-k)
   return deliver_groups(lanes_d.as<uint64_t>(), kv_d.as<int64_t>(), kvalid_d.as<uint8_t>(), n_groups, out_order, done, err_d.as<uint32_t>(), s, &h, &trace, out, having);
 }

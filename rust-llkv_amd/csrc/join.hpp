@@ -365,6 +365,11 @@ struct JoinPayloadCols {
 };
 hipError_t hj_launch_lookup_payload(const uint64_t *sorted_keys, const uint64_t *sorted_rows, const uint32_t *sorted_pos, uint64_t n_dim, const int64_t *probe_keys,
                                     long long base, uint64_t m, const JoinPayloadCols &cols, int64_t *out_payload, uint8_t *out_valid, uint32_t *out_pos, hipStream_t s);
+// … for n group keys in HBM in ASCENDING order (join_tail.hip): a workgroup bounds its stretch of groups in the sorted dimension
+// keys and resolves them inside that slice (in LDS when it fits).  out_kv / out_kvalid: [cols.n + 1][n] key cells — the payload
+// columns, then the position (0xFFFFFFFF when the key is not there; its validity is always 1).
+hipError_t hj_launch_join_dim_cells(const int64_t *group_keys, uint64_t n, const uint64_t *sorted_keys, const uint64_t *sorted_rows, const uint32_t *sorted_pos,
+                                    uint64_t n_dim, long long base, const JoinPayloadCols &cols, int64_t *out_kv, uint8_t *out_kvalid, hipStream_t s);
 
 // ---- ordered scans (stream.cpp) -----------------------------------------------------------------------------
 hipError_t hj_launch_gather_u64(const uint64_t *in, const uint32_t *perm, uint64_t n, uint64_t *out, hipStream_t s);

@@ -14,6 +14,9 @@
 //      handling and the sharded merge of partial groups are its own; a fact table clustered by the key needs no sort
 //   3. per result group: bisection of its key in the qualifying dimension rows sorted by key → payload cells and the row's
 //      position (the last tie-break of the order), ORDER BY / LIMIT on the host over the finalized cells.
+//      With a result tail (llkv_hip_join_groupby_set_tail: HAVING, ORDER BY, OFFSET / LIMIT) step 3 runs on the device before anything is
+//      copied out: join_tail.hip merges the groups (ascending keys) with the sorted dimension rows into payload and position cells, and
+//      the GROUP BY's own device HAVING and top-k take them as key cells — the end of this file.
 // No joined row ever exists: the fact columns are read once (predicate columns, then the arguments of the rows that join).
 #include "engine.hpp"
 #include "join.hpp"
@@ -77,6 +80,27 @@ struct JoinGroupState {
   uint64_t n_dim = 0;
   long long key_base = 0;
   uint32_t dim_key_field = 0;
+  // the result tail (llkv_hip_join_groupby_set_tail): its HAVING and its order live in Query::having / Query::order, over the key
+  // cells (key, payload …, position); here what turns a group into those cells
+  bool tail_set = false;
+  std::vector<uint32_t> tail_payload;
+  ColumnInfo pos_info;       // the position column of the extended key cells: an Int64 that is never NULL
+  bool tail_applied = false; // the latest execution ran with the tail: Query::lazy holds extended key cells
+  std::vector<int64_t> m_kv; // extended key cells of a sharded table's merged groups
+  std::vector<uint8_t> m_kvalid;
+  // the payload columns as the lookup kernels read them and, for LazyGroups::key_cols, the columns that type the extended cells
+  int tail_columns(JoinPayloadCols *pc, std::vector<const ColumnInfo *> *cols) const {
+    std::memset(pc, 0, sizeof *pc);
+    pc->n = (uint32_t)tail_payload.size();
+    cols->assign(1, &td->cols.at(dim_key_field).info);
+    for (uint32_t c = 0; c < pc->n; ++c) {
+      const ColumnInfo *ci = nullptr;
+      if (int rc = key_col_of(td, tail_payload[c], &pc->col[c], &ci, true)) return rc;
+      cols->push_back(ci);
+    }
+    cols->push_back(&pos_info);
+    return LLKV_OK;
+  }
 };
 void join_group_state_free(JoinGroupState *s) { delete s; }
 
@@ -157,7 +181,7 @@ static int join_groupby_prepare(const llkv_join_side *fact, const llkv_join_side
 
   // ---- 2. GROUP BY the fact key over   filters ∧ InKeySet<fact key>   ---------------------------------------------------------
   JoinKeyColumn kf;
-  if ((rc = key_col_of(tf, fact->key_field, &kf, nullptr, false))) return rc;
+  if ((rc = key_col_of(tf, fact->key_field, &kf, nullptr, true))) return rc; // (a NULL fact key joins no dimension row: the selection drops it)
   std::unique_ptr<Query> q(new Query());
   q->table = tf;
   q->epochs.add(tf, "fact ");
@@ -208,6 +232,8 @@ static int join_groupby_rows(Query *q, const uint32_t *payload_fields, uint32_t 
   int rc = ensure_device();
   if (rc) return rc;
   if (!q || !q->join_state || !q->sorted || !out) return set_error(LLKV_INVALID_ARGUMENT, "not a join → GROUP BY query");
+  if (q->join_state->tail_set)
+    return set_error(LLKV_INVALID_ARGUMENT, "the query has a result tail set (its groups may be filtered or cut): read llkv_hip_join_groupby_tail_rows, or clear the tail");
   if (!q->lazy.active) return set_error(LLKV_INVALID_ARGUMENT, "the query has not finished an execution yet");
   if ((rc = q->epochs.check())) return rc; // (the payload gather reads the dimension's columns through the rows kept at prepare)
   if (n_payload > 4) return set_error(LLKV_UNSUPPORTED, "more than 4 payload columns");
@@ -308,6 +334,172 @@ static int join_groupby_rows(Query *q, const uint32_t *payload_fields, uint32_t 
   return LLKV_OK;
 }
 
+// ---- the result tail: HAVING, ORDER BY / OFFSET / LIMIT before the groups leave the device --------------------------------------
+// The groups of the sort-based run stay in HBM in ascending key order; join_dim_cells (join_tail.hip) merges them with the sorted
+// dimension rows into key cells 1 … n_payload (payload) and n_payload + 1 (position), and the tail of every GROUP BY —
+// having_device, group_order_device, or the copy-out and Query::apply_order on the host — runs over the extended cells: a payload
+// column is a key column, the position the last ascending order term.
+static int join_tail_extend_device(const JoinGroupState *st, LazyGroups *out, const int64_t *d_kv, const uint8_t *d_kvalid, uint64_t n, hipStream_t s, Scratch *x_kv,
+                                   Scratch *x_kvalid) {
+  JoinPayloadCols pc;
+  std::vector<const ColumnInfo *> cols;
+  int rc = st->tail_columns(&pc, &cols);
+  if (rc) return rc;
+  const size_t nk = cols.size(); // key, payload …, position
+  if ((rc = x_kv->alloc(n * nk * 8)) || (rc = x_kvalid->alloc(n * nk))) return rc;
+  HIP_TRY(hipMemcpyAsync(x_kv->p, d_kv, n * 8, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(x_kvalid->p, d_kvalid, n, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hj_launch_join_dim_cells(d_kv, n, st->keys.as<uint64_t>(), st->rows.as<uint64_t>(), st->pos.as<uint32_t>(), st->n_dim, st->key_base, pc,
+                                   x_kv->as<int64_t>() + n, x_kvalid->as<uint8_t>() + n, s));
+  out->n_keys = (uint32_t)nk;
+  out->key_cols = cols;
+  return LLKV_OK;
+}
+
+void join_tail_after_launch(Query *q) {
+  JoinGroupState &st = *q->join_state;
+  st.tail_applied = st.tail_set && q->table->world == 1;
+}
+
+int join_tail_extend_merged(Query *q) {
+  JoinGroupState &st = *q->join_state;
+  if (!st.tail_set) return LLKV_OK;
+  int rc = ensure_device();
+  if (rc || (rc = q->epochs.check())) return rc;
+  LazyGroups &lz = q->lazy;
+  JoinPayloadCols pc;
+  std::vector<const ColumnInfo *> cols;
+  if ((rc = st.tail_columns(&pc, &cols))) return rc;
+  const uint64_t n = lz.n;
+  const size_t nk = cols.size(), P = pc.n;
+  st.m_kv.assign(n * nk, 0);
+  st.m_kvalid.assign(n * nk, 1);
+  if (n) {
+    hipStream_t s = g_ctx.stream;
+    std::vector<uint32_t> h_pos(n);
+    Scratch d_keys, d_payload, d_valid, d_pos;
+    if ((rc = d_keys.alloc(n * 8)) || (rc = d_payload.alloc((P ? P : 1) * n * 8)) || (rc = d_valid.alloc((P ? P : 1) * n)) || (rc = d_pos.alloc(n * 4))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_keys.p, lz.key_vals, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hj_launch_lookup_payload(st.keys.as<uint64_t>(), st.rows.as<uint64_t>(), st.pos.as<uint32_t>(), st.n_dim, d_keys.as<int64_t>(), st.key_base, n, pc,
+                                     d_payload.as<int64_t>(), d_valid.as<uint8_t>(), d_pos.as<uint32_t>(), s));
+    if (P) {
+      HIP_TRY(hipMemcpyAsync(st.m_kv.data() + n, d_payload.p, P * n * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(st.m_kvalid.data() + n, d_valid.p, P * n, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipMemcpyAsync(h_pos.data(), d_pos.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::memcpy(st.m_kv.data(), lz.key_vals, n * 8);
+    std::memcpy(st.m_kvalid.data(), lz.key_valid, n);
+    for (uint64_t g = 0; g < n; ++g) st.m_kv[(P + 1) * n + g] = (int64_t)h_pos[g];
+  }
+  lz.key_vals = st.m_kv.data();
+  lz.key_valid = st.m_kvalid.data();
+  lz.n_keys = (uint32_t)nk;
+  lz.key_cols = cols;
+  st.tail_applied = true;
+  return LLKV_OK;
+}
+
+static int join_groupby_set_tail(Query *q, const uint32_t *payload_fields, uint32_t n_payload, const llkv_having_node *having, uint32_t n_having,
+                                 const llkv_having_expr *exprs, uint32_t n_exprs, const llkv_join_order_key *order, uint32_t n_order, uint64_t offset, uint64_t limit) {
+  if (!q || !q->join_state || !q->sorted) return set_error(LLKV_INVALID_ARGUMENT, "not a join → GROUP BY query");
+  if (q->n_launched != q->n_collected) return set_error(LLKV_INVALID_ARGUMENT, "executions in flight");
+  JoinGroupState &st = *q->join_state;
+  if (!n_payload && !n_having && !n_order && offset == 0 && limit == UINT64_MAX) { // clear: the next launch leaves plain groups again
+    if (st.tail_applied) { q->lazy.active = false; q->row_mapped = false; q->row_map.clear(); q->order_note.clear(); } // (its groups were filtered or cut)
+    st.tail_set = st.tail_applied = false;
+    st.tail_payload.clear();
+    q->order = GroupOrderSpec();
+    q->having.assign(nullptr, 0);
+    sorted_groupby_set_key_extender(q->sorted, GroupKeyExtender());
+    return LLKV_OK;
+  }
+  if (n_payload > 4) return set_error(LLKV_UNSUPPORTED, "more than 4 payload columns");
+  const uint32_t n_aggs = q->n_user_aggs;
+  std::vector<int32_t> key_dtypes(1, st.td->cols.at(st.dim_key_field).info.dtype);
+  for (uint32_t c = 0; c < n_payload; ++c) {
+    JoinKeyColumn view;
+    const ColumnInfo *ci = nullptr;
+    if (int rc = key_col_of(st.td, payload_fields[c], &view, &ci, true)) return rc;
+    key_dtypes.push_back(ci->dtype);
+  }
+  GroupOrderSpec spec;
+  for (uint32_t o = 0; o < n_order; ++o) {
+    const llkv_join_order_key &k = order[o];
+    if ((k.kind == LLKV_JOIN_ORDER_AGGREGATE && k.index >= n_aggs) || (k.kind == LLKV_JOIN_ORDER_PAYLOAD && k.index >= n_payload) ||
+        (k.kind != LLKV_JOIN_ORDER_AGGREGATE && k.kind != LLKV_JOIN_ORDER_PAYLOAD && k.kind != LLKV_JOIN_ORDER_KEY))
+      return set_error(LLKV_INVALID_ARGUMENT, "ORDER BY key out of range");
+    llkv_group_order_key t;
+    t.kind = k.kind == LLKV_JOIN_ORDER_AGGREGATE ? LLKV_GROUP_ORDER_AGGREGATE : LLKV_GROUP_ORDER_KEY;
+    t.index = k.kind == LLKV_JOIN_ORDER_AGGREGATE ? k.index : k.kind == LLKV_JOIN_ORDER_PAYLOAD ? 1 + k.index : 0;
+    t.descending = k.descending;
+    t.nulls_first = k.nulls_first;
+    spec.terms.push_back(t);
+  }
+  spec.terms.push_back(llkv_group_order_key{LLKV_GROUP_ORDER_KEY, 1 + n_payload, 0, 0}); // ties: the dimension row's position
+  spec.offset = offset;
+  spec.limit = limit;
+  if (n_having) {
+    std::string err;
+    if (int rc = having_validate(having, n_having, exprs, n_exprs, 1 + n_payload, n_aggs, &err)) return set_error(rc, err);
+    if (int rc = having_expr_leaves_numeric(having, n_having, exprs, n_exprs, 1 + n_payload, [&](uint32_t k) { return key_dtypes[k]; }, *sorted_groupby_plan(q->sorted), n_aggs, &err))
+      return set_error(rc, err);
+  }
+  if (st.tail_applied) { q->lazy.active = false; q->row_mapped = false; q->row_map.clear(); q->order_note.clear(); } // (rows of another tail)
+  st.tail_applied = false;
+  st.tail_set = true;
+  st.tail_payload.assign(payload_fields, payload_fields + n_payload);
+  st.pos_info = ColumnInfo();
+  st.pos_info.dtype = LLKV_DT_INT64;
+  q->order = spec;
+  q->having.assign(having, n_having, exprs, n_exprs);
+  const JoinGroupState *stp = &st;
+  sorted_groupby_set_key_extender(q->sorted, [stp](LazyGroups *out, const int64_t *d_kv, const uint8_t *d_kvalid, uint64_t n, hipStream_t s, Scratch *x_kv, Scratch *x_kvalid) {
+    return join_tail_extend_device(stp, out, d_kv, d_kvalid, n, s, x_kv, x_kvalid);
+  });
+  return LLKV_OK;
+}
+
+// The rows the tail left, in order: through Query::row_map when the host filtered or ordered, else the result's own rows.
+static int join_groupby_tail_rows(Query *q, JoinRows **out) {
+  if (!q || !q->join_state || !q->sorted || !out) return set_error(LLKV_INVALID_ARGUMENT, "not a join → GROUP BY query");
+  const JoinGroupState &st = *q->join_state;
+  if (!st.tail_set) return set_error(LLKV_INVALID_ARGUMENT, "no result tail is set (llkv_hip_join_groupby_set_tail)");
+  if (!q->lazy.active || !st.tail_applied || q->n_launched != q->n_collected)
+    return set_error(LLKV_INVALID_ARGUMENT, "the query has not finished an execution with this tail yet");
+  const LazyGroups &lz = q->lazy;
+  const uint32_t n_aggs = q->n_user_aggs, n_payload = (uint32_t)st.tail_payload.size();
+  std::unique_ptr<JoinRows> res(new JoinRows());
+  res->n_aggs = n_aggs;
+  res->n_payload = n_payload;
+  res->total_groups = q->total_groups;
+  const uint64_t n = lz.n, take = q->row_mapped ? q->row_map.size() : n;
+  if (take && lz.n_keys != n_payload + 2) return set_error(LLKV_INTERNAL, "join → GROUP BY: the groups carry no dimension cells");
+  res->keys.resize(take);
+  res->group_index.resize(take);
+  res->payload.resize((size_t)take * n_payload);
+  res->payload_null.resize((size_t)take * n_payload);
+  res->values.resize((size_t)take * n_aggs);
+  std::string err;
+  for (uint64_t r = 0; r < take; ++r) {
+    const uint64_t g = q->row_mapped ? q->row_map[r] : r;
+    if (g >= n) return set_error(LLKV_INTERNAL, "join → GROUP BY: a row of the tail is out of range");
+    const int64_t pos = lz.key_vals[(size_t)(n_payload + 1) * n + g];
+    if (pos == 0xFFFFFFFFll) return set_error(LLKV_INTERNAL, "join → GROUP BY: a result group's key is not among the qualifying dimension rows");
+    res->keys[r] = lz.key_vals[g];
+    res->group_index[r] = (uint64_t)pos;
+    for (uint32_t c = 0; c < n_payload; ++c) {
+      const bool valid = lz.key_valid[(size_t)(1 + c) * n + g] != 0;
+      res->payload[(size_t)r * n_payload + c] = valid ? lz.key_vals[(size_t)(1 + c) * n + g] : 0;
+      res->payload_null[(size_t)r * n_payload + c] = valid ? 0 : 1;
+    }
+    for (uint32_t a = 0; a < n_aggs; ++a)
+      if (int rc = finalize_value(lz.plan->aggs[a], lz.lanes + (size_t)g * lz.k, 2, &res->values[(size_t)r * n_aggs + a], &err, false)) return set_error(rc, err);
+  }
+  *out = res.release();
+  return LLKV_OK;
+}
+
 } // namespace llkv
 
 using namespace llkv;
@@ -329,6 +521,23 @@ llkv_status llkv_hip_join_groupby_rows(llkv_hip_query *query, const uint32_t *pa
   if (n_order && !order) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "NULL ORDER BY list");
   JoinRows *r = nullptr;
   const int rc = join_groupby_rows(reinterpret_cast<Query *>(query), payload_fields, n_payload, order, n_order, limit, &r);
+  if (rc) return (llkv_status)rc;
+  *out = reinterpret_cast<llkv_hip_join_rows *>(r);
+  return LLKV_OK;
+}
+
+llkv_status llkv_hip_join_groupby_set_tail(llkv_hip_query *query, const uint32_t *payload_fields, uint32_t n_payload, const llkv_having_node *having, uint32_t n_having,
+                                           const llkv_having_expr *exprs, uint32_t n_exprs, const llkv_join_order_key *order, uint32_t n_order, uint64_t offset,
+                                           uint64_t limit) {
+  if (n_payload && !payload_fields) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "NULL payload field list");
+  if (n_having && !having) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "NULL HAVING program");
+  if (n_order && !order) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "NULL ORDER BY list");
+  return (llkv_status)join_groupby_set_tail(reinterpret_cast<Query *>(query), payload_fields, n_payload, having, n_having, exprs, n_exprs, order, n_order, offset, limit);
+}
+
+llkv_status llkv_hip_join_groupby_tail_rows(llkv_hip_query *query, llkv_hip_join_rows **out) {
+  JoinRows *r = nullptr;
+  const int rc = join_groupby_tail_rows(reinterpret_cast<Query *>(query), &r);
   if (rc) return (llkv_status)rc;
   *out = reinterpret_cast<llkv_hip_join_rows *>(r);
   return LLKV_OK;

@@ -515,11 +515,13 @@ struct Lowering {
     return LLKV_OK;
   }
   // "the key of this field is in the key set the launch binds" (InKeySet, fused_scan.hip.h)
-  int in_key_set(uint32_t field, std::string *node) {
+  // `present`: a key column with NULL cells is taken, and *present is its validity node ("" without NULL cells)
+  int in_key_set(uint32_t field, std::string *node, std::string *present = nullptr) {
     const ColumnInfo *ci;
     int slot, rc;
     std::string key;
-    if ((rc = key_column(field, &ci, &slot)) || (rc = key_node(*ci, slot, &key))) return rc;
+    if ((rc = present ? slot_of(field, &ci, &slot) : key_column(field, &ci, &slot)) || (rc = key_node(*ci, slot, &key))) return rc;
+    if (present && (rc = valid_of_field(field, present))) return rc;
     *node = "InKeySet<" + key + ">";
     return LLKV_OK;
   }
@@ -2211,14 +2213,15 @@ int lower_selection(const ColumnResolver &resolve, const llkv_filter *filters, u
 }
 
 int lower_selection_in_set(const ColumnResolver &resolve, const llkv_filter *filters, uint32_t n_filters, uint32_t key_field,
-                           LoweredPlan *out, std::string *err) {
+                           LoweredPlan *out, std::string *err, bool null_key_matches_nothing) {
   *out = LoweredPlan{};
   Lowering L{resolve, *out, err, false};
-  std::string pred, in_set;
+  std::string pred, in_set, present;
   int rc = L.predicate(filters, n_filters, nullptr, 0, &pred);
   if (rc) return rc;
-  if ((rc = L.in_key_set(key_field, &in_set))) return rc;
+  if ((rc = L.in_key_set(key_field, &in_set, null_key_matches_nothing ? &present : nullptr))) return rc;
   out->always_false = pred == "False";
+  if (!out->always_false && !present.empty()) pred = pred == "True" ? present : "And<" + pred + "," + present + ">";
   if (!out->always_false) pred = pred == "True" ? in_set : "AndThen<" + pred + "," + in_set + ">";
   out->type_string = "SelPlan<" + cols_string(*out, &out->bytes_per_row) + "," + pred + ">";
   return LLKV_OK;

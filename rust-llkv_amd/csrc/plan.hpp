@@ -179,10 +179,12 @@ int lower_plan(const ColumnResolver &resolve, const llkv_filter *filters, uint32
 int lower_selection(const ColumnResolver &resolve, const llkv_filter *filters, uint32_t n_filters,
                     const llkv_eval_op *ops, uint32_t n_ops, const uint32_t *drop_null_fields, uint32_t n_drop_null_fields,
                     LoweredPlan *out, std::string *err);
-// The same with one more conjunct: the integer column `key_field` (no NULL cells) must be in the key set the launch
-// binds (InKeySet, fused_scan.hip.h) → "SelPlan<Cols<…>,AndThen<pred,InKeySet<key>>>".
+// The same with one more conjunct: the integer column `key_field` must be in the key set the launch
+// binds (InKeySet, fused_scan.hip.h) → "SelPlan<Cols<…>,AndThen<pred,InKeySet<key>>>".  A key column with NULL cells is refused,
+// unless `null_key_matches_nothing` (the probe side of an inner join: a NULL key joins no row): its validity is then one more
+// conjunct of `pred`, so the set is asked only about present keys.
 int lower_selection_in_set(const ColumnResolver &resolve, const llkv_filter *filters, uint32_t n_filters, uint32_t key_field,
-                           LoweredPlan *out, std::string *err);
+                           LoweredPlan *out, std::string *err, bool null_key_matches_nothing = false);
 // Scan projections (ScanProjection::{Column,Computed}, llkv-scan/src/lib.rs:59-65) →
 // "ProjPlan<Cols<…>,Outs<…>>" (window gather + computed expressions).
 // `pad_rows`: a row index of ~0 yields a NULL in every output (the build side of a LEFT join)

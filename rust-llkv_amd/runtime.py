@@ -1094,6 +1094,31 @@ class JoinGroupBy(PreparedQuery):
         h = C.c_void_p()
         check(L.llkv_hip_join_groupby_rows(self._h, pay, C.c_uint32(len(payload_fields)), ok, C.c_uint32(len(order)),
                                            C.c_uint64(2**64 - 1 if limit is None else limit), C.byref(h)))
+        return self._read_rows(h, len(payload_fields))
+
+    def set_tail(self, payload_fields: Sequence[int] = (), having=None, order=(), offset: int = 0, limit: Optional[int] = None, exprs=None):
+        """HAVING, ORDER BY, OFFSET / LIMIT applied before the groups leave the device (llkv_hip_join_groupby_set_tail), from the
+        next launch on; read the rows with ``tail_rows``.  ``having``: an ``abi.Having`` tree as PreparedQuery.set_having takes it —
+        key 0 is the group key, key 1 + c payload column c.  ``order`` as in ``result``.  All defaults clear the tail."""
+        keep: list = []
+        nodes, n, ex, n_ex = abi.having_program(having, keep, exprs)
+        pay = (C.c_uint32 * max(1, len(payload_fields)))(*payload_fields)
+        ok = (abi.CJoinOrderKey * max(1, len(order)))()
+        for i, o in enumerate(order):
+            ok[i].kind, ok[i].index, ok[i].descending, ok[i].nulls_first = o[0], o[1], int(o[2]) if len(o) > 2 else 0, int(o[3]) if len(o) > 3 else 0
+        check(lib().llkv_hip_join_groupby_set_tail(self._h, pay, C.c_uint32(len(payload_fields)), nodes, C.c_uint32(n), ex, C.c_uint32(n_ex), ok,
+                                                   C.c_uint32(len(order)), C.c_uint64(int(offset)), C.c_uint64(2**64 - 1 if limit is None else int(limit))))
+        self._tail_payload = len(payload_fields)
+
+    def tail_rows(self):
+        """The rows the tail of ``set_tail`` left of the latest finished execution: (rows, total_groups) — the JoinRows of ``result``;
+        total_groups counts the groups after HAVING, before OFFSET / LIMIT."""
+        h = C.c_void_p()
+        check(lib().llkv_hip_join_groupby_tail_rows(self._h, C.byref(h)))
+        return self._read_rows(h, getattr(self, "_tail_payload", 0))
+
+    def _read_rows(self, h, n_payload: int):
+        L = lib()
         try:
             L.llkv_hip_join_rows_len.restype = C.c_uint64
             L.llkv_hip_join_rows_total_groups.restype = C.c_uint64
@@ -1106,7 +1131,7 @@ class JoinGroupBy(PreparedQuery):
             vals = C.POINTER(abi.CValue)()
             for i in range(n):
                 check(L.llkv_hip_join_rows_get(h, C.c_uint64(i), C.byref(key), pv, pn, C.byref(gi), C.byref(vals)))
-                rows.append(JoinRow(key.value, [None if pn[c] else pv[c] for c in range(len(payload_fields))],
+                rows.append(JoinRow(key.value, [None if pn[c] else pv[c] for c in range(n_payload)],
                                     [Value.from_c(vals[a]) for a in range(self.n_aggs)], gi.value))
             return rows, total
         finally:

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """TPC-H Q3 shape at SF10 on one GPU (BASELINE.json configs[4], single-GPU form): time of
 llkv_hip_join_groupby_topk with all inputs resident in HBM; algorithmic bytes per SURVEY.md §8(d).
-Options: --general (the general join → GROUP BY route over the same star), --decimal (the money columns as DECIMAL(15,2):
+Options: --general (the general join → GROUP BY route over the same star), --tail (that route with its result tail — HAVING /
+ORDER BY / LIMIT on the device, llkv_hip_join_groupby_set_tail: Q3's own order and LIMIT 10, and a Q18-shaped query), --decimal (the money columns as DECIMAL(15,2):
 llkv_hip_join_groupby_topk_exact and the general route over them), --sharded (configs[4] emulated on one device)."""
-import importlib, json, os, sys, time
+import ctypes as C, importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
@@ -13,7 +14,7 @@ sf = sys.argv[1] if len(sys.argv) > 1 else "sf10"
 rt.init(0)
 rows, scale = tpch.LINEITEM_ROWS[sf], tpch.SCALE[sf]
 D = tpch.DATE_1995_03_15
-li = tpch.gen_lineitem(rows, scale, ["l_orderkey", "l_shipdate", "l_extendedprice", "l_discount"])
+li = tpch.gen_lineitem(rows, scale, ["l_orderkey", "l_shipdate", "l_extendedprice", "l_discount"] + (["l_quantity"] if "--tail" in sys.argv else []))
 n_ord = tpch.orders_for_lineitems(rows); od = tpch.gen_orders(n_ord, scale)
 n_cust = tpch.customers_for_scale(scale); cu = tpch.gen_customer(n_cust, scale)
 lt = rt.HipTable(1, tpch.chunk_rows(rows))
@@ -59,6 +60,65 @@ if "--general" in sys.argv:
         res["general"][name] = {"groups": total_, "seconds_prepare_and_run_best": min(cold), "seconds_prepared_run_best": min(warm),
                                 "top_keys": [r.key for r in rows_[:3]], "same_top_keys_as_the_q3_pipeline": [r.key for r in rows_] == [o[0] for o in out]}
         jq.close()
+# ---- the result tail of the general route (llkv_hip_join_groupby_set_tail): HAVING, ORDER BY and LIMIT before the groups leave the
+# device, against finish + llkv_hip_join_groupby_rows over every group (what a binding paid before, plus its own CPU filter)
+if "--tail" in sys.argv:
+    A, H = abi.AggregateSpec, abi.Having
+    AGGK, PAYK = abi.JOIN_ORDER_AGGREGATE, abi.JOIN_ORDER_PAYLOAD
+
+    def timed(fn, n=5):
+        fn()
+        ts_ = []
+        for _ in range(n):
+            t0 = time.perf_counter(); r = fn(); ts_.append(time.perf_counter() - t0)
+        return min(ts_), r
+
+    def rows_of(rs):
+        return [(r.key, r.payload, r.group_index, [v.value for v in r.values]) for r in rs]
+    res["tail"] = {}
+    # Q3: its own order and LIMIT 10
+    pay, order = [tpch.O_ORDERDATE, tpch.O_SHIPPRIORITY], [(AGGK, 0, True), (PAYK, 0, False)]
+    mk = lambda: rt.JoinGroupBy(lt, [F(tpch.L_SHIPDATE, O.GreaterThan(D))], tpch.L_ORDERKEY, ot, [F(tpch.O_ORDERDATE, O.LessThan(D))], tpch.O_ORDERKEY, [A.sum(rev)],
+                                dim_fk=tpch.O_CUSTKEY, dim2=ct, dim2_filters=[F(tpch.C_MKTSEGMENT, O.Equals("BUILDING"))], dim2_key=tpch.C_CUSTKEY)
+    plain, tailq = mk(), mk()
+    tailq.set_tail(pay, None, order, 0, 10)
+
+    def q3_plain():
+        plain.launch(); plain.finish_only()
+        return plain.result(pay, order, 10)
+
+    def q3_tail():
+        tailq.launch(); tailq.finish_only()
+        return tailq.tail_rows()
+    tp, (rp, np_) = timed(q3_plain)
+    tt, (rt_, nt) = timed(q3_tail)
+    res["tail"]["q3_limit_10"] = {"groups": nt, "seconds_finish_and_rows_best": tp, "seconds_tail_best": tt, "same_rows": rows_of(rp) == rows_of(rt_) and np_ == nt,
+                                  "route_note": tailq.route_note}
+    plain.close(); tailq.close()
+    # Q18 shape: lineitem ⋈ orders GROUP BY o_orderkey HAVING sum(l_quantity) > 300 ORDER BY sum(l_quantity) DESC, o_orderdate LIMIT 100
+    mk = lambda: rt.JoinGroupBy(lt, [], tpch.L_ORDERKEY, ot, [], tpch.O_ORDERKEY, [A.sum(tpch.L_QUANTITY)])
+    pay, order = [tpch.O_ORDERDATE], [(AGGK, 0, True), (PAYK, 0, False)]
+    plain, tailq = mk(), mk()
+    tailq.set_tail(pay, H.compare(H.agg(0), abi.CMP_GT, 300), order, 0, 100)
+
+    def q18_plain():  # every group leaves, ordered (the C call alone, no Python rows): the binding's CPU route then filters and cuts
+        plain.launch(); plain.finish_only()
+        payc, okc, h = (C.c_uint32 * 1)(*pay), (abi.CJoinOrderKey * 2)(), C.c_void_p()
+        for i_, o_ in enumerate(order): okc[i_].kind, okc[i_].index, okc[i_].descending, okc[i_].nulls_first = o_[0], o_[1], int(o_[2]), 0
+        rt.check(rt.lib().llkv_hip_join_groupby_rows(plain._h, payc, C.c_uint32(1), okc, C.c_uint32(2), C.c_uint64(2**64 - 1), C.byref(h)))
+        rt.lib().llkv_hip_join_rows_free(h)
+
+    def q18_tail():
+        tailq.launch(); tailq.finish_only()
+        return tailq.tail_rows()
+    tp, _ = timed(q18_plain, 2)
+    tt, (rt_, nt) = timed(q18_tail, 3)
+    # the order is sum DESC first, so the survivors are a prefix of the ordered groups
+    head, np_ = plain.result(pay, order, 1000)
+    kept = [r for r in head if r.values[0].value > 300]
+    res["tail"]["q18_having_limit_100"] = {"groups": np_, "survivors": nt, "seconds_finish_and_all_rows_best": tp, "seconds_tail_best": tt,
+                                           "same_rows": rows_of(kept[:100]) == rows_of(rt_) and (nt == len(kept) or len(kept) == 1000), "route_note": tailq.route_note}
+    plain.close(); tailq.close()
 # ---- Q3 over the reference's own DDL: the money columns as DECIMAL(15,2) (tpch.lineitem_as_decimal).  The exact call
 # (llkv_hip_join_groupby_topk_exact: integer sums of the scale-4 products, every cell bit-equal to the general route's) and, for
 # comparison, the general route those queries took before it (a sort-based GROUP BY of the fact key plus host ordering).
