@@ -1,0 +1,531 @@
+"""GPU (-m gpu): join → GROUP BY (llkv_hip_join_groupby_prepare / _rows) and its device tail (_set_tail / _tail_rows) at the
+edges the TPC-H star of test_gpu_join_group.py and the formula star of test_gpu_join_tail.py never reach: key dtypes and key
+ranges next to the ends of their type, payload cells of every admitted type under the device order, the boundaries of
+join_dim_cells_kernel (csrc/join_tail.hip), no group at all, the semi join's dim2, and the staging order of both key columns.
+
+Yardsticks: the rows are the oracle's `join_groupby(..., order=order, limit=None)` — a Python restatement over exact integers —
+the HAVING is tests/having_expr_model.evaluate over (key cell, payload cells …) and the aggregates of those rows, then the
+slice [offset : offset + limit] taken here.  Key, payload, group_index and integer cells exact; f64 sums within 1e-9.  The
+library's own having_eval is never the expectation, and result() only in the one place that says so (both deliveries of one
+query name the same rows).
+
+Every table is a formula over np.arange; every test first asserts — on the host, from numpy and the oracle alone — that the
+table is the one its case was designed for."""
+import importlib
+
+import numpy as np
+import pytest
+
+from conftest import same_value
+from having_expr_model import evaluate
+
+pytestmark = pytest.mark.gpu
+REL = 1e-9
+
+abi_mod = importlib.import_module("rust-llkv_amd.abi")
+H = abi_mod.Having
+LT, GT, GE = abi_mod.CMP_LT, abi_mod.CMP_GT, abi_mod.CMP_GT_EQ
+AGG, PAY, KEY = abi_mod.JOIN_ORDER_AGGREGATE, abi_mod.JOIN_ORDER_PAYLOAD, abi_mod.JOIN_ORDER_KEY
+I64, I32, U32, D32, F64, BOOL = abi_mod.DT_INT64, abi_mod.DT_INT32, abi_mod.DT_UINT32, abi_mod.DT_DATE32, abi_mod.DT_FLOAT64, abi_mod.DT_BOOLEAN
+I64_MIN, I64_MAX, I32_MIN, I32_MAX, U32_MAX = -(1 << 63), (1 << 63) - 1, -(1 << 31), (1 << 31) - 1, (1 << 32) - 1
+
+F_FK, F_Q, F_X, F_G = 1, 2, 3, 4                          # fact: key, Int64 argument, Float64 argument, a tag to filter by
+D_KEY, D_FLAG, D_P0, D_P1, D_P2, D_P3, D_FK = 1, 2, 3, 4, 5, 6, 7
+E_KEY, E_FLAG = 1, 2                                      # dim2
+
+
+# ---- helpers --------------------------------------------------------------------------------------------------------------------
+def same_rows(got, want, ctx=""):
+    """The rules of test_gpu_join_group.same_rows (copied: nothing is imported from a test file)."""
+    assert len(got) == len(want), (ctx, len(got), len(want))
+    for g, w in zip(got, want):
+        assert (g.key, g.payload, g.group_index) == (w[0], w[1], w[3]), (ctx, g, w)
+        for x, y in zip(g.values, w[2]):
+            assert x.dtype == y.dtype and x.is_null == y.is_null, (ctx, g.key, x, y)
+            if isinstance(y.value, float):
+                assert same_value(x.value, y.value, REL), (ctx, g.key, x, y)
+            else:
+                assert x == y, (ctx, g.key, x, y)
+
+
+def run_tail(jq, having, order, offset, limit, payload):
+    jq.set_tail(payload, having, order, offset, limit)
+    jq.launch()
+    jq.finish_only()
+    rows, total = jq.tail_rows()
+    return rows, total, jq.route_note
+
+
+def arr(values, dtype):
+    """Python ints → a numpy array of the column's storage type (no pass through a narrower or signed type on the way)."""
+    return np.array([int(v) for v in values], dtype=abi_mod.NUMPY_OF_DTYPE[dtype])
+
+
+def stage(rt, orc, table_id, chunks, cols, stats=()):
+    """One table on both sides: cols = [(field, dtype, values, valid | None)].  `stats`: fields whose (min, max) the caller
+    installs (a UInt32 column gets none at staging)."""
+    n = sum(chunks)
+    ht, ot = rt.HipTable(table_id, chunks), orc.OracleTable(n)
+    for fid, dt, values, valid in cols:
+        values = np.ascontiguousarray(values, dtype=abi_mod.NUMPY_OF_DTYPE[dt])
+        assert len(values) == n
+        ht.append_column(fid, dt, values, None if valid is None else np.asarray(valid, dtype=bool))
+        ot.add(fid, dt, values, None if valid is None else [bool(v) for v in valid])
+        if fid in stats:
+            ht.set_column_stats(fid, int(values.min()), int(values.max()))
+    return ht, ot
+
+
+class Star:
+    """A staged star, its prepared query and the oracle's ordered rows per order (computed once, never changed)."""
+
+    def __init__(self, rt, orc, fact, dim, aggs, payload, pay_dtypes, fact_filters=(), dim_filters=(), dim2=None, dim2_filters=(), dim_fk=0, key_dtype=I64):
+        self.orc, self.payload, self.aggs = orc, list(payload), aggs
+        self.key_dtypes = [key_dtype] + list(pay_dtypes)  # the model types a cell by its COLUMN: key 0 is the dimension key, key 1 + c payload column c
+        (self.ft, self.fo), (self.dt, self.do) = fact, dim
+        self.d2t, self.d2o = dim2 if dim2 is not None else (None, None)
+        self.args = dict(fact_filters=list(fact_filters), dim_filters=list(dim_filters), dim2_filters=list(dim2_filters), dim_fk=dim_fk)
+        self._cache = {}
+        kw = dict(dim_fk=dim_fk, dim2=self.d2t, dim2_filters=list(dim2_filters), dim2_key=E_KEY) if dim2 is not None else {}
+        self.jq = rt.JoinGroupBy(self.ft, list(fact_filters), F_FK, self.dt, list(dim_filters), D_KEY, aggs, **kw)
+        assert self.jq.route_note.startswith("join → GROUP BY")
+
+    def ordered(self, order):
+        k = repr(order)
+        if k not in self._cache:
+            a = self.args
+            kw = dict(dim_fk=a["dim_fk"], dim2=self.d2o, dim2_filters=a["dim2_filters"], dim2_key=E_KEY) if self.d2o is not None else {}
+            rows, total = self.orc.join_groupby(self.fo, a["fact_filters"], F_FK, self.do, a["dim_filters"], D_KEY, self.aggs, payload_fields=self.payload,
+                                                order=order, limit=None, **kw)
+            assert total == len(rows)
+            self._cache[k] = tuple(rows)
+        return self._cache[k]
+
+    def keeps(self, h, row):
+        if h is None:
+            return True
+        cells = [abi_mod.Value(I64, False, row[0])] + [abi_mod.Value(I64, p is None, p) for p in row[1]]
+        return evaluate(h, cells, self.key_dtypes, row[2]) is True
+
+    def expected(self, h, order, offset, limit):
+        kept = [r for r in self.ordered(order) if self.keeps(h, r)]
+        return (kept[offset:] if limit is None else kept[offset:offset + limit]), len(kept)
+
+    def check_result(self, order, limit, ctx=""):
+        """launch / finish_only / result(payload, order, limit) against the oracle (the caller has launched)."""
+        want, total = self.expected(None, order, 0, limit)
+        got, got_total = self.jq.result(self.payload, order, limit)
+        assert got_total == total, (ctx, got_total, total)
+        same_rows(got, want, f"{ctx} result order={order} limit={limit}")
+        return got
+
+    def check_tail(self, h, order, offset, limit, ctx="", device_order=None):
+        want, total = self.expected(h, order, offset, limit)
+        got, got_total, note = run_tail(self.jq, h, order, offset, limit, self.payload)
+        ctx = f"{ctx} tail order={order} offset={offset} limit={limit}: {note}"
+        assert got_total == total, (ctx, got_total, total)
+        same_rows(got, want, ctx)
+        if device_order is None:
+            device_order = limit is not None and total > 0
+        if device_order:
+            assert note.endswith("; order: device top-k"), ctx
+        elif limit is None and total:
+            assert "; order: host" in note, ctx
+        return got, note
+
+    def launch_plain(self):
+        self.jq.set_tail()
+        self.jq.launch()
+        self.jq.finish_only()
+
+    def close(self):
+        self.jq.close()
+
+
+def fact_columns(n, fk, fk_dtype, fk_valid=None, tag=None):
+    i = np.arange(n, dtype=np.int64)
+    q = (i * 31 + (i // 600) * 7) % 1000 - 500
+    x = ((i * 17) % 1000) / 8.0
+    cols = [(F_FK, fk_dtype, fk, fk_valid), (F_Q, I64, q, None), (F_X, F64, x, None)]
+    if tag is not None:
+        cols.append((F_G, I64, tag, None))
+    return cols
+
+
+def std_aggs():
+    A = abi_mod.AggregateSpec
+    return [A.count_star(), A.sum(F_Q), A.min(F_Q), A.max(F_Q), A.sum(F_X)]
+
+
+def refused(fn, kind, text):
+    with pytest.raises(abi_mod.LlkvError) as e:
+        fn()
+    kinds = kind if isinstance(kind, tuple) else (kind,)
+    assert e.value.kind in kinds and text in e.value.message, e.value
+    return e.value
+
+
+# ---- 1. key dtype and range --------------------------------------------------------------------------------------------------------
+# name → (fact key dtype, dimension key dtype, lo, hi of the dimension key column, keys that must not join)
+KEY_CASES = {
+    "Int64 around zero": (I64, I64, -5000, 5000, [-5001, 5001, I64_MIN, I64_MAX]),                                # span 10 000: no multiple of 64
+    "Int64 at INT64_MIN": (I64, I64, I64_MIN, I64_MIN + (1 << 20), [I64_MIN + (1 << 20) + 1, I64_MAX, 0, -1]),        # span 2^20: a multiple of 64
+    "Int64 at INT64_MAX": (I64, I64, I64_MAX - (1 << 20), I64_MAX, [I64_MAX - (1 << 20) - 1, I64_MIN, 0, -1]),
+    "Int32 at INT32_MIN": (I32, I32, I32_MIN, I32_MIN + 9000, [I32_MIN + 9001, I32_MAX, 0, -1]),
+    "Date32 before 1970": (D32, D32, -8000, 1000, [-8001, 1001, I32_MIN, I32_MAX]),
+    "UInt32 at UINT32_MAX": (U32, U32, U32_MAX - 70000, U32_MAX, [U32_MAX - 70001, 0, I32_MAX, 1 << 31]),
+    "Int32 fact, Int64 dimension": (I32, I64, -5000, 5000, [-5001, 5001, I32_MIN, I32_MAX]),
+}
+N_DIM1, N_FACT1 = 600, 7000
+
+
+def key_case_arrays(name):
+    fdt, ddt, lo, hi, outside = KEY_CASES[name]
+    span = hi - lo
+    r = np.arange(N_DIM1)
+    offs = [(int(j) * span) // (N_DIM1 - 1) for j in (r * 7) % N_DIM1]  # distinct, 0 and span among them, not in key order
+    dkey = [lo + o for o in offs]
+    flag = np.where((r * 7) % N_DIM1 % 3 == 1, 0, 1)  # the filter drops every third key of the range; the two ends stay
+    cand = dkey + list(outside)
+    i = np.arange(N_FACT1)
+    fk = [cand[int(j)] for j in i % len(cand)]
+    fk_valid = (i % 11) != 0
+    return dict(fdt=fdt, ddt=ddt, lo=lo, hi=hi, span=span, dkey=dkey, flag=flag, fk=fk, fk_valid=fk_valid, outside=outside,
+                pay0=r % 7, pay0_valid=(r % 13) != 0, pay1=r - 300)
+
+
+def key_case_star(rt, orc, name):
+    a = key_case_arrays(name)
+    F, O = abi_mod.Filter, abi_mod.Operator
+    fact = stage(rt, orc, 1, [4096, N_FACT1 - 4096], fact_columns(N_FACT1, arr(a["fk"], a["fdt"]), a["fdt"], a["fk_valid"]))
+    dim = stage(rt, orc, 2, [N_DIM1], [(D_KEY, a["ddt"], arr(a["dkey"], a["ddt"]), None), (D_FLAG, I64, a["flag"], None), (D_P0, I64, a["pay0"], a["pay0_valid"]),
+                                      (D_P1, I32, a["pay1"], None)], stats=(D_KEY,) if a["ddt"] == U32 else ())
+    return a, lambda: Star(rt, orc, fact, dim, std_aggs(), [D_P0, D_P1], [I64, I32], fact_filters=[F(F_Q, O.GreaterThan(-400))], dim_filters=[F(D_FLAG, O.GreaterThan(0))],
+                             key_dtype=a["ddt"])
+
+
+@pytest.mark.parametrize("name", list(KEY_CASES))
+def test_key_dtypes_and_ranges(rt, orc, name):
+    """Keys of every admitted dtype at the ends of their type, through result() and through the device tail.  The fact table also
+    holds min − 1 and max + 1 of the dimension range (where the type has them), the opposite extreme of the type (key − min
+    wraps), keys the dimension filter removed, and NULL cells whose stored value is a qualifying key: none of them may join.
+    A UInt32 column gets no statistics at staging, so the test installs them (set_column_stats) — without them the prepare
+    refuses, see test_key_refusals.
+    "Int32 fact, Int64 dimension": the prepare ACCEPTS the pair (both sides are read as i64 and compared as images against the
+    dimension's minimum) and the rows are the oracle's."""
+    a, make = key_case_star(rt, orc, name)
+    # -- the table is the one the case was designed for (host only)
+    dkey, flag, fk = a["dkey"], a["flag"], a["fk"]
+    assert len(set(dkey)) == N_DIM1 and min(dkey) == a["lo"] and max(dkey) == a["hi"] and dkey != sorted(dkey)
+    qual = {k for k, f in zip(dkey, flag) if f}
+    assert len(qual) == 400 and a["lo"] in qual and a["hi"] in qual
+    assert (a["span"] % 64 == 0) == (name in ("Int64 at INT64_MIN", "Int64 at INT64_MAX"))
+    assert all(k not in set(dkey) for k in a["outside"]) and all(k in fk for k in a["outside"])
+    if name == "Int64 around zero":
+        assert {a["lo"] - 1, a["hi"] + 1, I64_MIN, I64_MAX} <= set(fk)
+    assert sum(1 for k, v in zip(fk, a["fk_valid"]) if not v and k in qual) > 300            # NULL cells over qualifying keys
+    assert sum(1 for k, v in zip(fk, a["fk_valid"]) if v and k in set(dkey) - qual) > 1500    # filtered dimension rows
+    try:
+        star = make()
+    except abi_mod.LlkvError as e:  # only the mixed pair may be handed back, and only by name
+        assert name == "Int32 fact, Int64 dimension" and e.kind in ("Unsupported", "InvalidArgumentError"), (name, e)
+        return
+    rows = star.ordered([])
+    assert len(rows) == 400 and {w[0] for w in rows} == qual                                  # both ends of the range form a group
+    assert sum(w[2][0].value for w in rows) == sum(1 for i, (k, v) in enumerate(zip(fk, a["fk_valid"])) if v and k in qual and (i * 31 + (i // 600) * 7) % 1000 - 500 > -400)
+    # -- result()
+    star.launch_plain()
+    orders = [([], None), ([(KEY, 0, True)], 50), ([(PAY, 0, False, True), (AGG, 1, True)], 100), ([(KEY, 0)], 1)]
+    plain = {}
+    for order, limit in orders:
+        plain[repr(order)] = star.check_result(order, limit, name)
+    assert plain[repr([(KEY, 0, True)])][0].key == a["hi"] and plain[repr([(KEY, 0)])][0].key == a["lo"]
+    # -- the device tail, and the tail without a limit
+    for order, limit in orders:
+        got, note = star.check_tail(None, order, 0, limit, name)
+        assert [(g.key, g.payload, g.group_index, g.values) for g in got] == [(g.key, g.payload, g.group_index, g.values) for g in plain[repr(order)]], (name, order)
+    star.check_tail(H.compare(H.agg(0), GE, 8), [(AGG, 1, True)], 2, 1022, name)
+    # a HAVING over the key itself: on the device for an Int64 key, on the host for the 4-byte ones (a Date32 cell compares FALSE)
+    got, note = star.check_tail(H.compare(H.key(0), GE, a["hi"] - 5), [(KEY, 0, True)], 0, 10, name, device_order=a["ddt"] == I64)
+    assert (len(got) > 0) == (a["ddt"] != D32) and ("; having: device" in note) == (a["ddt"] == I64), (name, note)
+    star.close()
+
+
+def test_key_refusals(rt, orc):
+    """What the prepare hands back: a key range of exactly 2^32 (checked before any allocation), a UInt32 dimension key without
+    installed statistics, a dimension key with NULL cells; and a Float64 or Boolean payload column, by result() and by set_tail."""
+    A, n = abi_mod.AggregateSpec, 64
+    i = np.arange(n, dtype=np.int64)
+    fact = stage(rt, orc, 1, [n], fact_columns(n, i % 8, I64))
+    wide = np.where(i == n - 1, 1 << 32, i)
+    assert int(wide.max()) - int(wide.min()) == 1 << 32
+    u = arr([U32_MAX - int(v) for v in i], U32)
+    dim = stage(rt, orc, 2, [n], [(D_KEY, I64, i, None), (D_FLAG, I64, wide, None), (D_P0, I64, i, (i % 5) != 0), (D_P1, U32, u, None), (D_P2, F64, i / 2.0, None),
+                                  (D_P3, BOOL, i % 2, None)])
+    ft, dt = fact[0], dim[0]
+    refused(lambda: rt.JoinGroupBy(ft, [], F_FK, dt, [], D_FLAG, [A.count_star()]), "Unsupported", "no statistics-bounded range")
+    refused(lambda: rt.JoinGroupBy(ft, [], F_FK, dt, [], D_P1, [A.count_star()]), "Unsupported", "no statistics-bounded range")
+    refused(lambda: rt.JoinGroupBy(ft, [], F_FK, dt, [], D_P0, [A.count_star()]), "Unsupported", "NULL cells")
+    jq = rt.JoinGroupBy(ft, [], F_FK, dt, [], D_KEY, [A.count_star()])
+    jq.launch()
+    jq.finish_only()
+    for field in (D_P2, D_P3):
+        refused(lambda: jq.result([field], [], None), "Unsupported", "integer column expected")
+        refused(lambda: jq.set_tail([D_P0, field], None, [(KEY, 0)], 0, 5), "Unsupported", "integer column expected")
+    got, total = jq.result([D_P0], [(KEY, 0)], None)  # (the refusals left the query as it was)
+    assert total == 8 and [(g.key, g.payload, g.values[0].value) for g in got] == [(k, [None if k % 5 == 0 else k], 8) for k in range(8)]
+    jq.close()
+
+
+# ---- 2. payload cell types under the device order --------------------------------------------------------------------------------------
+N_DIM2, N_FACT2 = 900, 12000
+PAY2 = [D_P0, D_P1, D_P2, D_P3]
+PAY2_DTYPES = [I64, I32, U32, D32]
+
+
+def payload_arrays():
+    r = np.arange(N_DIM2)
+    p0 = [[I64_MIN, I64_MAX, -1, 0, 5][int(j)] for j in r % 5]
+    p1 = [[I32_MIN, -1, 7, I32_MAX][int(j)] for j in r % 4]
+    p2 = [[1 << 31, U32_MAX, 3, I32_MAX][int(j)] for j in (r // 2) % 4]
+    p3 = [[-20000, -1, 0, 12000][int(j)] for j in (r // 5) % 4]
+    i = np.arange(N_FACT2, dtype=np.int64)
+    return dict(key=(r * 1103) % N_DIM2 + 100, flag=r % 3, p0=p0, p0_valid=(r % 7) != 0, p1=p1, p1_valid=(r % 11) != 0, p2=p2, p3=p3, fk=(i * 7) % 1100 + 50)
+
+
+@pytest.fixture(scope="module")
+def pay_star(rt, orc):
+    a = payload_arrays()
+    F, O = abi_mod.Filter, abi_mod.Operator
+    fact = stage(rt, orc, 1, [8192, N_FACT2 - 8192], fact_columns(N_FACT2, a["fk"], I64))
+    dim = stage(rt, orc, 2, [512, N_DIM2 - 512], [(D_KEY, I64, a["key"], None), (D_FLAG, I64, a["flag"], None), (D_P0, I64, arr(a["p0"], I64), a["p0_valid"]),
+                                                  (D_P1, I32, arr(a["p1"], I32), a["p1_valid"]), (D_P2, U32, arr(a["p2"], U32), None), (D_P3, D32, arr(a["p3"], D32), None)])
+    star = Star(rt, orc, fact, dim, std_aggs()[:4], PAY2, PAY2_DTYPES, dim_filters=[F(D_FLAG, O.GreaterThan(0))])
+    yield star
+    star.close()
+
+
+def test_the_payload_star_is_the_one_the_cases_were_worked_out_for(pay_star):
+    rows = pay_star.ordered([])
+    assert len(rows) == 600
+    assert [w[3] for w in rows] == list(range(600)) and [w[0] for w in rows] != sorted(w[0] for w in rows)  # position order is not key order
+    col = lambda c: [w[1][c] for w in rows]
+    assert {v for v in col(0)} == {I64_MIN, I64_MAX, -1, 0, 5, None} and {v for v in col(1)} == {I32_MIN, -1, 7, I32_MAX, None}
+    assert {v for v in col(2)} == {1 << 31, U32_MAX, 3, I32_MAX} and {v for v in col(3)} == {-20000, -1, 0, 12000}
+    assert sum(1 for v in col(0) if v is None) == 86 and sum(1 for v in col(1) if v is None) == 54
+    for c in range(4):  # every payload value is shared by many groups: the position tie-break decides
+        assert min(col(c).count(v) for v in set(col(c))) >= 50
+    assert all(10 <= w[2][0].value <= 11 for w in rows)
+
+
+@pytest.mark.parametrize("column", range(4), ids=["Int64", "Int32", "UInt32", "Date32"])
+def test_each_payload_type_orders_on_the_device(pay_star, column):
+    """One payload column as the only order term under every (descending, nulls_first): offset 3, limit 40 through the device
+    top-k (order_key_kernel takes the cell through i64_image), and again without a limit on the host."""
+    for descending in (False, True):
+        for nulls_first in (False, True):
+            order = [(PAY, column, descending, nulls_first)]
+            got, note = pay_star.check_tail(None, order, 3, 40, f"payload {column}", device_order=True)
+            assert len(got) == 40
+            pay_star.check_tail(None, order, 0, None, f"payload {column}")
+
+
+def test_two_payload_terms_and_an_aggregate_order_on_the_device(pay_star):
+    for order in ([(PAY, 1, True, True), (PAY, 2, False), (AGG, 1, True)], [(PAY, 2, True), (PAY, 0, False, True), (AGG, 2, False)],
+                  [(PAY, 3, False), (PAY, 1, False, False), (AGG, 3, True)]):
+        got, note = pay_star.check_tail(None, order, 3, 40, "three terms", device_order=True)
+        assert len(got) == 40
+        pay_star.check_tail(None, order, 0, None, "three terms")
+
+
+HAVING2 = {  # name → (HAVING, survivors, where it runs)
+    "Int64: pay < 0 OR pay IS NULL": (H.or_(H.compare(H.key(1), LT, 0), H.is_null(H.key(1))), 292, "device"),
+    "Int64: pay IN (INT64_MIN, INT64_MAX)": (H.in_list(H.key(1), [I64_MIN, I64_MAX]), 206, "device"),
+    "Int32: pay < 0 OR pay IS NULL": (H.or_(H.compare(H.key(2), LT, 0), H.is_null(H.key(2))), 327, "host (key 2 is a Int32 column)"),
+    "Int32: pay IN (INT32_MIN, INT32_MAX)": (H.in_list(H.key(2), [I32_MIN, I32_MAX]), 272, "host (key 2 is a Int32 column)"),
+    "UInt32: pay < 0 OR pay IS NULL": (H.or_(H.compare(H.key(3), LT, 0), H.is_null(H.key(3))), 0, "host (key 3 is a UInt32 column)"),
+    "UInt32: pay IN (2^31, 2^32 - 1)": (H.in_list(H.key(3), [1 << 31, U32_MAX]), 301, "host (key 3 is a UInt32 column)"),
+    # a Date32 payload cell is a Date32 value: every compare with a number is FALSE (as test_gpu_join_tail pins it)
+    "Date32: pay < 0": (H.compare(H.key(4), LT, 0), 0, "host (key 4 is a Date32 column)"),
+    "Date32: pay > 0": (H.compare(H.key(4), GT, 0), 0, "host (key 4 is a Date32 column)"),
+}
+
+
+@pytest.mark.parametrize("name", list(HAVING2))
+def test_having_over_each_payload_type(pay_star, name):
+    h, survivors, where = HAVING2[name]
+    order = [(PAY, 0, True, True), (AGG, 1, False)]
+    for offset, limit in ((3, 40), (0, None)):
+        want, total = pay_star.expected(h, order, offset, limit)
+        assert total == survivors, (name, total)
+        got, note = pay_star.check_tail(h, order, offset, limit, name, device_order=False)
+        assert f"; having: {where}" in note, (name, note)
+        if where == "device" and limit is not None:
+            assert note.endswith("; having: device; order: device top-k"), note
+
+
+# ---- 3. the tail kernel's boundaries ---------------------------------------------------------------------------------------------------
+K0, N_G, N_DIM3 = -5000, 769, 6153
+
+
+def boundary_keys():
+    """The distinct joining fact keys G (ascending): 256 + 256 + 256 + 1 of them, one stretch of dimension keys per workgroup."""
+    j = np.arange(256)
+    offs = np.concatenate([(j * 2047) // 255, 2050 + (j * 2048) // 255, 4101 + (j * 2046) // 255, [N_DIM3 - 1]])
+    return K0 + offs
+
+
+@pytest.mark.parametrize("staged", ["ascending", "permuted"])
+def test_the_tail_kernel_at_its_slice_and_group_boundaries(rt, orc, staged):
+    """join_dim_cells_kernel (csrc/join_tail.hip) with kTailGroups = 256 groups per workgroup and kTailSlice = 2048 dimension keys
+    in LDS — a change to either constant has to move the stretches below.  The dimension holds the keys −5000 + r, r in [0, 6153),
+    all qualifying; the 769 groups give the four workgroups of one launch stretches of exactly 2048 keys (the slice full, first key
+    = image 0), 2049 (one too many: resolved in global memory), 2047, and one single group whose key is the LAST dimension key
+    (bound[1] = at + 1 == n_dim).  Fact filters then keep exactly 256 groups (one full workgroup), 257 (a second workgroup of one
+    group) and one."""
+    G = boundary_keys()
+    r = np.arange(N_DIM3, dtype=np.int64)
+    # -- the stretches, from numpy alone: the dimension keys are contiguous, so a key's index among the sorted keys is key − K0
+    assert len(G) == N_G and np.all(np.diff(G) > 0) and G[0] == K0 and G[-1] == K0 + N_DIM3 - 1
+    at = G - K0
+    assert [int(at[min(w * 256 + 255, N_G - 1)] + 1 - at[w * 256]) for w in range(4)] == [2048, 2049, 2047, 1]
+    dkey = K0 + (r if staged == "ascending" else (r * 1103) % N_DIM3)
+    assert sorted(dkey.tolist()) == list(range(K0, K0 + N_DIM3)) and (staged == "ascending") == bool(np.all(np.diff(dkey) > 0))
+    p0, p0_valid, p1 = r * 3 - 7000, (r % 13) != 0, r - 3000
+    n = N_G * 8 + 40
+    i = np.arange(n, dtype=np.int64)
+    tag = np.where(i < N_G * 8, i % N_G, N_G)  # the group a row belongs to; the last 40 rows hold keys next to the range and join nothing
+    fk = np.where(i < N_G * 8, G[i % N_G], np.where(i % 2 == 0, K0 - 1 - (i % 7), K0 + N_DIM3 + (i % 5)))
+    assert set(fk[tag == N_G].tolist()).isdisjoint(dkey.tolist()) and {K0 - 1, K0 + N_DIM3} <= set(fk.tolist())
+    F, O = abi_mod.Filter, abi_mod.Operator
+    fact = stage(rt, orc, 1, [4096, n - 4096], fact_columns(n, fk, I64, tag=tag))
+    dim = stage(rt, orc, 2, [4096, N_DIM3 - 4096], [(D_KEY, I64, dkey, None), (D_P0, I64, p0, p0_valid), (D_P1, I32, p1, None)])
+    row_of_key = {int(k): int(j) for j, k in enumerate(dkey)}
+    for name, filters, groups in (("every group", [], N_G), ("256 groups", [F(F_G, O.LessThan(256))], 256), ("257 groups", [F(F_G, O.LessThan(257))], 257),
+                                  ("one group", [F(F_G, O.Equals(N_G - 1))], 1)):
+        star = Star(rt, orc, fact, dim, std_aggs()[:4], [D_P0, D_P1], [I64, I32], fact_filters=filters)
+        rows = star.ordered([(KEY, 0)])
+        assert len(rows) == groups and [w[0] for w in rows] == [int(k) for k in (G[:groups] if groups > 1 else G[-1:])]
+        for w in rows:  # the oracle's cells are the row's own (a wrong row is a wrong cell)
+            j = row_of_key[w[0]]
+            assert w[3] == j and w[1] == [None if j % 13 == 0 else j * 3 - 7000, j - 3000] and w[2][0].value == 8
+        assert sum(1 for w in rows if w[1][0] is None) == sum(1 for k in (G[:groups] if groups > 1 else G[-1:]) if row_of_key[int(k)] % 13 == 0)
+        ctx = f"{staged}, {name}"
+        got, note = star.check_tail(None, [(KEY, 0)], 0, None, ctx)
+        assert len(got) == groups
+        got, note = star.check_tail(None, [(KEY, 0)], 0, 1024, ctx, device_order=True)
+        assert len(got) == groups
+        star.check_tail(H.or_(H.is_null(H.key(1)), H.compare(H.key(1), GE, 0)), [(PAY, 1, True)], 1, 1023, ctx, device_order=groups > 1)
+        star.close()
+
+
+# ---- 4. no groups at all ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["no dimension row", "no fact row", "no fact key in the key set"])
+def test_no_group_reaches_the_tail(rt, orc, case):
+    """Zero groups through a tail with payload, HAVING and order (every buffer of the tail is sized by n = 0): ([], 0) and no
+    error, with and without a limit; after clearing the tail result() says the same."""
+    n, nd = 3000, 200
+    i, r = np.arange(n, dtype=np.int64), np.arange(nd, dtype=np.int64)
+    fk = (i * 7) % 300 - 50 if case != "no fact key in the key set" else np.where(i % 2 == 0, -51 - (i % 9), 150 + (i % 9))
+    dkey = (r * 11) % nd - 50  # −50 … 149
+    F, O = abi_mod.Filter, abi_mod.Operator
+    fact = stage(rt, orc, 1, [2048, n - 2048], fact_columns(n, fk, I64))
+    dim = stage(rt, orc, 2, [nd], [(D_KEY, I64, dkey, None), (D_FLAG, I64, r % 3, None), (D_P0, I64, r % 7, (r % 13) != 0), (D_P1, I32, r - 100, None)])
+    dim_filters = [F(D_FLAG, O.GreaterThan(5))] if case == "no dimension row" else [F(D_FLAG, O.GreaterThan(0))]
+    fact_filters = [F(F_Q, O.GreaterThan(5000))] if case == "no fact row" else [F(F_Q, O.GreaterThan(-400))]
+    assert set(dkey.tolist()) == set(range(-50, 150)) and (case != "no fact key in the key set" or set(fk.tolist()).isdisjoint(dkey.tolist()))
+    assert {-51, 150} <= set(fk.tolist()) or case != "no fact key in the key set"
+    star = Star(rt, orc, fact, dim, std_aggs(), [D_P0, D_P1], [I64, I32], fact_filters=fact_filters, dim_filters=dim_filters)
+    assert star.ordered([]) == ()
+    h = H.or_(H.compare(H.agg(0), GT, 1), H.is_null(H.key(1)))
+    order = [(PAY, 0, True, True), (AGG, 1, True)]
+    for limit in (10, None):
+        got, total, note = run_tail(star.jq, h, order, 0, limit, star.payload)
+        assert (got, total) == ([], 0), (case, limit, note)
+    star.launch_plain()
+    assert star.jq.result([], [], None) == ([], 0)
+    assert star.jq.result(star.payload, order, 10) == ([], 0)
+    star.close()
+
+
+# ---- 5. dim2, and the staging order of the keys ----------------------------------------------------------------------------------------
+def semi_tables(rt, orc, fk_valid=None):
+    n, nd, n2 = 5000, 300, 40
+    i, r, e = np.arange(n, dtype=np.int64), np.arange(nd, dtype=np.int64), np.arange(n2, dtype=np.int64)
+    fact = stage(rt, orc, 1, [4096, n - 4096], fact_columns(n, (i * 13) % 340 - 20, I64))
+    dim = stage(rt, orc, 2, [nd], [(D_KEY, I64, (r * 7) % nd, None), (D_FLAG, I64, r % 4, None), (D_P0, I64, r % 7, (r % 13) != 0), (D_P1, I32, 100 - r, None),
+                                  (D_FK, I64, r % 25 + 8, fk_valid)])  # 8 … 32: both sides of dim2's keys 10 … 29
+    dim2 = stage(rt, orc, 3, [n2], [(E_KEY, I64, e // 2 + 10, None), (E_FLAG, I64, (e * 3) % 8, None)])  # every key twice
+    return fact, dim, dim2
+
+
+@pytest.mark.parametrize("keep", ["half", "none"])
+def test_dim2_with_repeated_keys_and_with_no_row(rt, orc, keep):
+    """The semi join's key set from a dim2 whose every key occurs twice, under a filter that keeps about half of its rows (some
+    keys once, some twice, some not at all) or none: result() and a device tail against the oracle called with its dim2 arguments."""
+    fact, dim, dim2 = semi_tables(rt, orc)
+    F, O = abi_mod.Filter, abi_mod.Operator
+    e = np.arange(40)
+    kept = e[(e * 3) % 8 < (4 if keep == "half" else 0)]
+    keys2 = (kept // 2 + 10).tolist()
+    assert len(kept) == (20 if keep == "half" else 0)
+    if keep == "half":
+        assert {keys2.count(k) for k in set(keys2)} == {1, 2} and len(set(keys2)) < 20  # once, twice, and some keys not at all
+    star = Star(rt, orc, fact, dim, std_aggs(), [D_P0, D_P1], [I64, I32], fact_filters=[F(F_Q, O.GreaterThan(-400))], dim_filters=[F(D_FLAG, O.GreaterThan(0))],
+                dim2=dim2, dim2_filters=[F(E_FLAG, O.LessThan(4 if keep == "half" else 0))], dim_fk=D_FK)
+    rows = star.ordered([])
+    r = np.arange(300)
+    want_keys = {int((j * 7) % 300) for j in r if j % 4 > 0 and int(j % 25 + 8) in set(keys2)}
+    assert {w[0] for w in rows} == want_keys and (len(rows) > 60 if keep == "half" else len(rows) == 0)
+    star.launch_plain()
+    for order, limit in (([], None), ([(AGG, 1, True), (PAY, 0, False, True)], 20), ([(KEY, 0, True)], 7)):
+        star.check_result(order, limit, keep)
+    for order, offset, limit in (([(AGG, 1, True), (PAY, 0, False, True)], 2, 20), ([(KEY, 0)], 0, None)):
+        star.check_tail(H.compare(H.agg(0), GE, 13), order, offset, limit, keep)
+        star.check_tail(None, order, offset, limit, keep)
+    star.close()
+
+
+def test_a_nullable_dim_fk_is_refused(rt, orc):
+    """A foreign key with NULL cells on the dimension side of the semi join: the lowering of the dimension's selection refuses it
+    (lower_selection_in_set with null_key_matches_nothing = false)."""
+    fact, dim, dim2 = semi_tables(rt, orc, fk_valid=(np.arange(300) % 9) != 0)
+    A = abi_mod.AggregateSpec
+    refused(lambda: rt.JoinGroupBy(fact[0], [], F_FK, dim[0], [], D_KEY, [A.count_star()], dim_fk=D_FK, dim2=dim2[0], dim2_filters=[], dim2_key=E_KEY),
+            "Unsupported", "NULL join keys in the join-aggregate pipeline")
+
+
+@pytest.mark.parametrize("case", ["descending dimension key", "ascending dimension key under a filter", "clustered fact key with NULL cells"])
+def test_staging_order_of_the_keys(rt, orc, case):
+    """A dimension key staged in descending order; one staged strictly ascending under a filter that drops every third row (the
+    prepare skips its sort while positions are not row numbers); a non-decreasing fact key with NULL cells whose stored values
+    break the order.  Both deliveries against the oracle."""
+    n, nd = 6000, 900
+    i, r = np.arange(n, dtype=np.int64), np.arange(nd, dtype=np.int64)
+    F, O = abi_mod.Filter, abi_mod.Operator
+    dkey = (nd - 1 - r) * 3 - 1000 if case == "descending dimension key" else r * 3 - 1000
+    flag = np.where(r % 3 == 1, 0, 1)
+    fk, fk_valid = ((i * 37) % (nd + 20)) * 3 - 1030 + (i % 50 == 0), (i % 11) != 0  # (every 50th row: a key between two dimension keys)
+    if case == "clustered fact key with NULL cells":
+        fk, fk_valid = (i // 5) * 3 - 1300, (i % 17) != 0
+        assert np.all(np.diff(fk) >= 0)
+        fk = np.where(fk_valid, fk, ((i * 7) % nd) * 3 - 1000)  # a NULL cell holds some qualifying key, out of order
+        assert np.any(np.diff(fk) < 0) and np.all(np.diff(fk[fk_valid]) >= 0)
+    if case == "descending dimension key":
+        assert np.all(np.diff(dkey) < 0)
+    else:
+        assert np.all(np.diff(dkey) > 0)
+    fact = stage(rt, orc, 1, [4096, n - 4096], fact_columns(n, fk, I64, fk_valid))
+    dim = stage(rt, orc, 2, [512, nd - 512], [(D_KEY, I64, dkey, None), (D_FLAG, I64, flag, None), (D_P0, I64, r % 7, (r % 13) != 0), (D_P1, I32, r - 450, None)])
+    star = Star(rt, orc, fact, dim, std_aggs(), [D_P0, D_P1], [I64, I32], fact_filters=[F(F_Q, O.GreaterThan(-400))], dim_filters=[F(D_FLAG, O.GreaterThan(0))])
+    rows = star.ordered([])
+    qual = [int(k) for k, f in zip(dkey, flag) if f]
+    assert len(qual) == 600 and len(rows) > 400 and {w[0] for w in rows} <= set(qual)
+    assert all(qual.index(w[0]) == w[3] for w in rows) and any(w[3] != int(np.where(dkey == w[0])[0][0]) for w in rows)  # positions are not row numbers
+    star.launch_plain()
+    for order, limit in (([], None), ([(PAY, 1, True)], 30), ([(AGG, 1, True), (KEY, 0)], 25)):
+        star.check_result(order, limit, case)
+    for order, offset, limit in (([(PAY, 1, True)], 3, 30), ([], 0, 1024), ([(KEY, 0, True)], 0, None)):
+        star.check_tail(None, order, offset, limit, case)
+        star.check_tail(H.or_(H.is_null(H.key(1)), H.compare(H.agg(1), LT, 0)), order, offset, limit, case)
+    star.close()
