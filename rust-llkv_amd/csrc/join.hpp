@@ -356,18 +356,15 @@ hipError_t hj_launch_run_heads(const uint64_t *sorted, uint64_t n, uint64_t *fla
 hipError_t hj_launch_sum_f64_ordered(const uint64_t *vals, uint64_t n, int as_int, double *out, double *scratch /* ⌈n / 65 536⌉ doubles */, hipStream_t s);
 
 // ---- join → GROUP BY with an aggregate list (join_group.cpp) --------------------------------------------------------------------
-// For m group keys: bisection in the qualifying dimension rows sorted by key image (value − base) → the row's payload cells
-// (out_payload[c][i], sign-extended; out_valid[c][i] = 0 for a NULL cell) and its position among the qualifying rows in row order
-// (out_pos[i]; ~0u when the key is not there).
+// The dimension rows of n group keys in ASCENDING order, in HBM (join_tail.hip; the one lookup of every delivery, join_group.cpp:
+// dim_cells): the qualifying dimension rows are sorted by key image (value − base), a workgroup bounds its stretch of groups in
+// those keys and resolves them inside that slice (in LDS when it fits).  out_kv / out_kvalid: [cols.n + 1][n] key cells — the
+// row's payload cells (sign-extended; validity 0 for a NULL cell), then its position among the qualifying rows in row order
+// (0xFFFFFFFF when the key is not there; its validity is always 1).
 struct JoinPayloadCols {
   JoinKeyColumn col[4];
   uint32_t n;
 };
-hipError_t hj_launch_lookup_payload(const uint64_t *sorted_keys, const uint64_t *sorted_rows, const uint32_t *sorted_pos, uint64_t n_dim, const int64_t *probe_keys,
-                                    long long base, uint64_t m, const JoinPayloadCols &cols, int64_t *out_payload, uint8_t *out_valid, uint32_t *out_pos, hipStream_t s);
-// … for n group keys in HBM in ASCENDING order (join_tail.hip): a workgroup bounds its stretch of groups in the sorted dimension
-// keys and resolves them inside that slice (in LDS when it fits).  out_kv / out_kvalid: [cols.n + 1][n] key cells — the payload
-// columns, then the position (0xFFFFFFFF when the key is not there; its validity is always 1).
 hipError_t hj_launch_join_dim_cells(const int64_t *group_keys, uint64_t n, const uint64_t *sorted_keys, const uint64_t *sorted_rows, const uint32_t *sorted_pos,
                                     uint64_t n_dim, long long base, const JoinPayloadCols &cols, int64_t *out_kv, uint8_t *out_kvalid, hipStream_t s);
 

@@ -12,17 +12,21 @@
 //   2. GROUP BY the fact key over the fact rows that pass   filters ∧ InKeySet<fact key>   — the sort-based GROUP BY
 //      (group_sort.cpp) with one more conjunct: every accumulator, the PlanValue argument semantics (decimals included), NULL
 //      handling and the sharded merge of partial groups are its own; a fact table clustered by the key needs no sort
-//   3. per result group: bisection of its key in the qualifying dimension rows sorted by key → payload cells and the row's
-//      position (the last tie-break of the order), ORDER BY / LIMIT on the host over the finalized cells.
-//      With a result tail (llkv_hip_join_groupby_set_tail: HAVING, ORDER BY, OFFSET / LIMIT) step 3 runs on the device before anything is
-//      copied out: join_tail.hip merges the groups (ascending keys) with the sorted dimension rows into payload and position cells, and
-//      the GROUP BY's own device HAVING and top-k take them as key cells — the end of this file.
+//   3. per result group: its dimension row → payload cells and the row's position (the last tie-break of the order).  The groups are
+//      in ascending key order and the qualifying dimension rows are kept sorted by key, so ONE kernel — join_dim_cells_kernel
+//      (join_tail.hip), a merge of two sorted lists — looks them up for every delivery, through one helper (dim_cells): the groups
+//      become extended key cells (key, payload …, position).  Over those cells
+//        _rows       orders on the host (its own partial_sort over the finalized cells) and cuts at LIMIT: a pure reader of the
+//                    finished groups
+//        the tail    (llkv_hip_join_groupby_set_tail: HAVING, ORDER BY, OFFSET / LIMIT) extends the groups in HBM before anything is copied
+//                    out, and the GROUP BY's own device HAVING and top-k take the payload and the position as key cells; the merged
+//                    groups of a sharded fact table are extended on the host side and filtered and ordered by Query::apply_order
+//      One translation of the caller's ORDER BY (join_order_spec) and one row builder (build_join_rows) serve both.
 // No joined row ever exists: the fact columns are read once (predicate columns, then the arguments of the rows that join).
 #include "engine.hpp"
 #include "join.hpp"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <numeric>
 #include <vector>
@@ -80,25 +84,51 @@ struct JoinGroupState {
   uint64_t n_dim = 0;
   long long key_base = 0;
   uint32_t dim_key_field = 0;
+  ColumnInfo pos_info; // the position column of the extended key cells: an Int64 that is never NULL
   // the result tail (llkv_hip_join_groupby_set_tail): its HAVING and its order live in Query::having / Query::order, over the key
   // cells (key, payload …, position); here what turns a group into those cells
   bool tail_set = false;
-  std::vector<uint32_t> tail_payload;
-  ColumnInfo pos_info;       // the position column of the extended key cells: an Int64 that is never NULL
+  // (both point into the dimension table and are kept from set_tail on: every execution checks the table epochs before it uses
+  // them, so the device pointers are those of the staged columns, and Table::cols is a std::map, whose nodes do not move)
+  JoinPayloadCols tail_pc{};                    // the payload columns as the lookup kernel reads them …
+  std::vector<const ColumnInfo *> tail_cols;     // … and, for LazyGroups::key_cols, the columns that type the extended cells
   bool tail_applied = false; // the latest execution ran with the tail: Query::lazy holds extended key cells
   std::vector<int64_t> m_kv; // extended key cells of a sharded table's merged groups
   std::vector<uint8_t> m_kvalid;
-  // the payload columns as the lookup kernels read them and, for LazyGroups::key_cols, the columns that type the extended cells
-  int tail_columns(JoinPayloadCols *pc, std::vector<const ColumnInfo *> *cols) const {
+
+  // One walk over the payload fields: the views the lookup kernel reads and the columns of the extended cells (key, payload …, position).
+  int payload_columns(const uint32_t *fields, uint32_t n, JoinPayloadCols *pc, std::vector<const ColumnInfo *> *cols) const {
     std::memset(pc, 0, sizeof *pc);
-    pc->n = (uint32_t)tail_payload.size();
+    pc->n = n;
     cols->assign(1, &td->cols.at(dim_key_field).info);
-    for (uint32_t c = 0; c < pc->n; ++c) {
+    for (uint32_t c = 0; c < n; ++c) {
       const ColumnInfo *ci = nullptr;
-      if (int rc = key_col_of(td, tail_payload[c], &pc->col[c], &ci, true)) return rc;
+      if (int rc = key_col_of(td, fields[c], &pc->col[c], &ci, true)) return rc;
       cols->push_back(ci);
     }
     cols->push_back(&pos_info);
+    return LLKV_OK;
+  }
+
+  // The dimension cells of `n` groups whose keys `g_keys` are in ascending order: out_kv / out_kvalid = [pc.n + 1][n] — the payload
+  // cells of their dimension rows, then the rows' positions (0xFFFFFFFF: the key is not among them).  Behind a group's own key cell
+  // they are its extended key cells (key, payload …, position).  on_device: the keys are in HBM and so are out_kv / out_kvalid (the
+  // launch goes on `s`); else both are host memory, and the keys go up and the cells come back in one round trip that has ended on return.
+  int dim_cells(const JoinPayloadCols &pc, const int64_t *g_keys, uint64_t n, bool on_device, int64_t *out_kv, uint8_t *out_kvalid, hipStream_t s) const {
+    if (n == 0) return LLKV_OK;
+    const size_t cells = (size_t)(pc.n + 1) * n;
+    Scratch d_keys, d_kv, d_kvalid;
+    if (!on_device) {
+      int rc;
+      if ((rc = d_keys.alloc(n * 8)) || (rc = d_kv.alloc(cells * 8)) || (rc = d_kvalid.alloc(cells))) return rc;
+      HIP_TRY(hipMemcpyAsync(d_keys.p, g_keys, n * 8, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hj_launch_join_dim_cells(on_device ? g_keys : d_keys.as<int64_t>(), n, keys.as<uint64_t>(), rows.as<uint64_t>(), pos.as<uint32_t>(), n_dim, key_base, pc,
+                                     on_device ? out_kv : d_kv.as<int64_t>(), on_device ? out_kvalid : d_kvalid.as<uint8_t>(), s));
+    if (on_device) return LLKV_OK;
+    HIP_TRY(hipMemcpyAsync(out_kv, d_kv.p, cells * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_kvalid, d_kvalid.p, cells, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return LLKV_OK;
   }
 };
@@ -129,6 +159,7 @@ static int join_groupby_prepare(const llkv_join_side *fact, const llkv_join_side
   std::unique_ptr<JoinGroupState, void (*)(JoinGroupState *)> st(new JoinGroupState(), join_group_state_free);
   st->td = td;
   st->dim_key_field = dim->key_field;
+  st->pos_info.dtype = LLKV_DT_INT64;
   std::string err;
 
   // ---- 1. the dimension rows that qualify: filters [⋉ dim2] -------------------------------------------------------------------
@@ -200,16 +231,73 @@ static int join_groupby_prepare(const llkv_join_side *fact, const llkv_join_side
 }
 
 namespace {
-// One ORDER BY key of a result row as something comparable: NULL flag + (integer | double).
+// The caller's ORDER BY over (aggregates, payload columns, key) as an order over the extended key cells: KEY → key 0, PAYLOAD c →
+// key 1 + c, and the dimension row's position as the last, ascending term (ties: dimension row order, so every rank count agrees).
+int join_order_spec(const llkv_join_order_key *order, uint32_t n_order, uint32_t n_aggs, uint32_t n_payload, uint64_t offset, uint64_t limit, GroupOrderSpec *spec) {
+  for (uint32_t o = 0; o < n_order; ++o) {
+    const llkv_join_order_key &k = order[o];
+    if ((k.kind == LLKV_JOIN_ORDER_AGGREGATE && k.index >= n_aggs) || (k.kind == LLKV_JOIN_ORDER_PAYLOAD && k.index >= n_payload) ||
+        (k.kind != LLKV_JOIN_ORDER_AGGREGATE && k.kind != LLKV_JOIN_ORDER_PAYLOAD && k.kind != LLKV_JOIN_ORDER_KEY))
+      return set_error(LLKV_INVALID_ARGUMENT, "ORDER BY key out of range");
+    llkv_group_order_key t;
+    t.kind = k.kind == LLKV_JOIN_ORDER_AGGREGATE ? LLKV_GROUP_ORDER_AGGREGATE : LLKV_GROUP_ORDER_KEY;
+    t.index = k.kind == LLKV_JOIN_ORDER_AGGREGATE ? k.index : k.kind == LLKV_JOIN_ORDER_PAYLOAD ? 1 + k.index : 0;
+    t.descending = k.descending;
+    t.nulls_first = k.nulls_first;
+    spec->terms.push_back(t);
+  }
+  spec->terms.push_back(llkv_group_order_key{LLKV_GROUP_ORDER_KEY, 1 + n_payload, 0, 0});
+  spec->offset = offset;
+  spec->limit = limit;
+  return LLKV_OK;
+}
+
+// The rows `rows` (nullptr: every group, in place) of the groups `lz` (their key cells: column 0 of lz.key_vals) whose dimension cells
+// are kv / kvalid ([n_payload + 1][lz.n]: JoinGroupState::dim_cells).
+// A position of 0xFFFFFFFF — a group whose key is not among the qualifying dimension rows, which the key set makes impossible — is
+// refused for the delivered rows, with every_group for all of them (so that no LIMIT hides it).
+int build_join_rows(const LazyGroups &lz, const int64_t *kv, const uint8_t *kvalid, uint32_t n_payload, uint32_t n_aggs, const std::vector<uint64_t> *rows, bool every_group,
+                    JoinRows *res) {
+  const uint64_t n = lz.n, take = rows ? rows->size() : n;
+  const int64_t *pos = kv + (size_t)n_payload * n;
+  static const char *const kLost = "join → GROUP BY: a result group's key is not among the qualifying dimension rows";
+  for (uint64_t g = 0; every_group && g < n; ++g)
+    if (pos[g] == 0xFFFFFFFFll) return set_error(LLKV_INTERNAL, kLost);
+  res->keys.resize(take);
+  res->group_index.resize(take);
+  res->payload.resize((size_t)take * n_payload);
+  res->payload_null.resize((size_t)take * n_payload);
+  res->values.resize((size_t)take * n_aggs);
+  std::string err;
+  for (uint64_t r = 0; r < take; ++r) {
+    const uint64_t g = rows ? (*rows)[r] : r;
+    if (g >= n) return set_error(LLKV_INTERNAL, "join → GROUP BY: a row of the result is out of range");
+    if (pos[g] == 0xFFFFFFFFll) return set_error(LLKV_INTERNAL, kLost);
+    res->keys[r] = lz.key_vals[g];
+    res->group_index[r] = (uint64_t)pos[g];
+    for (uint32_t c = 0; c < n_payload; ++c) {
+      const bool valid = kvalid[(size_t)c * n + g] != 0;
+      res->payload[(size_t)r * n_payload + c] = valid ? kv[(size_t)c * n + g] : 0;
+      res->payload_null[(size_t)r * n_payload + c] = valid ? 0 : 1;
+    }
+    for (uint32_t a = 0; a < n_aggs; ++a)
+      if (int rc = finalize_value(lz.plan->aggs[a], lz.lanes + (size_t)g * lz.k, 2, &res->values[(size_t)r * n_aggs + a], &err, false)) return set_error(rc, err);
+  }
+  return LLKV_OK;
+}
+
+// One ORDER BY key of a result row of _rows as something comparable: NULL flag + (integer | double).  (_rows keeps its own host
+// sort: through group_order_host its LIMIT 10 over 112 470 groups measured 0.3 ms slower — profiles/join_rows/README.md.)
 struct OrderCell {
   bool null = false, is_f = false;
   __int128 i = 0;
   double f = 0;
 };
+// < 0: a comes first in ascending order
 int cmp_cells(const OrderCell &a, const OrderCell &b, bool nulls_first) {
   if (a.null || b.null) return a.null == b.null ? 0 : ((a.null == nulls_first) ? -1 : 1);
   if (a.is_f || b.is_f) {
-    // arrow's sort orders floats by totalOrder: NaN above every number (llkv-executor/src/lib.rs:13847-13864 → lexsort_to_indices)
+    // NaN above every number (llkv-executor/src/lib.rs:13847-13864 → lexsort_to_indices); ±0.0 tie
     const double x = a.is_f ? a.f : (double)a.i, y = b.is_f ? b.f : (double)b.i;
     const bool xn = x != x, yn = y != y;
     if (xn || yn) return xn == yn ? 0 : (xn ? 1 : -1);
@@ -227,6 +315,8 @@ OrderCell cell_of_value(const llkv_value &v) {
 }
 } // namespace
 
+// ORDER BY … LIMIT over the finished groups of a query without a tail.  A pure reader: nothing of the query or of its join state is
+// written, so it may be asked again with another payload, order or limit, and the query's own accessors keep answering the plain groups.
 static int join_groupby_rows(Query *q, const uint32_t *payload_fields, uint32_t n_payload, const llkv_join_order_key *order, uint32_t n_order,
                              uint64_t limit, JoinRows **out) {
   int rc = ensure_device();
@@ -240,49 +330,26 @@ static int join_groupby_rows(Query *q, const uint32_t *payload_fields, uint32_t 
   const JoinGroupState &st = *q->join_state;
   const LazyGroups &lz = q->lazy;
   const uint32_t n_aggs = q->n_user_aggs;
-  for (uint32_t o = 0; o < n_order; ++o) {
-    const llkv_join_order_key &k = order[o];
-    if ((k.kind == LLKV_JOIN_ORDER_AGGREGATE && k.index >= n_aggs) || (k.kind == LLKV_JOIN_ORDER_PAYLOAD && k.index >= n_payload) ||
-        (k.kind != LLKV_JOIN_ORDER_AGGREGATE && k.kind != LLKV_JOIN_ORDER_PAYLOAD && k.kind != LLKV_JOIN_ORDER_KEY))
-      return set_error(LLKV_INVALID_ARGUMENT, "ORDER BY key out of range");
-  }
+  GroupOrderSpec spec;
+  if ((rc = join_order_spec(order, n_order, n_aggs, n_payload, 0, limit, &spec))) return rc;
   const uint64_t n = lz.n;
   std::unique_ptr<JoinRows> res(new JoinRows());
   res->n_aggs = n_aggs;
   res->n_payload = n_payload;
   res->total_groups = n;
   if (n == 0 || limit == 0) { *out = res.release(); return LLKV_OK; }
-  hipStream_t s = g_ctx.stream;
 
-  // ---- 3a. every group's dimension row: payload cells + position among the qualifying rows -----------------------------------
+  PhaseTrace trace("[llkv join rows] %-12s %8.3f ms\n");
   JoinPayloadCols pc;
-  std::memset(&pc, 0, sizeof pc);
-  pc.n = n_payload;
-  for (uint32_t c = 0; c < n_payload; ++c)
-    if ((rc = key_col_of(st.td, payload_fields[c], &pc.col[c], nullptr, true))) return rc;
-  std::vector<int64_t> h_payload((size_t)n_payload * n);
-  std::vector<uint8_t> h_pvalid((size_t)n_payload * n);
-  std::vector<uint32_t> h_pos(n);
-  {
-    Scratch d_keys, d_payload, d_valid, d_pos;
-    if ((rc = d_keys.alloc(n * 8)) || (rc = d_payload.alloc((size_t)(n_payload ? n_payload : 1) * n * 8)) || (rc = d_valid.alloc((size_t)(n_payload ? n_payload : 1) * n)) ||
-        (rc = d_pos.alloc(n * 4)))
-      return rc;
-    HIP_TRY(hipMemcpyAsync(d_keys.p, lz.key_vals, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hj_launch_lookup_payload(st.keys.as<uint64_t>(), st.rows.as<uint64_t>(), st.pos.as<uint32_t>(), st.n_dim, d_keys.as<int64_t>(), st.key_base, n, pc,
-                                     d_payload.as<int64_t>(), d_valid.as<uint8_t>(), d_pos.as<uint32_t>(), s));
-    if (n_payload) {
-      HIP_TRY(hipMemcpyAsync(h_payload.data(), d_payload.p, (size_t)n_payload * n * 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(h_pvalid.data(), d_valid.p, (size_t)n_payload * n, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipMemcpyAsync(h_pos.data(), d_pos.p, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  for (uint64_t g = 0; g < n; ++g)
-    if (h_pos[g] == 0xFFFFFFFFu) return set_error(LLKV_INTERNAL, "join → GROUP BY: a result group's key is not among the qualifying dimension rows");
-
-  // ---- 3b. ORDER BY … LIMIT over the finalized cells (ties: dimension row order, so every rank count agrees) -----------------
-  // only the aggregates an ORDER BY key names are finalized for every group; the rest for the rows that are delivered
+  std::vector<const ColumnInfo *> cols;
+  if ((rc = st.payload_columns(payload_fields, n_payload, &pc, &cols))) return rc;
+  std::vector<int64_t> kv((size_t)(n_payload + 1) * n);
+  std::vector<uint8_t> kvalid((size_t)(n_payload + 1) * n);
+  if ((rc = st.dim_cells(pc, lz.key_vals, n, false, kv.data(), kvalid.data(), g_ctx.stream))) return rc;
+  trace.mark("lookup");
+  // ORDER BY … LIMIT over the finalized cells (ties: dimension row order, so every rank count agrees); only the aggregates an
+  // ORDER BY key names are finalized for every group, the rest for the rows that are delivered
+  const int64_t *pos = kv.data() + (size_t)n_payload * n;
   std::vector<std::vector<OrderCell>> cells(n_order);
   std::string err;
   for (uint32_t o = 0; o < n_order; ++o) {
@@ -291,7 +358,7 @@ static int join_groupby_rows(Query *q, const uint32_t *payload_fields, uint32_t 
     for (uint64_t g = 0; g < n; ++g) {
       OrderCell c;
       if (k.kind == LLKV_JOIN_ORDER_KEY) c.i = lz.key_vals[g];
-      else if (k.kind == LLKV_JOIN_ORDER_PAYLOAD) { c.null = !h_pvalid[(size_t)k.index * n + g]; c.i = h_payload[(size_t)k.index * n + g]; }
+      else if (k.kind == LLKV_JOIN_ORDER_PAYLOAD) { c.null = !kvalid[(size_t)k.index * n + g]; c.i = kv[(size_t)k.index * n + g]; }
       else {
         llkv_value v;
         if ((rc = finalize_value(lz.plan->aggs[k.index], lz.lanes + (size_t)g * lz.k, 2, &v, &err, false))) return set_error(rc, err);
@@ -302,57 +369,42 @@ static int join_groupby_rows(Query *q, const uint32_t *payload_fields, uint32_t 
   }
   auto before = [&](uint64_t a, uint64_t b) {
     for (uint32_t o = 0; o < n_order; ++o) {
-      int c = cmp_cells(cells[o][a], cells[o][b], order[o].nulls_first != 0);
-      if (c) return order[o].descending ? c > 0 : c < 0;
+      const OrderCell &x = cells[o][a], &y = cells[o][b];
+      const int c = cmp_cells(x, y, order[o].nulls_first != 0);
+      // DESC turns the values round, not the NULL placement (arrow's SortOptions, the tail and the oracle place NULLs the same way)
+      if (c) return order[o].descending && !x.null && !y.null ? c > 0 : c < 0;
     }
-    return h_pos[a] < h_pos[b];
+    return pos[a] < pos[b];
   };
-  std::vector<uint64_t> idx(n);
-  std::iota(idx.begin(), idx.end(), 0ull);
-  const uint64_t take = limit > n ? n : limit; // (UINT64_MAX: every group)
-  if (take < n) std::partial_sort(idx.begin(), idx.begin() + (long)take, idx.end(), before);
-  else std::sort(idx.begin(), idx.end(), before);
-  idx.resize(take);
-
-  res->keys.resize(take);
-  res->group_index.resize(take);
-  res->payload.resize((size_t)take * n_payload);
-  res->payload_null.resize((size_t)take * n_payload);
-  res->values.resize((size_t)take * n_aggs);
-  for (uint64_t r = 0; r < take; ++r) {
-    const uint64_t g = idx[r];
-    res->keys[r] = lz.key_vals[g];
-    res->group_index[r] = h_pos[g];
-    for (uint32_t c = 0; c < n_payload; ++c) {
-      res->payload[(size_t)r * n_payload + c] = h_payload[(size_t)c * n + g];
-      res->payload_null[(size_t)r * n_payload + c] = h_pvalid[(size_t)c * n + g] ? 0 : 1;
-    }
-    for (uint32_t a = 0; a < n_aggs; ++a)
-      if ((rc = finalize_value(lz.plan->aggs[a], lz.lanes + (size_t)g * lz.k, 2, &res->values[(size_t)r * n_aggs + a], &err, false))) return set_error(rc, err);
-  }
+  trace.mark("order cells");
+  std::vector<uint64_t> rows(n);
+  std::iota(rows.begin(), rows.end(), 0ull);
+  const uint64_t take = spec.end(n);
+  if (take < n) std::partial_sort(rows.begin(), rows.begin() + (long)take, rows.end(), before);
+  else std::sort(rows.begin(), rows.end(), before);
+  rows.resize(take);
+  trace.mark("sort");
+  if ((rc = build_join_rows(lz, kv.data(), kvalid.data(), n_payload, n_aggs, &rows, true, res.get()))) return rc;
+  trace.mark("rows");
   *out = res.release();
   return LLKV_OK;
 }
 
 // ---- the result tail: HAVING, ORDER BY / OFFSET / LIMIT before the groups leave the device --------------------------------------
-// The groups of the sort-based run stay in HBM in ascending key order; join_dim_cells (join_tail.hip) merges them with the sorted
-// dimension rows into key cells 1 … n_payload (payload) and n_payload + 1 (position), and the tail of every GROUP BY —
-// having_device, group_order_device, or the copy-out and Query::apply_order on the host — runs over the extended cells: a payload
-// column is a key column, the position the last ascending order term.
+// The groups of the sort-based run stay in HBM in ascending key order; dim_cells makes them key cells 1 … n_payload (payload)
+// and n_payload + 1 (position), and the tail of every GROUP BY — having_device, group_order_device, or the copy-out and
+// Query::apply_order on the host — runs over the extended cells: a payload column is a key column, the position the last ascending
+// order term.
 static int join_tail_extend_device(const JoinGroupState *st, LazyGroups *out, const int64_t *d_kv, const uint8_t *d_kvalid, uint64_t n, hipStream_t s, Scratch *x_kv,
                                    Scratch *x_kvalid) {
-  JoinPayloadCols pc;
-  std::vector<const ColumnInfo *> cols;
-  int rc = st->tail_columns(&pc, &cols);
-  if (rc) return rc;
-  const size_t nk = cols.size(); // key, payload …, position
+  const size_t nk = st->tail_cols.size(); // key, payload …, position
+  int rc;
   if ((rc = x_kv->alloc(n * nk * 8)) || (rc = x_kvalid->alloc(n * nk))) return rc;
   HIP_TRY(hipMemcpyAsync(x_kv->p, d_kv, n * 8, hipMemcpyDeviceToDevice, s));
   HIP_TRY(hipMemcpyAsync(x_kvalid->p, d_kvalid, n, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hj_launch_join_dim_cells(d_kv, n, st->keys.as<uint64_t>(), st->rows.as<uint64_t>(), st->pos.as<uint32_t>(), st->n_dim, st->key_base, pc,
-                                   x_kv->as<int64_t>() + n, x_kvalid->as<uint8_t>() + n, s));
+  if ((rc = st->dim_cells(st->tail_pc, d_kv, n, true, x_kv->as<int64_t>() + n, x_kvalid->as<uint8_t>() + n, s))) return rc;
   out->n_keys = (uint32_t)nk;
-  out->key_cols = cols;
+  out->key_cols = st->tail_cols;
   return LLKV_OK;
 }
 
@@ -367,35 +419,19 @@ int join_tail_extend_merged(Query *q) {
   int rc = ensure_device();
   if (rc || (rc = q->epochs.check())) return rc;
   LazyGroups &lz = q->lazy;
-  JoinPayloadCols pc;
-  std::vector<const ColumnInfo *> cols;
-  if ((rc = st.tail_columns(&pc, &cols))) return rc;
   const uint64_t n = lz.n;
-  const size_t nk = cols.size(), P = pc.n;
+  const size_t nk = st.tail_cols.size();
   st.m_kv.assign(n * nk, 0);
   st.m_kvalid.assign(n * nk, 1);
   if (n) {
-    hipStream_t s = g_ctx.stream;
-    std::vector<uint32_t> h_pos(n);
-    Scratch d_keys, d_payload, d_valid, d_pos;
-    if ((rc = d_keys.alloc(n * 8)) || (rc = d_payload.alloc((P ? P : 1) * n * 8)) || (rc = d_valid.alloc((P ? P : 1) * n)) || (rc = d_pos.alloc(n * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_keys.p, lz.key_vals, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hj_launch_lookup_payload(st.keys.as<uint64_t>(), st.rows.as<uint64_t>(), st.pos.as<uint32_t>(), st.n_dim, d_keys.as<int64_t>(), st.key_base, n, pc,
-                                     d_payload.as<int64_t>(), d_valid.as<uint8_t>(), d_pos.as<uint32_t>(), s));
-    if (P) {
-      HIP_TRY(hipMemcpyAsync(st.m_kv.data() + n, d_payload.p, P * n * 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(st.m_kvalid.data() + n, d_valid.p, P * n, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipMemcpyAsync(h_pos.data(), d_pos.p, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
     std::memcpy(st.m_kv.data(), lz.key_vals, n * 8);
     std::memcpy(st.m_kvalid.data(), lz.key_valid, n);
-    for (uint64_t g = 0; g < n; ++g) st.m_kv[(P + 1) * n + g] = (int64_t)h_pos[g];
+    if ((rc = st.dim_cells(st.tail_pc, lz.key_vals, n, false, st.m_kv.data() + n, st.m_kvalid.data() + n, g_ctx.stream))) return rc;
   }
   lz.key_vals = st.m_kv.data();
   lz.key_valid = st.m_kvalid.data();
   lz.n_keys = (uint32_t)nk;
-  lz.key_cols = cols;
+  lz.key_cols = st.tail_cols;
   st.tail_applied = true;
   return LLKV_OK;
 }
@@ -408,7 +444,7 @@ static int join_groupby_set_tail(Query *q, const uint32_t *payload_fields, uint3
   if (!n_payload && !n_having && !n_order && offset == 0 && limit == UINT64_MAX) { // clear: the next launch leaves plain groups again
     if (st.tail_applied) { q->lazy.active = false; q->row_mapped = false; q->row_map.clear(); q->order_note.clear(); } // (its groups were filtered or cut)
     st.tail_set = st.tail_applied = false;
-    st.tail_payload.clear();
+    st.tail_cols.clear();
     q->order = GroupOrderSpec();
     q->having.assign(nullptr, 0);
     sorted_groupby_set_key_extender(q->sorted, GroupKeyExtender());
@@ -416,41 +452,22 @@ static int join_groupby_set_tail(Query *q, const uint32_t *payload_fields, uint3
   }
   if (n_payload > 4) return set_error(LLKV_UNSUPPORTED, "more than 4 payload columns");
   const uint32_t n_aggs = q->n_user_aggs;
-  std::vector<int32_t> key_dtypes(1, st.td->cols.at(st.dim_key_field).info.dtype);
-  for (uint32_t c = 0; c < n_payload; ++c) {
-    JoinKeyColumn view;
-    const ColumnInfo *ci = nullptr;
-    if (int rc = key_col_of(st.td, payload_fields[c], &view, &ci, true)) return rc;
-    key_dtypes.push_back(ci->dtype);
-  }
+  JoinPayloadCols pc;
+  std::vector<const ColumnInfo *> cols;
+  if (int rc = st.payload_columns(payload_fields, n_payload, &pc, &cols)) return rc;
   GroupOrderSpec spec;
-  for (uint32_t o = 0; o < n_order; ++o) {
-    const llkv_join_order_key &k = order[o];
-    if ((k.kind == LLKV_JOIN_ORDER_AGGREGATE && k.index >= n_aggs) || (k.kind == LLKV_JOIN_ORDER_PAYLOAD && k.index >= n_payload) ||
-        (k.kind != LLKV_JOIN_ORDER_AGGREGATE && k.kind != LLKV_JOIN_ORDER_PAYLOAD && k.kind != LLKV_JOIN_ORDER_KEY))
-      return set_error(LLKV_INVALID_ARGUMENT, "ORDER BY key out of range");
-    llkv_group_order_key t;
-    t.kind = k.kind == LLKV_JOIN_ORDER_AGGREGATE ? LLKV_GROUP_ORDER_AGGREGATE : LLKV_GROUP_ORDER_KEY;
-    t.index = k.kind == LLKV_JOIN_ORDER_AGGREGATE ? k.index : k.kind == LLKV_JOIN_ORDER_PAYLOAD ? 1 + k.index : 0;
-    t.descending = k.descending;
-    t.nulls_first = k.nulls_first;
-    spec.terms.push_back(t);
-  }
-  spec.terms.push_back(llkv_group_order_key{LLKV_GROUP_ORDER_KEY, 1 + n_payload, 0, 0}); // ties: the dimension row's position
-  spec.offset = offset;
-  spec.limit = limit;
+  if (int rc = join_order_spec(order, n_order, n_aggs, n_payload, offset, limit, &spec)) return rc;
   if (n_having) {
     std::string err;
     if (int rc = having_validate(having, n_having, exprs, n_exprs, 1 + n_payload, n_aggs, &err)) return set_error(rc, err);
-    if (int rc = having_expr_leaves_numeric(having, n_having, exprs, n_exprs, 1 + n_payload, [&](uint32_t k) { return key_dtypes[k]; }, *sorted_groupby_plan(q->sorted), n_aggs, &err))
+    if (int rc = having_expr_leaves_numeric(having, n_having, exprs, n_exprs, 1 + n_payload, [&](uint32_t k) { return cols[k]->dtype; }, *sorted_groupby_plan(q->sorted), n_aggs, &err))
       return set_error(rc, err);
   }
   if (st.tail_applied) { q->lazy.active = false; q->row_mapped = false; q->row_map.clear(); q->order_note.clear(); } // (rows of another tail)
   st.tail_applied = false;
   st.tail_set = true;
-  st.tail_payload.assign(payload_fields, payload_fields + n_payload);
-  st.pos_info = ColumnInfo();
-  st.pos_info.dtype = LLKV_DT_INT64;
+  st.tail_pc = pc;
+  st.tail_cols = cols;
   q->order = spec;
   q->having.assign(having, n_having, exprs, n_exprs);
   const JoinGroupState *stp = &st;
@@ -468,34 +485,15 @@ static int join_groupby_tail_rows(Query *q, JoinRows **out) {
   if (!q->lazy.active || !st.tail_applied || q->n_launched != q->n_collected)
     return set_error(LLKV_INVALID_ARGUMENT, "the query has not finished an execution with this tail yet");
   const LazyGroups &lz = q->lazy;
-  const uint32_t n_aggs = q->n_user_aggs, n_payload = (uint32_t)st.tail_payload.size();
+  const uint32_t n_payload = st.tail_pc.n;
   std::unique_ptr<JoinRows> res(new JoinRows());
-  res->n_aggs = n_aggs;
+  res->n_aggs = q->n_user_aggs;
   res->n_payload = n_payload;
   res->total_groups = q->total_groups;
-  const uint64_t n = lz.n, take = q->row_mapped ? q->row_map.size() : n;
+  const uint64_t take = q->row_mapped ? q->row_map.size() : lz.n;
   if (take && lz.n_keys != n_payload + 2) return set_error(LLKV_INTERNAL, "join → GROUP BY: the groups carry no dimension cells");
-  res->keys.resize(take);
-  res->group_index.resize(take);
-  res->payload.resize((size_t)take * n_payload);
-  res->payload_null.resize((size_t)take * n_payload);
-  res->values.resize((size_t)take * n_aggs);
-  std::string err;
-  for (uint64_t r = 0; r < take; ++r) {
-    const uint64_t g = q->row_mapped ? q->row_map[r] : r;
-    if (g >= n) return set_error(LLKV_INTERNAL, "join → GROUP BY: a row of the tail is out of range");
-    const int64_t pos = lz.key_vals[(size_t)(n_payload + 1) * n + g];
-    if (pos == 0xFFFFFFFFll) return set_error(LLKV_INTERNAL, "join → GROUP BY: a result group's key is not among the qualifying dimension rows");
-    res->keys[r] = lz.key_vals[g];
-    res->group_index[r] = (uint64_t)pos;
-    for (uint32_t c = 0; c < n_payload; ++c) {
-      const bool valid = lz.key_valid[(size_t)(1 + c) * n + g] != 0;
-      res->payload[(size_t)r * n_payload + c] = valid ? lz.key_vals[(size_t)(1 + c) * n + g] : 0;
-      res->payload_null[(size_t)r * n_payload + c] = valid ? 0 : 1;
-    }
-    for (uint32_t a = 0; a < n_aggs; ++a)
-      if (int rc = finalize_value(lz.plan->aggs[a], lz.lanes + (size_t)g * lz.k, 2, &res->values[(size_t)r * n_aggs + a], &err, false)) return set_error(rc, err);
-  }
+  if (take)
+    if (int rc = build_join_rows(lz, lz.key_vals + lz.n, lz.key_valid + lz.n, n_payload, res->n_aggs, q->row_mapped ? &q->row_map : nullptr, false, res.get())) return rc;
   *out = res.release();
   return LLKV_OK;
 }

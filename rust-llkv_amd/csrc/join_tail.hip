@@ -1,5 +1,6 @@
-// join_tail.hip — the dimension cells of the groups a join → GROUP BY left in HBM (join_group.cpp: the result tail of
-// llkv_hip_join_groupby_set_tail).  The sort-based GROUP BY writes its groups in ascending key order ([1][n] key cells), and the
+// join_tail.hip — the dimension cells of the groups of a join → GROUP BY (join_group.cpp: dim_cells, the one lookup of every
+// delivery — the groups the result tail keeps in HBM, and the keys _rows and a sharded table's merge copy up).  The groups are in
+// ascending key order ([1][n] key cells: the sort-based GROUP BY writes them so, the sharded merge sorts them), and the
 // qualifying dimension rows are kept sorted by key image (JoinGroupState::keys / rows / pos), so the lookup is a merge of two
 // sorted lists, not n independent searches over the whole dimension:
 //   bounds    threads 0 and 1 of a workgroup bisect the workgroup's first and last group key in the dimension keys: its stretch of

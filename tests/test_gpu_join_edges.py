@@ -382,7 +382,7 @@ def test_the_tail_kernel_at_its_slice_and_group_boundaries(rt, orc, staged):
     all qualifying; the 769 groups give the four workgroups of one launch stretches of exactly 2048 keys (the slice full, first key
     = image 0), 2049 (one too many: resolved in global memory), 2047, and one single group whose key is the LAST dimension key
     (bound[1] = at + 1 == n_dim).  Fact filters then keep exactly 256 groups (one full workgroup), 257 (a second workgroup of one
-    group) and one."""
+    group) and one.  Every case is read through result() (no tail) and through the tail."""
     G = boundary_keys()
     r = np.arange(N_DIM3, dtype=np.int64)
     # -- the stretches, from numpy alone: the dimension keys are contiguous, so a key's index among the sorted keys is key − K0
@@ -411,6 +411,8 @@ def test_the_tail_kernel_at_its_slice_and_group_boundaries(rt, orc, staged):
             assert w[3] == j and w[1] == [None if j % 13 == 0 else j * 3 - 7000, j - 3000] and w[2][0].value == 8
         assert sum(1 for w in rows if w[1][0] is None) == sum(1 for k in (G[:groups] if groups > 1 else G[-1:]) if row_of_key[int(k)] % 13 == 0)
         ctx = f"{staged}, {name}"
+        star.launch_plain()  # the plain result runs the same kernel over the copied-out keys
+        assert len(star.check_result([(KEY, 0)], None, ctx)) == groups
         got, note = star.check_tail(None, [(KEY, 0)], 0, None, ctx)
         assert len(got) == groups
         got, note = star.check_tail(None, [(KEY, 0)], 0, 1024, ctx, device_order=True)

@@ -384,3 +384,37 @@ def test_without_a_having_the_tail_equals_result(rt, abi, star):
         for g, w in zip(got, want):
             assert (g.key, g.payload, g.group_index, g.values) == (w.key, w.payload, w.group_index, w.values), (order, note, g, w)
     plain.close()
+
+
+def test_result_and_tail_rows_name_the_same_rows(abi, star):
+    """Both deliveries order with one comparator over one lookup: under an aggregate term with heavy ties and a payload term with
+    NULL cells, for every (descending, nulls_first), result(payload, order) and set_tail(payload, order=order) + tail_rows() are
+    the same rows — group_index included — and both are the oracle's; once more cut at 7.  Then, the tail cleared, result() with two
+    orders and the first again on one finished execution: it reads the groups and leaves them as they were."""
+    jq = star["jq"]
+    cells = lambda rows: [(g.key, g.payload, g.group_index, g.values) for g in rows]
+
+    def plain_result(payload, order, limit):
+        jq.set_tail()
+        jq.launch()
+        jq.finish_only()
+        return jq.result(payload, order, limit)
+    orders = [[(AGG, 1, d, nf), (PAY, 0, d, nf)] for d in (False, True) for nf in (False, True)]
+    for order in orders:
+        want, want_total = plain_result(PAYLOAD, order, None)
+        got, total, note = run_tail(jq, None, order, 0, None)
+        assert total == want_total == 2000 and cells(got) == cells(want), (order, note)
+        same_rows(want, star["ordered"](order), f"result order={order}")
+    want7, _ = plain_result(PAYLOAD, orders[1], 7)
+    got7, total7, note = run_tail(jq, None, orders[1], 0, 7)
+    assert total7 == 2000 and len(got7) == 7 and cells(got7) == cells(want7) and note.endswith("; order: device top-k"), note
+    same_rows(want7, star["ordered"](orders[1])[:7], "limit 7")
+    first, _ = plain_result(PAYLOAD, orders[0], None)
+    other, other_total = jq.result([D_PAY1], [(PAY, 0, True), (KEY, 0)], 50)
+    again, _ = jq.result(PAYLOAD, orders[0], None)
+    same_rows(first, star["ordered"](orders[0]), "first")
+    assert cells(again) == cells(first) and other_total == 2000
+    by_date = sorted(star["ordered"]([]), key=lambda w: (-w[1][1], w[0]))[:50]
+    assert [(g.key, g.payload, g.group_index) for g in other] == [(w[0], w[1][1:], w[3]) for w in by_date]
+    own = jq.rows()  # the query's own accessors still answer the plain groups: one key cell each, ascending
+    assert [[k.value for k in r.keys] for r in own] == [[k] for k in sorted(w[0] for w in star["ordered"]([]))] and jq.total_groups == 2000
