@@ -184,7 +184,7 @@ static int finish_sharded(Query *q, hipStream_t stream) {
   if (q->sorted) {
     // every rank reduced its own chunks: partial groups → all ranks → merge in rank order (= row order)
     if ((rc = q->finish(stream))) return rc;
-    const LazyGroups &lz = q->lazy;
+    const LazyGroups &lz = q->result.view;
     if (!lz.active) return set_error(LLKV_INVALID_ARGUMENT, "launch the query first");
     const uint64_t n = lz.n, nk = lz.n_keys, k = (uint64_t)lz.k;
     // [n, n_keys, k][key values i64 nk·n][lanes u64 n·k][key validity u8 nk·n, padded to 8]
@@ -215,7 +215,7 @@ static int finish_sharded(Query *q, hipStream_t stream) {
       ln[r] = reinterpret_cast<const uint64_t *>(b + 24 + nk * h[0] * 8);
       kva[r] = b + 24 + nk * h[0] * 8 + h[0] * k * 8;
     }
-    if ((rc = sorted_groupby_merge(q->sorted, world, counts.data(), kv.data(), kva.data(), ln.data(), &q->lazy))) return rc;
+    if ((rc = sorted_groupby_merge(q->sorted, world, counts.data(), kv.data(), kva.data(), ln.data(), &q->result.view))) return rc;
     return q->apply_merged_order();
   }
   while (q->n_submitted < q->n_launched) {

@@ -337,13 +337,12 @@ int Query::launch(hipStream_t stream) {
   if (sorted) { // the sort-based route runs to completion here; submit / collect only hand the result over
     if (n_launched != n_collected) return set_error(LLKV_INVALID_ARGUMENT, "a sort-based GROUP BY keeps one execution in flight");
     // (a sharded table orders the merged groups: llkv_hip_query_merge_groups / finish_sharded)
-    const bool local_order = order.active() && table->world == 1, local_having = having.active() && table->world == 1;
-    row_mapped = false;
-    row_map.clear();
+    const GroupOrderSpec *run_order = order.active() && table->world == 1 ? &order : nullptr;
+    const HavingProgram *run_having = having.active() && table->world == 1 ? &having : nullptr;
+    result.reset();
     GroupOrderDone done;
-    int rc = sorted_groupby_run(sorted, &lazy, local_order ? &order : nullptr, &done, local_having ? &having : nullptr);
-    if (!rc && (local_order || local_having)) rc = apply_order(&done);
-    else if (!rc) { row_mapped = false; row_map.clear(); order_note.clear(); total_groups = lazy.n; }
+    int rc = sorted_groupby_run(sorted, &result.view, run_order, &done, run_having);
+    if (!rc) rc = result.apply(run_having, run_order, &done);
     if (rc) return rc;
     if (join_state) join_tail_after_launch(this);
     n_launched++;
@@ -824,7 +823,7 @@ int Query::distinct_partial(size_t agg, const uint64_t **values, uint64_t *n) {
 // seen; i64 sums checked, f64 sums 0.0 then += in that order).
 int Query::merge_distinct(size_t agg, uint32_t world, const uint64_t *counts, const uint64_t *const *values) {
   if (agg >= distinct.size() || distinct[agg].kind < 0) return set_error(LLKV_INVALID_ARGUMENT, "not a DISTINCT aggregate");
-  if (groups.empty() || agg >= groups.n_values) return set_error(LLKV_INVALID_ARGUMENT, "finish the query before merging");
+  if (sorted || result.unordered_rows() == 0 || agg >= result.dense_values.size()) return set_error(LLKV_INVALID_ARGUMENT, "finish the query before merging");
   const DistinctAgg &da = distinct[agg];
   std::unordered_set<uint64_t> seen;
   std::vector<uint64_t> all;
@@ -866,7 +865,7 @@ int Query::merge_distinct(size_t agg, uint32_t world, const uint64_t *counts, co
   }
   default: return set_error(LLKV_INTERNAL, "not a DISTINCT aggregate");
   }
-  groups.value(0, agg) = out;
+  result.dense_values[agg] = out; // (the one row of an ungrouped query)
   return LLKV_OK;
 }
 
@@ -882,9 +881,7 @@ int Query::finish_from_exchange(const uint64_t *exchange) {
     std::memcpy(state.data(), exchange + (size_t)__builtin_ctz(table->owned_mask | 0x100u) * p.lanes, (size_t)p.lanes * 8);
   else fold_exchange_host(exchange, p.lane_ops.data(), (uint32_t)p.lanes, state.data());
   mark("fold");
-  groups.reset(0, 0, 0);
-  row_mapped = false;
-  row_map.clear();
+  result.reset();
   if (state[(size_t)p.ng * p.k] != 0) // checked arithmetic failed on a selected row
     return set_error(LLKV_INTERNAL, arith_error_message(state[(size_t)p.ng * p.k]));
   const int base = p.track_first ? 2 : 1;
@@ -920,32 +917,25 @@ int Query::finish_from_exchange(const uint64_t *exchange) {
   auto before = [](const Ref &x, const Ref &y) { return x.order < y.order; };
   if (p.grouped && !std::is_sorted(present.begin(), present.end(), before)) std::stable_sort(present.begin(), present.end(), before); // (integer keys: already in order)
   mark("order");
-  groups.reset(present.size(), p.grouped ? p.key_fields.size() : 0, p.aggs.size());
-  std::vector<const std::vector<std::string> *> dicts(p.key_fields.size(), nullptr);
-  for (size_t k = 0; p.grouped && k < p.key_fields.size(); ++k)
-    if (!p.key_is_int[k]) dicts[k] = &table->cols.at(p.key_fields[k]).info.dictionary;
+  // The cells every route leaves (LazyGroups): per key a raw cell — the integer, or the dictionary code of a Utf8 key (the dense
+  // routes admit Int64 / Int32 / Date32 keys, key_is_int, and Utf8: what ColumnInfo::dtype decodes the same way) — and its validity.
+  const size_t n = present.size(), n_keys = p.grouped ? p.key_fields.size() : 0, n_aggs = p.aggs.size();
+  std::vector<const ColumnInfo *> key_cols;
+  for (size_t k = 0; k < n_keys; ++k) key_cols.push_back(&table->cols.at(p.key_fields[k]).info);
+  result.dense_kv.resize(n_keys * n);
+  result.dense_kvalid.resize(n_keys * n);
+  result.dense_values.assign(n * n_aggs, llkv_value{});
   std::string err;
-  for (const Ref &ref : present) {
-    const uint32_t g = ref.g;
+  for (size_t at = 0; at < n; ++at) {
+    const uint32_t g = present[at].g;
     const uint64_t *gl = &state[(size_t)g * p.k];
-    const size_t at = groups.n++;
-    if (p.grouped)
-      for (size_t k = 0; k < p.key_fields.size(); ++k) {
-        const uint32_t code = (g / p.key_strides[k]) % p.key_cards[k];
-        groups.keys.emplace_back();
-        GroupKey &gk = groups.keys.back();
-        if (p.key_nullable[k] && code == p.key_cards[k] - 1) {
-          gk.is_null = true;
-          gk.is_int = p.key_is_int[k] != 0;
-        } else if (p.key_is_int[k]) {
-          gk.is_int = true;
-          gk.i = p.key_bases[k] + (int64_t)code;
-        } else if (code < dicts[k]->size()) {
-          gk.s = (*dicts[k])[code];
-        }
-      }
-    for (size_t a = 0; a < p.aggs.size(); ++a) {
-      llkv_value *out = &groups.value(at, a);
+    for (size_t k = 0; k < n_keys; ++k) {
+      const uint32_t code = (g / p.key_strides[k]) % p.key_cards[k];
+      result.dense_kv[k * n + at] = p.key_bases[k] + (int64_t)code; // (a Utf8 key's base is 0)
+      result.dense_kvalid[k * n + at] = !(p.key_nullable[k] && code == p.key_cards[k] - 1);
+    }
+    for (size_t a = 0; a < n_aggs; ++a) {
+      llkv_value *out = &result.dense_values[at * n_aggs + a];
       int rc = finalize_value(p.aggs[a], gl, base, out, &err, false);
       if (rc == LLKV_UNSUPPORTED && !p.grouped && a < exact_plans.size() && !exact_plans[a].type_string.empty()) {
         // the order-free state cannot tell whether a PREFIX of the reference's checked_add chain overflows:
@@ -959,73 +949,11 @@ int Query::finish_from_exchange(const uint64_t *exchange) {
     }
     if (!p.grouped)
       for (size_t a = 0; a < distinct.size() && a < p.aggs.size(); ++a)
-        if (distinct[a].kind >= 0 && table->world == 1) { int rc = distinct_value(a, &groups.value(at, a)); if (rc) return rc; } // sharded: merge_distinct
+        if (distinct[a].kind >= 0 && table->world == 1) { int rc = distinct_value(a, &result.dense_values[at * n_aggs + a]); if (rc) return rc; } // sharded: merge_distinct
   }
+  result.set_dense(p, n, std::move(key_cols));
   mark("groups");
-  return apply_order(nullptr);
-}
-
-// The HAVING of llkv_hip_query_set_having, then the order of llkv_hip_query_set_group_order, over the result of the latest finish.
-// A sort-based / partitioned run may have done either on the device: `done->having_device` — the result holds the survivors only —
-// and `done->device` — the top-k left only the returned rows.  Otherwise the groups are filtered (having_eval over the finalized
-// cells) and sorted here and read through row_map.  done = nullptr: a dense route.
-int Query::apply_order(const GroupOrderDone *done) {
-  row_mapped = false;
-  row_map.clear();
-  order_note.clear();
-  total_groups = result_rows();
-  if (!plan_grouped()) return LLKV_OK;
-  bool filtered = false; // row_map = the surviving rows of the result, in their unordered position
-  if (having.active()) {
-    if (done && done->having_device) {
-      total_groups = done->total;
-      order_note = "; having: device";
-    } else {
-      // errors come before the filter: every group's fallible aggregates are finalized first (a dense route has finalized them all;
-      // the copied-out groups of a sort-based run too, the merged groups of a sharded table not yet)
-      std::string err;
-      llkv_value v;
-      if (lazy.active)
-        for (size_t a = 0; a < lazy.plan->aggs.size(); ++a) {
-          if (lazy.plan->aggs[a].fin != AggFinal::SumI64 && lazy.plan->aggs[a].fin != AggFinal::AvgI64) continue;
-          for (uint64_t g = 0; g < lazy.n; ++g)
-            if (int rc = finalize_value(lazy.plan->aggs[a], lazy.lanes + g * (size_t)lazy.k, 2, &v, &err, false)) return set_error(rc, err);
-        }
-      const uint64_t n = result_rows();
-      for (uint64_t r = 0; r < n; ++r) {
-        int32_t truth = 0;
-        const int rc = having_eval(having.nodes.data(), (uint32_t)having.nodes.size(), having.exprs.data(), (uint32_t)having.exprs.size(), [&](const llkv_having_operand &o, llkv_value *cell, int32_t *key_dtype) {
-          if (o.kind != LLKV_HAVING_OPERAND_KEY) return cell_value(r, o.index, cell);
-          *key_dtype = key_dtype_of(o.index);
-          return cell_key(r, o.index, cell);
-        }, &truth);
-        if (rc) { row_map.clear(); return rc; }
-        if (truth == 1) row_map.push_back(r);
-      }
-      filtered = true;
-      row_mapped = true;
-      total_groups = row_map.size();
-      order_note = "; having: host (" + (!done ? std::string("dense route") : done->having_why_host.empty() ? std::string("no groups") : done->having_why_host) + ")";
-    }
-  }
-  if (!order.active()) return LLKV_OK;
-  if (done && done->device) {
-    total_groups = done->total;
-    order_note += "; order: device top-k";
-    return LLKV_OK;
-  }
-  std::vector<uint64_t> ordered;
-  const int rc = group_order_host(order, total_groups, [&](uint64_t r, const llkv_group_order_key &t, llkv_value *v) {
-    const uint64_t row = filtered ? row_map[r] : r;
-    return t.kind == LLKV_GROUP_ORDER_KEY ? cell_key(row, t.index, v) : cell_value(row, t.index, v);
-  }, &ordered);
-  if (rc) { row_map.clear(); row_mapped = false; return rc; }
-  if (filtered)
-    for (uint64_t &r : ordered) r = row_map[r];
-  row_map.swap(ordered);
-  row_mapped = true;
-  order_note += "; order: host (" + (!done ? std::string("dense route") : done->why_host.empty() ? std::string("no groups") : done->why_host) + ")";
-  return LLKV_OK;
+  return result.apply(&having, &order, nullptr);
 }
 
 int Query::apply_merged_order() {
@@ -1033,56 +961,7 @@ int Query::apply_merged_order() {
     if (int rc = join_tail_extend_merged(this)) return rc;
   GroupOrderDone d;
   d.why_host = d.having_why_host = "merged groups";
-  return apply_order(&d);
-}
-
-// The dtype of key column `key` (what types a key cell under HAVING: cell_key hands Date32 / Boolean cells over as LLKV_DT_INT64).
-int32_t Query::key_dtype_of(uint32_t key) const {
-  if (lazy.active) return key < lazy.key_cols.size() ? lazy.key_cols[key]->dtype : (int32_t)LLKV_DT_INT64;
-  const std::vector<uint32_t> &fields = sorted ? sorted_groupby_key_fields(sorted) : plan.key_fields; // (before the first finish)
-  if (key >= fields.size()) return LLKV_DT_INT64;
-  auto it = table->cols.find(fields[key]);
-  return it == table->cols.end() ? (int32_t)LLKV_DT_INT64 : it->second.info.dtype;
-}
-
-// One cell of the result before the order (row = its position in the unordered output).
-int Query::cell_key(uint64_t group, uint32_t key, llkv_value *out) const {
-  if (lazy.active) { // sort-based route: decode the cell on request
-    const LazyGroups &lz = lazy;
-    if (group >= lz.n || key >= lz.n_keys) return set_error(LLKV_INVALID_ARGUMENT, "group/key index out of range");
-    std::memset(out, 0, sizeof *out);
-    const ColumnInfo *ci = lz.key_cols[key];
-    const int64_t v = lz.key_vals[(size_t)key * lz.n + group];
-    out->is_null = lz.key_valid[(size_t)key * lz.n + group] ? 0 : 1;
-    if (ci->dtype == LLKV_DT_UTF8) {
-      out->dtype = LLKV_DT_UTF8;
-      out->str = (!out->is_null && (uint64_t)v < ci->dictionary.size()) ? ci->dictionary[(size_t)v].c_str() : "";
-    } else {
-      out->dtype = LLKV_DT_INT64;
-      out->i64 = out->is_null ? 0 : v;
-    }
-    return LLKV_OK;
-  }
-  if (group >= groups.size() || key >= groups.n_keys) return set_error(LLKV_INVALID_ARGUMENT, "group/key index out of range");
-  std::memset(out, 0, sizeof *out);
-  const GroupKey &gk = groups.key(group, key);
-  if (gk.is_int) { out->dtype = LLKV_DT_INT64; out->i64 = gk.i; }
-  else { out->dtype = LLKV_DT_UTF8; out->str = gk.s.c_str(); }
-  out->is_null = gk.is_null ? 1 : 0;
-  return LLKV_OK;
-}
-
-int Query::cell_value(uint64_t group, uint32_t agg, llkv_value *out) const {
-  if (lazy.active) {
-    const LazyGroups &lz = lazy;
-    if (group >= lz.n || agg >= lz.plan->aggs.size()) return set_error(LLKV_INVALID_ARGUMENT, "group/aggregate index out of range");
-    std::string err;
-    const int rc = finalize_value(lz.plan->aggs[agg], lz.lanes + (size_t)group * lz.k, 2, out, &err, false);
-    return rc ? set_error(rc, err) : LLKV_OK;
-  }
-  if (group >= groups.size() || agg >= groups.n_values) return set_error(LLKV_INVALID_ARGUMENT, "group/aggregate index out of range");
-  *out = groups.value(group, agg);
-  return LLKV_OK;
+  return result.apply(&having, &order, &d);
 }
 
 // Make `stream` wait until the exchange image of the OLDEST not-yet-submitted execution is complete (for a
@@ -1296,27 +1175,20 @@ llkv_status llkv_hip_query_collect(llkv_hip_query *query) {
   return (llkv_status) reinterpret_cast<Query *>(query)->collect();
 }
 
-uint32_t llkv_hip_query_num_groups(const llkv_hip_query *query) {
-  if (!query) return 0;
-  const Query *q = reinterpret_cast<const Query *>(query);
-  if (q->row_mapped) return (uint32_t)q->row_map.size();
-  return q->lazy.active ? (uint32_t)q->lazy.n : (uint32_t)q->groups.size();
-}
+uint32_t llkv_hip_query_num_groups(const llkv_hip_query *query) { return query ? (uint32_t) reinterpret_cast<const Query *>(query)->result.rows() : 0; }
 uint32_t llkv_hip_query_num_keys(const llkv_hip_query *query) { return query ? (uint32_t) reinterpret_cast<const Query *>(query)->n_user_keys : 0; }
 uint32_t llkv_hip_query_num_aggregates(const llkv_hip_query *query) { return query ? reinterpret_cast<const Query *>(query)->n_user_aggs : 0; }
 
 llkv_status llkv_hip_query_group_key(const llkv_hip_query *query, uint32_t group, uint32_t key, llkv_value *out) {
   const Query *q = reinterpret_cast<const Query *>(query);
   if (!q || !out) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/key index out of range");
-  if (q->row_mapped && group >= q->row_map.size()) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/key index out of range");
-  return (llkv_status)q->cell_key(q->row_mapped ? q->row_map[group] : group, key, out);
+  return (llkv_status)q->result.cell_key(group, key, out);
 }
 
 llkv_status llkv_hip_query_value(const llkv_hip_query *query, uint32_t group, uint32_t agg, llkv_value *out) {
   const Query *q = reinterpret_cast<const Query *>(query);
   if (!q || !out) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/aggregate index out of range");
-  if (q->row_mapped && group >= q->row_map.size()) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "group/aggregate index out of range");
-  return (llkv_status)q->cell_value(q->row_mapped ? q->row_map[group] : group, agg, out);
+  return (llkv_status)q->result.cell_value(group, agg, out);
 }
 
 llkv_status llkv_hip_query_set_group_order(llkv_hip_query *query, const llkv_group_order_key *order, uint32_t n_order, uint64_t offset, uint64_t limit) {
@@ -1392,7 +1264,12 @@ llkv_status llkv_hip_query_set_having_ex(llkv_hip_query *query, const llkv_havin
   if (n_nodes) {
     std::string err;
     if (int rc = having_validate(nodes, n_nodes, exprs, n_exprs, q->n_user_keys, q->n_user_aggs, &err)) return (llkv_status)set_error(rc, err);
-    if (int rc = having_expr_leaves_numeric(nodes, n_nodes, exprs, n_exprs, q->n_user_keys, [q](uint32_t k) { return q->key_dtype_of(k); },
+    const std::vector<uint32_t> &fields = q->sorted ? sorted_groupby_key_fields(q->sorted) : q->plan.key_fields;
+    auto key_dtype = [&](uint32_t k) { // (of the table's column: there may be no result yet)
+      auto it = k < fields.size() ? q->table->cols.find(fields[k]) : q->table->cols.end();
+      return it == q->table->cols.end() ? (int32_t)LLKV_DT_INT64 : it->second.info.dtype;
+    };
+    if (int rc = having_expr_leaves_numeric(nodes, n_nodes, exprs, n_exprs, q->n_user_keys, key_dtype,
                                             q->sorted ? *sorted_groupby_plan(q->sorted) : q->plan, q->n_user_aggs, &err))
       return (llkv_status)set_error(rc, err);
   }
@@ -1406,32 +1283,33 @@ llkv_status llkv_hip_query_set_having(llkv_hip_query *query, const llkv_having_n
 
 uint64_t llkv_hip_query_total_groups(const llkv_hip_query *query) {
   const Query *q = reinterpret_cast<const Query *>(query);
-  return q ? q->total_groups : 0;
+  return q ? q->result.total_groups : 0;
 }
 
 llkv_status llkv_hip_query_partial_groups(const llkv_hip_query *query, uint64_t *n_groups, uint32_t *n_keys, uint32_t *lanes_per_group,
                                           const int64_t **key_values, const uint8_t **key_valid, const uint64_t **lanes) {
   const Query *q = reinterpret_cast<const Query *>(query);
-  if (!q || !q->sorted || !q->lazy.active) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "not a finished sort-based GROUP BY");
+  if (!q || !q->sorted || !q->result.view.active) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "not a finished sort-based GROUP BY");
   if (q->order.active())
     return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "partial groups of a query with an ORDER BY / LIMIT: order the merged groups (set_group_order before merge_groups)");
   if (q->having.active())
     return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "partial groups of a query with a HAVING: filter the merged groups (set_having before merge_groups)");
-  if (n_groups) *n_groups = q->lazy.n;
-  if (n_keys) *n_keys = q->lazy.n_keys;
-  if (lanes_per_group) *lanes_per_group = (uint32_t)q->lazy.k;
-  if (key_values) *key_values = q->lazy.key_vals;
-  if (key_valid) *key_valid = q->lazy.key_valid;
-  if (lanes) *lanes = q->lazy.lanes;
+  const LazyGroups &lz = q->result.view;
+  if (n_groups) *n_groups = lz.n;
+  if (n_keys) *n_keys = lz.n_keys;
+  if (lanes_per_group) *lanes_per_group = (uint32_t)lz.k;
+  if (key_values) *key_values = lz.key_vals;
+  if (key_valid) *key_valid = lz.key_valid;
+  if (lanes) *lanes = lz.lanes;
   return LLKV_OK;
 }
 
 llkv_status llkv_hip_query_merge_groups(llkv_hip_query *query, uint32_t world, const uint64_t *rank_groups, const int64_t *const *key_values,
                                         const uint8_t *const *key_valid, const uint64_t *const *lanes) {
   Query *q = reinterpret_cast<Query *>(query);
-  if (!q || !q->sorted || !q->lazy.active) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "not a finished sort-based GROUP BY");
+  if (!q || !q->sorted || !q->result.view.active) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "not a finished sort-based GROUP BY");
   if (world == 0 || !rank_groups || !key_values || !key_valid || !lanes) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "NULL argument");
-  int rc = sorted_groupby_merge(q->sorted, world, rank_groups, key_values, key_valid, lanes, &q->lazy);
+  int rc = sorted_groupby_merge(q->sorted, world, rank_groups, key_values, key_valid, lanes, &q->result.view);
   if (!rc) rc = q->apply_merged_order();
   return (llkv_status)rc;
 }
@@ -1488,9 +1366,7 @@ const char *llkv_hip_query_route_note(const llkv_hip_query *query) {
                      : q->plan.acc_lds      ? "GROUP BY with per-thread accumulator columns in LDS"
                      : q->plan.grouped      ? "GROUP BY with register accumulators"
                                             : "ungrouped aggregates, register accumulators";
-  if (q->order_note.empty()) return base;
-  q->note_buf = std::string(base) + q->order_note;
-  return q->note_buf.c_str();
+  return q->result.noted(base);
 }
 
 const char *llkv_hip_query_kernel_signature(const llkv_hip_query *query) {

@@ -353,46 +353,22 @@ int jit_launch(const JitKernel &k, const ScanParams &p, hipStream_t stream);
 int jit_launch_raw(hipFunction_t fn, uint32_t grid, void *params, size_t bytes, hipStream_t stream, uint32_t block = kBlock);
 void jit_shutdown();
 
-struct GroupKey { // GroupKeyValue: String or Int (llkv-executor/src/lib.rs:99-106)
-  bool is_int = false;
-  bool is_null = false; // GroupKeyValue::Null
-  int64_t i = 0;
-  std::string s;
-  // ORDER BY key ASC with NULLS FIRST (the caller re-sorts the handful of groups for any other order)
-  bool operator<(const GroupKey &o) const { return (is_null || o.is_null) ? (is_null && !o.is_null) : (is_int ? i < o.i : s < o.s); }
-  bool operator==(const GroupKey &o) const { return (is_null || o.is_null) ? (is_null == o.is_null) : (is_int ? i == o.i : s == o.s); }
-};
-// The finished groups of a dense / shared-image plan live in two flat arrays (keys: n_groups × n_keys, values: n_groups ×
-// n_aggs): a vector pair per group was two heap allocations each — as much time as the kernel for 2 526 groups.
-struct GroupStore {
-  size_t n = 0, n_keys = 0, n_values = 0;
-  std::vector<GroupKey> keys;
-  std::vector<llkv_value> values;
-  void reset(size_t groups, size_t keys_per_group, size_t values_per_group) {
-    n = 0; n_keys = keys_per_group; n_values = values_per_group;
-    keys.clear(); values.clear();
-    keys.reserve(groups * keys_per_group);
-    values.resize(groups * values_per_group);
-  }
-  size_t size() const { return n; }
-  bool empty() const { return n == 0; }
-  const GroupKey &key(size_t g, size_t k) const { return keys[g * n_keys + k]; }
-  llkv_value &value(size_t g, size_t a) { return values[g * n_values + a]; }
-  const llkv_value &value(size_t g, size_t a) const { return values[g * n_values + a]; }
-};
-
-// Result of a sort-based GROUP BY, kept as the arrays the device produced (already in output order, pinned host
-// memory) and finalized cell by cell on request: millions of groups cost no per-group host objects.
+// The finished groups of a GROUP BY, as flat arrays in output order and decoded cell by cell on request: millions of groups cost no
+// per-group host objects (a vector pair per group was as much time as the kernel for 2 526 groups).  A view: the arrays belong to
+// whoever filled it — the pinned buffers of a sort-based / partitioned run, the merge of a sharded table's groups, the storage of
+// GroupResult (dense routes).  An ungrouped query is one row with zero keys.
 struct LazyGroups {
   bool active = false;
   uint64_t n = 0;
   int k = 0;                       // lanes per group: rows, first row id, aggregate lanes
   uint32_t n_keys = 0;
-  const uint64_t *lanes = nullptr; // [n][k]
+  const uint64_t *lanes = nullptr; // [n][k], finalized on request; nullptr: the aggregates are finalized already, in `values`
+  const llkv_value *values = nullptr;  // [n][n_values] (dense routes: their finalize needs more than a group's lanes)
+  uint32_t n_values = 0;
   const int64_t *key_vals = nullptr;   // [n_keys][n] raw key cells (dictionary code / integer)
   const uint8_t *key_valid = nullptr;  // [n_keys][n]
   const LoweredPlan *plan = nullptr;   // aggregate finalization
-  std::vector<const ColumnInfo *> key_cols;
+  std::vector<const ColumnInfo *> key_cols; // what decodes a key cell: a Utf8 column's dictionary, else the integer itself
 };
 
 // ORDER BY output columns, then OFFSET / LIMIT, over the groups of a GROUP BY (llkv_hip_query_set_group_order; group_order.hip).
@@ -437,7 +413,7 @@ struct HavingProgram {
 // Expressions (`exprs`, what EXPR operands name): value-stack underflow, more than one value left, COALESCE with arg = 0, unknown
 // ops, an EXPR leaf, an index out of range, more than kHavingMaxValueDepth pending values — the message names the expression and the token.
 int having_validate(const llkv_having_node *nodes, uint32_t n, const llkv_having_expr *exprs, uint32_t n_exprs, uint32_t n_keys, uint32_t n_aggs, std::string *err);
-// The host evaluator (the one of llkv_hip_having_eval and of Query::apply_order): cell(operand, &v, &key_dtype) yields the
+// The host evaluator (the one of llkv_hip_having_eval and of GroupResult::apply): cell(operand, &v, &key_dtype) yields the
 // finalized cell of a KEY / AGGREGATE operand and, for a key, its column's dtype (what types the cell).  *truth: HavingTruth.
 using HavingCell = std::function<int(const llkv_having_operand &, llkv_value *, int32_t *)>;
 int having_eval(const llkv_having_node *nodes, uint32_t n, const llkv_having_expr *exprs, uint32_t n_exprs, const HavingCell &cell, int32_t *truth);
@@ -507,7 +483,7 @@ void join_group_state_free(struct JoinGroupState *s); // join_group.cpp
 struct Query;
 // The result tail of a join → GROUP BY (llkv_hip_join_groupby_set_tail, join_group.cpp).  After a launch: whether the execution ran
 // with the tail.  After the merge of a sharded table's groups: the dimension cells of the merged groups, looked up on the device
-// and kept on the host, so that Query::apply_order filters and orders them (a no-op without a tail).
+// and kept on the host, so that GroupResult::apply filters and orders them (a no-op without a tail).
 void join_tail_after_launch(Query *q);
 int join_tail_extend_merged(Query *q);
 // A leaf of a HAVING value expression that is statically not Integer / Float / Boolean / Null (LLKV_UNSUPPORTED, *err names it):
@@ -542,10 +518,45 @@ struct TableEpochs {
   int check() const; // LLKV_OK, or LLKV_INVALID_ARGUMENT "the … table was appended to after this handle was prepared …: prepare it again"
 };
 
+// The finished groups of a Query and which of them the caller sees (group_result.cpp).  Every route leaves `view`; a HAVING or an
+// ORDER BY / OFFSET / LIMIT that no device pass served is applied by apply(): the caller then sees a selection of the view's rows.
+struct GroupResult {
+  LazyGroups view; // filled by sorted_groupby_run / part_groupby_run / sorted_groupby_merge, or by set_dense
+  uint64_t total_groups = 0; // groups after HAVING, before OFFSET / LIMIT
+  // no result (before the first finish, a failed one, a join tail that no longer matches); total_groups keeps the latest finish's
+  void reset() { view.active = false; row_mapped = false; row_map.clear(); note.clear(); }
+  // The dense routes' storage: Query::finish_from_exchange fills [n_keys][n] raw key cells with validity and [n][n_values]
+  // finalized cells, then set_dense points the view at them (a finish that fails in between leaves no result).
+  std::vector<int64_t> dense_kv;
+  std::vector<uint8_t> dense_kvalid;
+  std::vector<llkv_value> dense_values;
+  void set_dense(const LoweredPlan &plan, uint64_t n, std::vector<const ColumnInfo *> key_cols);
+  uint64_t unordered_rows() const { return view.active ? view.n : 0; } // the view's rows: before a HAVING / an order on the host
+  uint64_t rows() const { return row_mapped ? row_map.size() : unordered_rows(); } // the rows the caller sees
+  const std::vector<uint64_t> *mapped_rows() const { return row_mapped ? &row_map : nullptr; } // … as rows of the view (nullptr: all, in place)
+  // One cell of output row `out_row`.  Date32 / Boolean key cells are handed over as LLKV_DT_INT64: key_dtype types them (HAVING).
+  int cell_key(uint64_t out_row, uint32_t key, llkv_value *out) const { return key_at(view_row(out_row), key, out); }
+  int cell_value(uint64_t out_row, uint32_t agg, llkv_value *out) const { return value_at(view_row(out_row), agg, out); }
+  int32_t key_dtype(uint32_t key) const { return key < view.key_cols.size() ? view.key_cols[key]->dtype : (int32_t)LLKV_DT_INT64; }
+  // The HAVING, then the order, over the view (nullptr: none, or not this rank's to apply).  `done`: what the run that filled the
+  // view did on the device already; nullptr: a dense route.
+  int apply(const HavingProgram *having, const GroupOrderSpec *order, const GroupOrderDone *done);
+  const char *noted(const char *route) const; // the route note + which paths served the HAVING and the order at the last finish
+
+ private:
+  bool row_mapped = false;
+  std::vector<uint64_t> row_map; // output row i = the view's row row_map[i]
+  std::string note;             // "; having: …" and "; order: …"
+  mutable std::string note_buf; // route + note
+  uint64_t view_row(uint64_t out_row) const { return !row_mapped ? out_row : out_row < row_map.size() ? row_map[out_row] : UINT64_MAX; }
+  int key_at(uint64_t row, uint32_t key, llkv_value *out) const;
+  int value_at(uint64_t row, uint32_t agg, llkv_value *out) const;
+};
+
 struct Query {
   const Table *table = nullptr;
   TableEpochs epochs; // the table (join → GROUP BY: fact, dim, dim2) and the generations this query was lowered over
-  LazyGroups lazy;
+  GroupResult result;
   SortedGroupBy *sorted = nullptr; // set when the dense GROUP BY kernel cannot hold the groups: executions run synchronously in launch()
   struct JoinGroupState *join_state = nullptr; // join → GROUP BY (join_group.cpp): the dimension side's key set and sorted rows
   LoweredPlan plan;
@@ -580,23 +591,12 @@ struct Query {
   uint64_t *d_exchange() const { return host_mapped ? h_exchange() : d_ring.as<uint64_t>(); } // the image the kernels write
   bool order_by_keys = false;
   uint32_t n_user_aggs = 0, n_user_keys = 0;
-  GroupStore groups;
   // ORDER BY / OFFSET / LIMIT over the groups (llkv_hip_query_set_group_order): applied by the device top-k of the sort-based and
-  // partitioned routes, or on the host — then output row i reads the result's row row_map[i]
+  // partitioned routes, or on the host (GroupResult::apply)
   GroupOrderSpec order;
   HavingProgram having; // llkv_hip_query_set_having: filters the groups before the order
-  bool row_mapped = false;
-  std::vector<uint64_t> row_map;
-  uint64_t total_groups = 0;
-  std::string order_note;           // "; having: …" and "; order: …" — which paths served the HAVING and the order at the last finish
-  mutable std::string note_buf;     // route_note + order_note
-  uint64_t result_rows() const { return lazy.active ? lazy.n : groups.size(); } // before the order
-  int apply_order(const GroupOrderDone *done);
-  int32_t key_dtype_of(uint32_t key) const;
   int apply_merged_order(); // a sharded table's groups after the merge
   bool plan_grouped() const { return sorted != nullptr || plan.grouped; }
-  int cell_key(uint64_t group, uint32_t key, llkv_value *out) const;     // the result before the order
-  int cell_value(uint64_t group, uint32_t agg, llkv_value *out) const;
   // ungrouped SUM/AVG(Int64) without overflow-excluding statistics: plan that emits the argument values of
   // the selected rows in row order, for the exact prefix-overflow check (index = aggregate, empty = n/a)
   std::vector<LoweredPlan> exact_plans;

@@ -1,6 +1,6 @@
 // having.cpp — HAVING over the output cells of a GROUP BY, host side: the owned program, its validation and THE host evaluator
 // (evaluate_having_expr llkv-executor/src/lib.rs:6667-7006; value expressions as operands :7177-7516).  llkv_hip_having_eval(_ex)
-// and Query::apply_order both run having_eval;
+// and GroupResult::apply both run having_eval;
 // the numeric rules it applies are those of having_rules.h, which the device flag kernel (group_having.hip) applies too.
 #include "engine.hpp"
 #include "having_rules.h"
@@ -58,7 +58,7 @@ HavingValue literal_value(const llkv_literal &l, const char **str) {
 }
 
 // plan_value_from_array (llkv-plan/src/plans.rs:1131-1197) of a finalized cell.  `column_dtype`: a key cell is typed by its
-// COLUMN (Query::cell_key hands Date32 and Boolean cells over as LLKV_DT_INT64); < 0: an aggregate cell, typed by itself.
+// COLUMN (GroupResult::cell_key hands Date32 and Boolean cells over as LLKV_DT_INT64); < 0: an aggregate cell, typed by itself.
 HavingValue cell_value(const llkv_value &v, int32_t column_dtype, const char **str) {
   *str = nullptr;
   if (v.is_null) return {kHvNull, 0};

@@ -20,7 +20,7 @@
 //                    finished groups
 //        the tail    (llkv_hip_join_groupby_set_tail: HAVING, ORDER BY, OFFSET / LIMIT) extends the groups in HBM before anything is copied
 //                    out, and the GROUP BY's own device HAVING and top-k take the payload and the position as key cells; the merged
-//                    groups of a sharded fact table are extended on the host side and filtered and ordered by Query::apply_order
+//                    groups of a sharded fact table are extended on the host side and filtered and ordered by GroupResult::apply
 //      One translation of the caller's ORDER BY (join_order_spec) and one row builder (build_join_rows) serve both.
 // No joined row ever exists: the fact columns are read once (predicate columns, then the arguments of the rows that join).
 #include "engine.hpp"
@@ -92,7 +92,7 @@ struct JoinGroupState {
   // them, so the device pointers are those of the staged columns, and Table::cols is a std::map, whose nodes do not move)
   JoinPayloadCols tail_pc{};                    // the payload columns as the lookup kernel reads them …
   std::vector<const ColumnInfo *> tail_cols;     // … and, for LazyGroups::key_cols, the columns that type the extended cells
-  bool tail_applied = false; // the latest execution ran with the tail: Query::lazy holds extended key cells
+  bool tail_applied = false; // the latest execution ran with the tail: Query::result holds extended key cells
   std::vector<int64_t> m_kv; // extended key cells of a sharded table's merged groups
   std::vector<uint8_t> m_kvalid;
 
@@ -324,11 +324,11 @@ static int join_groupby_rows(Query *q, const uint32_t *payload_fields, uint32_t 
   if (!q || !q->join_state || !q->sorted || !out) return set_error(LLKV_INVALID_ARGUMENT, "not a join → GROUP BY query");
   if (q->join_state->tail_set)
     return set_error(LLKV_INVALID_ARGUMENT, "the query has a result tail set (its groups may be filtered or cut): read llkv_hip_join_groupby_tail_rows, or clear the tail");
-  if (!q->lazy.active) return set_error(LLKV_INVALID_ARGUMENT, "the query has not finished an execution yet");
+  if (!q->result.view.active) return set_error(LLKV_INVALID_ARGUMENT, "the query has not finished an execution yet");
   if ((rc = q->epochs.check())) return rc; // (the payload gather reads the dimension's columns through the rows kept at prepare)
   if (n_payload > 4) return set_error(LLKV_UNSUPPORTED, "more than 4 payload columns");
   const JoinGroupState &st = *q->join_state;
-  const LazyGroups &lz = q->lazy;
+  const LazyGroups &lz = q->result.view;
   const uint32_t n_aggs = q->n_user_aggs;
   GroupOrderSpec spec;
   if ((rc = join_order_spec(order, n_order, n_aggs, n_payload, 0, limit, &spec))) return rc;
@@ -393,7 +393,7 @@ static int join_groupby_rows(Query *q, const uint32_t *payload_fields, uint32_t 
 // ---- the result tail: HAVING, ORDER BY / OFFSET / LIMIT before the groups leave the device --------------------------------------
 // The groups of the sort-based run stay in HBM in ascending key order; dim_cells makes them key cells 1 … n_payload (payload)
 // and n_payload + 1 (position), and the tail of every GROUP BY — having_device, group_order_device, or the copy-out and
-// Query::apply_order on the host — runs over the extended cells: a payload column is a key column, the position the last ascending
+// GroupResult::apply on the host — runs over the extended cells: a payload column is a key column, the position the last ascending
 // order term.
 static int join_tail_extend_device(const JoinGroupState *st, LazyGroups *out, const int64_t *d_kv, const uint8_t *d_kvalid, uint64_t n, hipStream_t s, Scratch *x_kv,
                                    Scratch *x_kvalid) {
@@ -418,7 +418,7 @@ int join_tail_extend_merged(Query *q) {
   if (!st.tail_set) return LLKV_OK;
   int rc = ensure_device();
   if (rc || (rc = q->epochs.check())) return rc;
-  LazyGroups &lz = q->lazy;
+  LazyGroups &lz = q->result.view;
   const uint64_t n = lz.n;
   const size_t nk = st.tail_cols.size();
   st.m_kv.assign(n * nk, 0);
@@ -442,7 +442,7 @@ static int join_groupby_set_tail(Query *q, const uint32_t *payload_fields, uint3
   if (q->n_launched != q->n_collected) return set_error(LLKV_INVALID_ARGUMENT, "executions in flight");
   JoinGroupState &st = *q->join_state;
   if (!n_payload && !n_having && !n_order && offset == 0 && limit == UINT64_MAX) { // clear: the next launch leaves plain groups again
-    if (st.tail_applied) { q->lazy.active = false; q->row_mapped = false; q->row_map.clear(); q->order_note.clear(); } // (its groups were filtered or cut)
+    if (st.tail_applied) q->result.reset(); // (its groups were filtered or cut)
     st.tail_set = st.tail_applied = false;
     st.tail_cols.clear();
     q->order = GroupOrderSpec();
@@ -463,7 +463,7 @@ static int join_groupby_set_tail(Query *q, const uint32_t *payload_fields, uint3
     if (int rc = having_expr_leaves_numeric(having, n_having, exprs, n_exprs, 1 + n_payload, [&](uint32_t k) { return cols[k]->dtype; }, *sorted_groupby_plan(q->sorted), n_aggs, &err))
       return set_error(rc, err);
   }
-  if (st.tail_applied) { q->lazy.active = false; q->row_mapped = false; q->row_map.clear(); q->order_note.clear(); } // (rows of another tail)
+  if (st.tail_applied) q->result.reset(); // (rows of another tail)
   st.tail_applied = false;
   st.tail_set = true;
   st.tail_pc = pc;
@@ -477,23 +477,23 @@ static int join_groupby_set_tail(Query *q, const uint32_t *payload_fields, uint3
   return LLKV_OK;
 }
 
-// The rows the tail left, in order: through Query::row_map when the host filtered or ordered, else the result's own rows.
+// The rows the tail left, in order: through GroupResult::mapped_rows when the host filtered or ordered, else the result's own rows.
 static int join_groupby_tail_rows(Query *q, JoinRows **out) {
   if (!q || !q->join_state || !q->sorted || !out) return set_error(LLKV_INVALID_ARGUMENT, "not a join → GROUP BY query");
   const JoinGroupState &st = *q->join_state;
   if (!st.tail_set) return set_error(LLKV_INVALID_ARGUMENT, "no result tail is set (llkv_hip_join_groupby_set_tail)");
-  if (!q->lazy.active || !st.tail_applied || q->n_launched != q->n_collected)
+  if (!q->result.view.active || !st.tail_applied || q->n_launched != q->n_collected)
     return set_error(LLKV_INVALID_ARGUMENT, "the query has not finished an execution with this tail yet");
-  const LazyGroups &lz = q->lazy;
+  const LazyGroups &lz = q->result.view;
   const uint32_t n_payload = st.tail_pc.n;
   std::unique_ptr<JoinRows> res(new JoinRows());
   res->n_aggs = q->n_user_aggs;
   res->n_payload = n_payload;
-  res->total_groups = q->total_groups;
-  const uint64_t take = q->row_mapped ? q->row_map.size() : lz.n;
+  res->total_groups = q->result.total_groups;
+  const uint64_t take = q->result.rows();
   if (take && lz.n_keys != n_payload + 2) return set_error(LLKV_INTERNAL, "join → GROUP BY: the groups carry no dimension cells");
   if (take)
-    if (int rc = build_join_rows(lz, lz.key_vals + lz.n, lz.key_valid + lz.n, n_payload, res->n_aggs, q->row_mapped ? &q->row_map : nullptr, false, res.get())) return rc;
+    if (int rc = build_join_rows(lz, lz.key_vals + lz.n, lz.key_valid + lz.n, n_payload, res->n_aggs, q->result.mapped_rows(), false, res.get())) return rc;
   *out = res.release();
   return LLKV_OK;
 }
