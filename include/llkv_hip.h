@@ -850,6 +850,31 @@ llkv_status llkv_hip_filter_row_ids(const llkv_hip_table *table, const llkv_filt
                                     uint64_t **out_row_ids, uint64_t *out_len);
 void llkv_hip_free(void *ptr);
 
+/* Top-N of a projection scan: ORDER BY projected columns, then OFFSET / LIMIT, applied in HBM (needs_post_sort
+ * llkv-executor/src/lib.rs:10979-11130 → sort_record_batch_with_order :13762-13868, SelectExecution::stream :10918-10955).
+ * The rows delivered are those of llkv_hip_scan_stream with the same projections, filter, include_nulls and
+ * include_row_ids and no `order`, concatenated in scan order, stably sorted by the terms as arrow's lexsort_to_indices
+ * compares them — integers, Date32 and Boolean numerically, floats by total_cmp (−NaN < −inf < … < −0.0 < +0.0 < … <
+ * +inf < +NaN), Utf8 by bytes, Decimal128 by value, per term NULLs first or last whatever `descending` says — and cut to
+ * [offset, offset + limit).  Ties keep scan order (ascending table position).  One callback with at most 1 024 rows, the
+ * views as in llkv_hip_scan_stream; none when no row is left.  *total_rows (may be NULL): the selected rows before
+ * OFFSET / LIMIT.  n_order = 0 returns the first rows in scan order.
+ * Served: offset + limit <= 1024, at most 8 terms, column projections only, an unsharded table, term columns of any
+ * staged type but a Decimal128 staged beyond 64 bits — anything else is LLKV_UNSUPPORTED and the message names it (a
+ * binding then streams through llkv_hip_scan_stream as before).  LLKV_INVALID_ARGUMENT: a term position outside the
+ * projections ("ORDER BY position N is out of bounds for M columns"), options->order_enabled, a NULL on_batch.       */
+typedef struct llkv_scan_order_term {
+  uint32_t projection; /* position in `projections` (OrderTarget::Index; a binding resolves OrderTarget::Column by name) */
+  int32_t descending;
+  int32_t nulls_first;
+} llkv_scan_order_term;
+
+llkv_status llkv_hip_scan_topn(const llkv_hip_table *table, const llkv_projection *projections, uint32_t n_projections,
+                               const llkv_filter *filters, uint32_t n_filters, const llkv_eval_op *ops, uint32_t n_ops,
+                               const llkv_scan_options *options, const llkv_scan_order_term *order, uint32_t n_order,
+                               uint64_t offset, uint64_t limit /* UINT64_MAX: no limit */,
+                               llkv_on_batch on_batch, void *user, uint64_t *total_rows /* may be NULL */);
+
 /* ------------------------------------------------------------------------- */
 /* Hash join — `TableJoinExt::join_stream` llkv-join/src/lib.rs:240-282.        */
 /* Build = right, probe = left; output = matching (left row, right row) index  */

@@ -118,6 +118,11 @@ def scan_options(include_nulls=False, include_row_ids=False, order=None) -> "CSc
     return o
 
 
+class CScanOrderTerm(C.Structure):
+    """llkv_scan_order_term: one ORDER BY term of llkv_hip_scan_topn, over a position in the projection list."""
+    _fields_ = [("projection", C.c_uint32), ("descending", C.c_int32), ("nulls_first", C.c_int32)]
+
+
 # llkv_hip_table_append_utf8_column_ex: more than 256 distinct strings may be staged, as u32 codes in byte order of the strings;
 # views of such a column carry precision 4 (values are uint32 codes)
 UTF8_WIDE_CODES = 1

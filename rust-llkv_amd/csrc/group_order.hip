@@ -22,6 +22,7 @@
 // groups of a sharded table, larger limits and terms without a device form (a computed DECIMAL argument's precision check).
 #include "engine.hpp"
 #include "group_cell.hip.h"
+#include "order_select.hip.h"
 
 #include <algorithm>
 #include <cstring>
@@ -31,10 +32,6 @@
 namespace llkv {
 
 namespace {
-
-constexpr int kMaxTerms = 8;
-constexpr int kMaxWords = 16;   // order-key words of the terms (a term: its NULL word and one or two value words)
-constexpr uint32_t kOrderBlock = 256;
 
 enum TermKind : int32_t { kTermKeyInt = 0, kTermKeyUtf8 = 1, kTermAgg = 2 };
 
@@ -57,17 +54,6 @@ struct OrderParams {
   int32_t err_lane[kMaxErrAggs], err_count_lane[kMaxErrAggs];
   OrderTerm t[kMaxTerms];
 };
-
-// Threshold of the radix select: the composite keys (words 0 … n_words − 1, then the position) whose bits under `mask` equal
-// `prefix` are still tied with it; `need` of them are still to be taken.
-struct SelectState {
-  unsigned long long need;
-  uint32_t done, pad;
-  unsigned long long prefix[kMaxWords + 1], mask[kMaxWords + 1];
-};
-
-__device__ inline uint64_t i64_image(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }
-__device__ inline uint64_t f64_image(uint64_t b) { return (b >> 63) ? ~b : (b | 0x8000000000000000ull); } // f64::total_cmp
 
 // order-preserving unsigned image of a finalized cell (group_cell.hip.h: agg_cell): *null, or the value's words (one, two for Decimal128)
 __device__ inline void agg_image(const AggCell &a, const uint64_t *g, bool *null, uint64_t *w0, uint64_t *w1) {
@@ -221,12 +207,6 @@ __global__ __launch_bounds__(kOrderBlock) void order_gather_kernel(const uint64_
 }
 
 bool is_decimal_fin(AggFinal f) { return agg_cell_type(f) == kCellDec; }
-
-uint32_t grid_for(uint64_t n) {
-  const uint64_t want = (n + kOrderBlock - 1) / kOrderBlock;
-  const uint64_t cap = (uint64_t)g_ctx.cu_count * 8;
-  return (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
-}
 
 } // namespace
 
