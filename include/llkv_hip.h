@@ -408,6 +408,13 @@ uint64_t llkv_hip_table_generation(const llkv_hip_table *table); /* number of ap
  * use and streams in place of the 8-byte column.  Device memory the table holds beside its columns: 4 B per row
  * and image; an append drops them.  `LLKV_HIP_JOIN_NO_KEY_IMAGE=1` turns them off.                                               */
 llkv_status llkv_hip_table_key_images(const llkv_hip_table *table, uint32_t *n_images, uint64_t *device_bytes);
+/* Value images: a 1-byte code per row beside an 8 B/row column (Float64, 64-bit integers, Decimal128 within 64 bits) that holds at
+ * most 256 distinct 64-bit patterns, found and coded on the device at the first prepare of a dense aggregate / GROUP BY plan that
+ * reads the column.  The fused scan streams the codes and decodes them to the column's own bits from a table in LDS:
+ * results do not change.  Device memory the table holds beside its columns: 1 B per row and image; an append drops them.  Tables of
+ * fewer than 2^20 local rows build none (`LLKV_HIP_VALUE_IMAGE_MIN_ROWS=n` moves the bound), `LLKV_HIP_NO_VALUE_IMAGES=1` turns
+ * them off; both are read when a query is prepared.                                                                            */
+llkv_status llkv_hip_table_value_images(const llkv_hip_table *table, uint32_t *n_images, uint64_t *device_bytes);
 
 /* Integer column statistics (the analogue of ChunkMetadata.min/max_val_u64, llkv-column-map/src/store/
  * descriptor.rs:19-84).  Plans use them (exact SUM without overflow tracking, dense integer GROUP BY), so every
@@ -1344,6 +1351,10 @@ typedef struct llkv_column_desc {
   double f_absmax;    /* largest |v| over the column's finite values         */
   double f_absmin_nz; /* smallest non-zero |v| over them (0: none)           */
   int32_t f_all_finite; /* … and the column holds no NaN / ±∞                */
+  uint32_t value_codes; /* an 8 B/row column that carries a value image
+                         * (llkv_hip_table_value_images): its distinct 64-bit
+                         * patterns, 1 … 256; 0 = none.  The dense Plan<…> routes
+                         * then stream 1 B/row: "D8<F64,16>" in Cols<…>         */
 } llkv_column_desc;
 
 /* `grouped`: 0 = ungrouped aggregates, 1 = GROUP BY (groups in first-appearance

@@ -3,12 +3,18 @@
 #include <algorithm>
 #include <cstdlib>
 #include "catalog.hpp"
+#include "plan.hpp"
 #include "fused_scan.hip.h"
 #include "select.hip.h"
 
 #include <cstring>
 
 namespace llkv {
+
+// the host's model of the kernels' LDS use (plan.hpp: plan_workgroups_per_cu) against the kernels themselves
+static_assert(kPlanBlock == kBlock && kPlanRedBatch == kRedBatch && kPlanRedRow == kRedRow && kPlanImageBlock == kImgBlock, "plan.hpp: kPlan… follow fused_scan.hip.h");
+static_assert(plan_image_replicas(24, 8) == image_replicas(24, 8) && plan_image_replicas(2000, 8) == image_replicas(2000, 8) &&
+              plan_image_replicas(5000, 4) == image_replicas(5000, 4) && plan_image_replicas(9000, 8) == image_replicas(9000, 8), "plan.hpp: plan_image_replicas follows image_replicas");
 
 template <class P> static hipError_t launch_plan(const ScanParams &p, hipStream_t stream) {
   if (p.n_tiles == 0) return hipSuccess;
@@ -177,6 +183,88 @@ hipError_t launch_narrow_i64(const int64_t *values, uint64_t n, int32_t *out, hi
   if (n == 0) return hipSuccess;
   const uint32_t grid = (uint32_t)std::min<uint64_t>((n / 2 + 255) / 256 + 1, 256 * 16);
   hipLaunchKernelGGL(narrow_i64_kernel, dim3(grid), dim3(256), 0, stream, values, n, out);
+  return hipGetLastError();
+}
+
+// ---- value images (engine.hpp: ValueImage) -------------------------------------------------------------------------------------
+// Pass 1: the distinct 64-bit patterns of a column, as long as there are at most kValueCodesMax of them.  Every workgroup keeps an
+// open-addressing set in LDS (kValueSetSlots slots; the all-ones pattern marks a free slot and is tracked by a flag of its own) and
+// leaves it in out[workgroup][0 … n) with n in counts[workgroup]; the host merges the sets.  A set that passes kValueCodesMax
+// raises *give_up, which every workgroup polls between batches of kValueBatch steps: a column of many values costs one batch.
+constexpr uint32_t kValueSetSlots = 2048, kValueBatch = 4;
+constexpr unsigned long long kValueFree = ~0ull;
+__global__ __launch_bounds__(256) void value_set_kernel(const unsigned long long *values, uint64_t n, unsigned long long *out, uint32_t *counts, uint32_t *give_up) {
+  __shared__ unsigned long long keys[kValueSetSlots];
+  __shared__ uint32_t held, has_free_pattern, stop, out_n;
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t i = tid; i < kValueSetSlots; i += 256) keys[i] = kValueFree;
+  if (tid == 0) { held = 0; has_free_pattern = 0; stop = 0; out_n = 0; }
+  __syncthreads();
+  // a batch adds at most kValueBatch · 256 patterns to a set that held at most kValueCodesMax before it: the probe below always finds a slot
+  static_assert(kValueCodesMax + kValueBatch * 256 <= kValueSetSlots, "a batch must not fill the set");
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  uint64_t row = (uint64_t)blockIdx.x * 256 + tid;
+  const uint64_t steps = (n + stride - 1) / stride;
+  unsigned long long last = kValueFree;
+  for (uint64_t s = 0; s < steps; s += kValueBatch) {
+    for (uint32_t b = 0; b < kValueBatch; ++b, row += stride) {
+      if (row >= n) continue;
+      const unsigned long long v = values[row];
+      if (v == last) continue;
+      last = v;
+      if (v == kValueFree) { has_free_pattern = 1; continue; }
+      uint32_t h = (uint32_t)mix64(v) & (kValueSetSlots - 1);
+      for (uint32_t probe = 0; probe < kValueSetSlots; ++probe, h = (h + 1) & (kValueSetSlots - 1)) {
+        unsigned long long seen = keys[h];
+        if (seen == kValueFree) seen = atomicCAS(&keys[h], kValueFree, v);
+        if (seen == kValueFree) { atomicAdd(&held, 1u); break; }
+        if (seen == v) break;
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const bool over = held + has_free_pattern > kValueCodesMax;
+      if (over) atomicExch(give_up, 1u);
+      stop = over || __hip_atomic_load(give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    }
+    __syncthreads();
+    if (stop) return; // (the same answer in every thread: `stop` is written between the two barriers only)
+  }
+  unsigned long long *mine = out + (uint64_t)blockIdx.x * (kValueCodesMax + 1);
+  for (uint32_t i = tid; i < kValueSetSlots; i += 256)
+    if (keys[i] != kValueFree) {
+      const uint32_t at = atomicAdd(&out_n, 1u);
+      if (at <= kValueCodesMax) mine[at] = keys[i];
+    }
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t c = out_n < kValueCodesMax + 1 ? out_n : kValueCodesMax + 1;
+    if (has_free_pattern && c <= kValueCodesMax) mine[c++] = kValueFree;
+    counts[blockIdx.x] = c;
+  }
+}
+hipError_t launch_value_set(const void *values, uint64_t n, uint64_t *d_sets, uint32_t *d_counts, uint32_t *d_give_up, hipStream_t stream) {
+  hipLaunchKernelGGL(value_set_kernel, dim3(kValueSetGrid), dim3(256), 0, stream, (const unsigned long long *)values, n, (unsigned long long *)d_sets, d_counts, d_give_up);
+  return hipGetLastError();
+}
+// Pass 2: every row's code = the position of its pattern in the dictionary (n_dict ≤ 256 patterns in ascending unsigned order).
+__global__ __launch_bounds__(256) void value_code_kernel(const unsigned long long *values, uint64_t n, const unsigned long long *dict, uint32_t n_dict, uint8_t *out) {
+  __shared__ unsigned long long d[kValueCodesMax];
+  for (uint32_t i = threadIdx.x; i < kValueCodesMax; i += 256) d[i] = i < n_dict ? dict[i] : ~0ull;
+  __syncthreads();
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t row = (uint64_t)blockIdx.x * 256 + threadIdx.x; row < n; row += stride) {
+    const unsigned long long v = values[row];
+    uint32_t lo = 0; // the first entry ≥ v among the 256 (entries past the dictionary are all-ones)
+#pragma unroll
+    for (uint32_t half = kValueCodesMax / 2; half >= 1; half /= 2) lo += d[lo + half - 1] < v ? half : 0u;
+    out[row] = (uint8_t)lo;
+  }
+}
+hipError_t launch_value_code(const void *values, uint64_t n, const uint64_t *d_dict, uint32_t n_dict, uint8_t *out, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 256 * 16);
+  hipLaunchKernelGGL(value_code_kernel, dim3(grid), dim3(256), 0, stream, (const unsigned long long *)values, n, (const unsigned long long *)d_dict, n_dict, out);
   return hipGetLastError();
 }
 

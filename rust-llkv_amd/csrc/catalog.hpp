@@ -34,6 +34,13 @@ hipError_t launch_exclusive_scan(const uint64_t *in, uint64_t *out, uint32_t n, 
 // Column statistics (min/max of an integer column already resident in HBM).
 hipError_t launch_ascending_check(const void *values, uint32_t width /*4 or 8, signed*/, const TileDesc *tiles, uint32_t n_tiles, uint32_t *flag, hipStream_t stream);
 hipError_t launch_narrow_i64(const int64_t *values, uint64_t n, int32_t *out, hipStream_t stream); // Int64 → the 4-byte key image
+// Value images (engine.hpp: ValueImage).  Pass 1 — the distinct 64-bit patterns of `n` rows of an 8 B/row column, unless there are
+// more than kValueCodesMax: workgroup w of the kValueSetGrid leaves d_counts[w] ≤ kValueCodesMax + 1 patterns in
+// d_sets[w · (kValueCodesMax + 1) …]; *d_give_up (zero before the launch) is raised when some workgroup met more, and the other
+// outputs then mean nothing.  Pass 2 — out[row] = position of the row's pattern in the dictionary (ascending, unsigned).
+constexpr uint32_t kValueCodesMax = 256, kValueSetGrid = 512;
+hipError_t launch_value_set(const void *values, uint64_t n, uint64_t *d_sets, uint32_t *d_counts, uint32_t *d_give_up, hipStream_t stream);
+hipError_t launch_value_code(const void *values, uint64_t n, const uint64_t *d_dict, uint32_t n_dict, uint8_t *out, hipStream_t stream);
 hipError_t launch_minmax_i64(const int64_t *values, uint64_t n, int64_t *d_minmax /*[2]*/, hipStream_t stream);
 hipError_t launch_minmax_i32(const int32_t *values, uint64_t n, int64_t *d_minmax /*[2]*/, hipStream_t stream);
 

@@ -80,6 +80,60 @@ int PlanTables::upload(const LoweredPlan &p, hipStream_t s) {
   return LLKV_OK;
 }
 
+// The decode tables of the plan's coded slots, back to back in slot order (ScanParams::value_tables): the image's dictionary, then
+// zeros up to the table's power of two.
+int PlanTables::upload_value_tables(const LoweredPlan &p, const Table &t, hipStream_t s) {
+  if (p.value_table_entries() == 0) return LLKV_OK;
+  std::vector<uint64_t> image;
+  for (size_t i = 0; i < p.slot_codes.size(); ++i) {
+    if (!p.slot_codes[i]) continue;
+    auto img = t.value_images.find(p.slot_fields[i]);
+    if (img == t.value_images.end() || img->second.dict.size() > p.slot_codes[i])
+      return set_error(LLKV_INTERNAL, "plan " + p.type_string + " was lowered over a value image the table does not hold");
+    image.insert(image.end(), img->second.dict.begin(), img->second.dict.end());
+    image.resize(image.size() + (p.slot_codes[i] - img->second.dict.size()), 0);
+  }
+  if (int rc = value_tables.alloc(image.size() * 8)) return rc;
+  HIP_TRY(hipMemcpyAsync(value_tables.p, image.data(), image.size() * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s)); // `image` is pageable and goes out of scope
+  return LLKV_OK;
+}
+
+// Value images (engine.hpp: ValueImage) for the 8 B/row value slots of a dense plan.  `build` = false: the column descriptions of the
+// fields that hold an image or could get one, with the smallest table (ColumnInfo::value_codes = 1) — what a dry lowering needs to
+// say whether the plan has the LDS for any table at all, before anything is built.  `build` = true: the images of the fields in
+// `wanted` are built where missing, and the descriptions carry their real code counts.
+static int value_image_columns(const Table &table, const ColumnResolver &resolve, const LoweredPlan &p, bool build, const std::set<uint32_t> *wanted,
+                               std::map<uint32_t, ColumnInfo> *coded) {
+  coded->clear();
+  if (std::getenv("LLKV_HIP_NO_VALUE_IMAGES")) return LLKV_OK;
+  uint64_t min_rows = 1ull << 20;
+  if (const char *e = std::getenv("LLKV_HIP_VALUE_IMAGE_MIN_ROWS")) { // a row count; anything else leaves the default
+    char *end = nullptr;
+    const unsigned long long v = std::strtoull(e, &end, 10);
+    if (end != e && *end == 0 && e[0] != '-') min_rows = v;
+  }
+  for (size_t s = 0; s < p.slot_fields.size(); ++s) {
+    const uint32_t field = p.slot_fields[s];
+    if (p.slot_is_valid[s] != 0 || dtype_width(p.slot_dtypes[s]) != 8 || coded->count(field) || (wanted && !wanted->count(field))) continue;
+    const ColumnInfo *ci = resolve(field);
+    if (!ci || ci->wide128) continue;
+    uint32_t codes = 1;
+    if (build) {
+      const ValueImage *img = nullptr;
+      if (int rc = get_value_image(table, field, min_rows, &img)) return rc;
+      if (!img) continue;
+      codes = (uint32_t)img->dict.size();
+    } else if (!value_image_candidate(table, field, min_rows)) {
+      continue;
+    }
+    ColumnInfo with = *ci;
+    with.value_codes = codes;
+    coded->emplace(field, std::move(with));
+  }
+  return LLKV_OK;
+}
+
 // The tile is the canonical unit of the reduction (one partial per tile — per (tile, wave) for LDS-resident states —
 // folded in order): its length depends on the plan alone, never on the table size, the shard or the GPU count, so
 // results are bit-identical across launch geometries.  Register-resident states amortise their block reduction quickly
@@ -138,7 +192,13 @@ static uint32_t pick_scan_grid(const LoweredPlan &p, uint32_t n_tiles) {
   const uint32_t cus = g_ctx.cu_count;
   uint32_t grid = cus;
   if (n_tiles >= 8 * cus) {
-    const uint32_t lo = (p.k <= 6 ? 184u : 232u) * cus / 256u, hi = (p.k <= 6 ? 232u : 256u) * cus / 256u;
+    uint32_t lo = (p.k <= 6 ? 184u : 232u) * cus / 256u, hi = (p.k <= 6 ? 232u : 256u) * cus / 256u;
+    // A plan over value images (LoweredPlan::slot_codes) streams less than half the bytes: what binds it is no longer the HBM but its DS
+    // atomics and the latency of its loads, and it wants every workgroup the LDS admits resident — Q1 at 17 B/row, two workgroups per
+    // CU: 193 workgroups 0.300 ms, 384: 0.217, 458: 0.185, 512: 0.195, 524 (a second round of 12): 0.249, 1 024: 0.195
+    // (profiles/value_images/).  Again the balanced count at or below that residency; one workgroup per CU keeps the rule above.
+    const uint32_t per_cu = p.value_table_entries() ? plan_workgroups_per_cu(p, true) : 1u;
+    if (per_cu > 1) { hi = per_cu * cus; lo = hi - hi / 8; }
     // the smallest count that keeps the workgroups ≥ 99.5 % busy (else the busiest): on the slower boxes fewer
     // workgroups still win among balanced counts (193: 354 µs, 204: 356, 216: 357, 229: 361; 192: 362)
     double best = 0.0;
@@ -228,6 +288,27 @@ int prepare_query(const Table *table, const llkv_filter *filters, uint32_t n_fil
     return set_error(rc, dense_err + "; sort-based route: " + g_last_error);
   }
   if (rc) return set_error(rc, err);
+  if (!q->plan.always_false) { // the same plan over the value images of its 8 B/row columns: other Cols<…>, the same lanes and finalize
+    std::map<uint32_t, ColumnInfo> coded;
+    const ColumnResolver with_images = [&](uint32_t fid) -> const ColumnInfo * {
+      auto it = coded.find(fid);
+      return it == coded.end() ? resolve(fid) : &it->second;
+    };
+    const auto lower_coded = [&](LoweredPlan *ip) {
+      std::string image_err;
+      return lower_plan(with_images, filters, n_filters, ops, n_ops, key_fields, n_keys, aggs, n_aggs, grouped, !order_by_keys, ip, &image_err, q->plan.acc_image) == LLKV_OK &&
+             ip->lanes == q->plan.lanes && ip->lane_ops == q->plan.lane_ops && ip->value_table_entries() != 0;
+    };
+    // dry first: with the smallest tables, does the plan take coded slots at all?  Only the fields it would read coded are built.
+    LoweredPlan dry, ip;
+    if ((rc = value_image_columns(*table, resolve, q->plan, /*build=*/false, nullptr, &coded))) return rc;
+    if (!coded.empty() && lower_coded(&dry)) {
+      std::set<uint32_t> wanted;
+      for (size_t s = 0; s < dry.slot_codes.size(); ++s) if (dry.slot_codes[s]) wanted.insert(dry.slot_fields[s]);
+      if ((rc = value_image_columns(*table, resolve, q->plan, /*build=*/true, &wanted, &coded))) return rc;
+      if (!coded.empty() && lower_coded(&ip)) q->plan = std::move(ip);
+    }
+  }
   const LoweredPlan &p = q->plan;
   if (!grouped) {
     q->exact_plans.resize(n_aggs);
@@ -250,7 +331,7 @@ int prepare_query(const Table *table, const llkv_filter *filters, uint32_t n_fil
   if ((rc = get_tileset(*table, pick_tile_rows(p), &ts))) return rc;
   q->tiles = ts;
 
-  if ((rc = q->tables.upload(p, g_ctx.stream)) || (rc = bind_plan(p, *table, &q->tables, &q->params))) return rc;
+  if ((rc = q->tables.upload(p, g_ctx.stream)) || (rc = q->tables.upload_value_tables(p, *table, g_ctx.stream)) || (rc = bind_plan(p, *table, &q->tables, &q->params))) return rc;
   q->params.tiles = ts->d_tiles.get<TileDesc>();
   q->params.n_tiles = ts->n_tiles;
   q->params.scan_grid = pick_scan_grid(p, ts->n_tiles);

@@ -19,6 +19,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <utility>
 #include <vector>
@@ -234,6 +235,7 @@ inline RadixRange radix_range(const ColumnInfo &ci, bool by_stats = false) {
 inline const void *slot_buffer(const std::map<uint32_t, DeviceColumn> &cols, const LoweredPlan &p, size_t s) {
   const DeviceColumn &c = cols.at(p.slot_fields[s]);
   const uint8_t part = s < p.slot_is_valid.size() ? p.slot_is_valid[s] : 0;
+  if (s < p.slot_codes.size() && p.slot_codes[s]) return nullptr; // a coded slot reads the field's value image: bind_plan(…, ScanParams) binds it
   return part == 1 ? c.d_valid.get() : part == 2 ? c.d_hi.get() : c.d_values.get();
 }
 
@@ -257,6 +259,16 @@ struct KeyImage {
   ColumnInfo info; // the column's, with dtype = Int32
 };
 
+// A 1-byte image of an 8 B/row column that holds at most 256 distinct 64-bit patterns (table.cpp: get_value_image): row r holds the
+// position of the column's bits in row r among the patterns in ascending unsigned order — NaN payloads, −0.0 and +0.0 are patterns of
+// their own, so decoding gives back the column's own bits.  It covers the padding rows and the slack behind the image too: every code
+// a tile can read indexes the dictionary.  What the dense aggregate / GROUP BY scans stream in place of the column (LoweredPlan::
+// slot_codes); built on first use, kept with the table, same row layout; an append (a new generation) drops it.
+struct ValueImage {
+  DeviceBuffer d;             // uint8_t codes
+  std::vector<uint64_t> dict; // code → pattern
+};
+
 struct Table {
   uint16_t table_id = 0;
   uint32_t rank = 0, world = 1;
@@ -270,6 +282,8 @@ struct Table {
   std::map<uint32_t, DeviceColumn> cols;
   std::map<uint32_t, TileSet> tilesets;
   std::map<uint32_t, KeyImage> key_images;
+  std::map<uint32_t, ValueImage> value_images;
+  std::set<uint32_t> value_image_refused; // fields of this generation whose discovery found more than 256 patterns: not asked again
   // Row ids that are not the positions 0 … n − 1 (llkv_hip_table_set_row_ids): the id of every local row, in the row layout of
   // the column images; empty = dense ids.  Everything inside works on positions; the calls that REPORT row ids translate.
   DeviceBuffer d_row_ids; // uint64_t
@@ -294,10 +308,12 @@ inline ColumnResolver table_resolver(const Table &t) {
 // The next plan-carried table is added here — upload, bind and the check of bind_plan — and nowhere else.
 struct PlanTables {
   Scratch dict_num, code_bits;
+  Scratch value_tables; // decode tables of the plan's coded slots (LoweredPlan::slot_codes), written by upload_value_tables
   // no-op for a plan without tables; complete on return (the sources are pageable: one stream synchronisation for both)
   int upload(const LoweredPlan &p, hipStream_t s);
-  bool holds(const LoweredPlan &p) const { return (p.dict_num.empty() || dict_num.p) && (p.code_bits.empty() || code_bits.p); }
-  void bind(ScanParams *sp) const { sp->dict_num = dict_num.as<double>(); sp->code_bits = code_bits.as<uint64_t>(); }
+  int upload_value_tables(const LoweredPlan &p, const Table &t, hipStream_t s);
+  bool holds(const LoweredPlan &p) const { return (p.dict_num.empty() || dict_num.p) && (p.code_bits.empty() || code_bits.p) && (p.value_table_entries() == 0 || value_tables.p); }
+  void bind(ScanParams *sp) const { sp->dict_num = dict_num.as<double>(); sp->code_bits = code_bits.as<uint64_t>(); sp->value_tables = value_tables.as<uint64_t>(); }
 };
 
 // Binds a lowered plan to the parameter block of its kernel: zeroes *params, then col[] from the table's columns by the plan's
@@ -313,9 +329,15 @@ template <class Params> void bind_plan(const LoweredPlan &p, const Table &t, Par
 inline int bind_plan(const LoweredPlan &p, const Table &t, const PlanTables *tables, ScanParams *sp) {
   bind_plan(p, t, sp);
   for (size_t i = 0; i < p.key_strides.size(); ++i) sp->key_stride[i] = p.key_strides[i];
-  if (tables ? !tables->holds(p) : !p.dict_num.empty() || !p.code_bits.empty())
-    return set_error(LLKV_INTERNAL, "plan " + p.type_string + " carries dict_num / code_bits tables its binder did not upload");
+  if (tables ? !tables->holds(p) : !p.dict_num.empty() || !p.code_bits.empty() || p.value_table_entries() != 0)
+    return set_error(LLKV_INTERNAL, "plan " + p.type_string + " carries dict_num / code_bits / decode tables its binder did not upload");
   if (tables) tables->bind(sp);
+  for (size_t s = 0; s < p.slot_codes.size(); ++s)
+    if (p.slot_codes[s]) {
+      auto img = t.value_images.find(p.slot_fields[s]);
+      if (img == t.value_images.end()) return set_error(LLKV_INTERNAL, "plan " + p.type_string + " reads a value image the table does not hold");
+      sp->col[s] = img->second.d.get();
+    }
   return LLKV_OK;
 }
 
@@ -644,6 +666,14 @@ int prepare_query(const Table *table, const llkv_filter *filters, uint32_t n_fil
 int get_tileset(const Table &t, uint32_t tile_rows, const TileSet **out);
 // *out = nullptr when the column does not qualify (not Int64, no statistics, a value outside 32 bits, fewer than `min_rows` rows)
 int get_key_image(const Table &t, uint32_t field, uint64_t min_rows, const KeyImage **out);
+// The value image of `field` (*out = nullptr: the column is not 8 B/row, holds more than 256 patterns, or the table has fewer than
+// `min_rows` local rows); built on first use.
+int get_value_image(const Table &t, uint32_t field, uint64_t min_rows, const ValueImage **out);
+// … whether get_value_image would hold or try to build one (the column's storage, the row bound, no refusal remembered): nothing is built
+bool value_image_candidate(const Table &t, uint32_t field, uint64_t min_rows);
+// The distinct patterns the workgroups of launch_value_set left (catalog.hpp), merged into ascending unsigned order; false: more than
+// kValueCodesMax.  Host only.
+bool merge_value_sets(const uint64_t *sets, const uint32_t *counts, uint32_t n_sets, std::vector<uint64_t> *dict);
 
 // `configured_thread_count` of the reference's shared Rayon pool (llkv-threading/src/lib.rs:13-31): LLKV_MAX_THREADS
 // when it parses to a positive number, else the detected parallelism (affinity mask ∧ cgroup quota, what

@@ -77,6 +77,10 @@ struct U64 { using T = uint64_t; static constexpr int W = 8; static constexpr bo
 struct F64 { using T = double; static constexpr int W = 8; static constexpr bool is_float = true; };
 struct I128 { using T = __int128; static constexpr int W = 16; static constexpr bool is_float = false; }; // outputs only
 struct U8 { using T = uint8_t; static constexpr int W = 1; static constexpr bool is_float = false; };
+// A value image (table.cpp: get_value_image): the slot streams ONE byte per row — the code of the row's value among the at most N_
+// distinct 64-bit patterns of an 8-byte column — and decode_range puts the column's own 64 bits in its place before anything reads
+// the slot.  Loaded like a U8 slot; expressions, predicates and keys go on naming Col<S, Ty>.
+template <class Ty, int N_> struct D8 { using T = typename Ty::T; static constexpr int W = 1; static constexpr int N = N_; static constexpr bool is_float = Ty::is_float; };
 
 template <class... Ts> struct Cols { static constexpr int N = sizeof...(Ts); };
 
@@ -153,6 +157,51 @@ template <class CL, int LO, int HI> __device__ __forceinline__ void load_range(c
   if constexpr (LO < HI && LO < CL::N) {
     load_pair<typename ColAt<LO, CL>::type>(p.col[LO], row, ld.w[LO]);
     load_range<CL, LO + 1, HI>(p, row, ld);
+  }
+}
+
+// ---- decode tables of the coded slots (D8) ----------------------------------------------------------------------------------
+// ScanParams::value_tables holds the tables of a plan's coded slots back to back in slot order, N entries each (a power of two:
+// the code is masked, so any byte indexes its own table).  Every workgroup copies them to LDS once, before its tile loop; the decode
+// is one ds_read_b64 per row and column.  (Decoding through global memory — DictNum's form — lost to the plain columns: three
+// gathers per row cost more address-pipeline time than the bytes saved, profiles/r04/value_image_probe.json.)
+template <class Ty> struct CodedSize { static constexpr int N = 0; };
+template <class Ty, int M> struct CodedSize<D8<Ty, M>> {
+  static_assert(M >= 1 && M <= 256 && (M & (M - 1)) == 0 && Ty::W == 8, "a decode table has a power of two ≤ 256 of 8-byte entries");
+  static constexpr int N = M;
+};
+template <class CL, int LO, int HI> constexpr int coded_entries() { // table entries of the coded slots in [LO, HI)
+  if constexpr (LO < HI && LO < CL::N) return CodedSize<typename ColAt<LO, CL>::type>::N + coded_entries<CL, LO + 1, HI>();
+  else return 0;
+}
+template <int NT> struct ValueTables {
+  static __device__ __forceinline__ uint64_t *lds() { __shared__ uint64_t t[NT]; return t; }
+};
+template <> struct ValueTables<0> {
+  static __device__ __forceinline__ uint64_t *lds() { return nullptr; }
+};
+// every thread of the workgroup calls this once, at a point the whole workgroup reaches
+template <class CL> __device__ __forceinline__ const uint64_t *stage_value_tables(const ScanParams &p) {
+  constexpr int NT = coded_entries<CL, 0, CL::N>();
+  uint64_t *t = ValueTables<NT>::lds();
+  if constexpr (NT > 0) {
+    for (uint32_t i = threadIdx.x; i < (uint32_t)NT; i += blockDim.x) t[i] = p.value_tables[i];
+    __syncthreads();
+  }
+  return t;
+}
+// the coded slots in [LO, HI) of two loaded rows: code bytes → the two 8-byte values
+template <class CL, int LO, int HI> __device__ __forceinline__ void decode_range(const uint64_t *vtab, Loaded &ld) {
+  if constexpr (LO < HI && LO < CL::N) {
+    constexpr int n = CodedSize<typename ColAt<LO, CL>::type>::N;
+    if constexpr (n > 0) {
+      const uint64_t *t = vtab + coded_entries<CL, 0, LO>();
+      const uint32_t codes = ld.w[LO][0];
+      const uint64_t a = t[codes & (uint32_t)(n - 1)], b = t[(codes >> 8) & (uint32_t)(n - 1)];
+      ld.w[LO][0] = (uint32_t)a; ld.w[LO][1] = (uint32_t)(a >> 32);
+      ld.w[LO][2] = (uint32_t)b; ld.w[LO][3] = (uint32_t)(b >> 32);
+    }
+    decode_range<CL, LO + 1, HI>(vtab, ld);
   }
 }
 
@@ -1020,6 +1069,7 @@ template <class P> __device__ __forceinline__ void fused_scan_body_reg(const Sca
   // is reduced on its own and publishes its own partial: the association — and so the bits — do not depend on the grid.
   const uint32_t g = p.scan_grid;
   if (g && blockIdx.x >= g) return; // (a launch wider than the grid the host announced must not walk off the tile list)
+  const uint64_t *vtab = stage_value_tables<typename P::ColList>(p);
   const uint32_t t_first = g ? (uint32_t)((uint64_t)blockIdx.x * p.n_tiles / g) : blockIdx.x;
   const uint32_t t_last = g ? (uint32_t)((uint64_t)(blockIdx.x + 1) * p.n_tiles / g) : (blockIdx.x < p.n_tiles ? blockIdx.x + 1 : blockIdx.x);
   for (uint32_t tile = t_first; tile < t_last; ++tile) {
@@ -1050,6 +1100,7 @@ template <class P> __device__ __forceinline__ void fused_scan_body_reg(const Sca
       uint32_t gidv[U][kRowsPerThread];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
+        decode_range<typename P::ColList, 0, P::EARLY>(vtab, ld[u]);
         const uint32_t row0 = (s + u) * kStepRows + tid * kRowsPerThread;
 #pragma unroll
         for (int j = 0; j < kRowsPerThread; ++j) {
@@ -1074,6 +1125,8 @@ template <class P> __device__ __forceinline__ void fused_scan_body_reg(const Sca
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
+        // (a lane that requested nothing decodes whatever the slot holds: the code is masked to its table, the rows do not pass)
+        decode_range<typename P::ColList, P::EARLY, P::ColList::N>(vtab, ld[u]);
         const uint32_t row0 = (s + u) * kStepRows + tid * kRowsPerThread;
 #pragma unroll
         for (int j = 0; j < kRowsPerThread; ++j) {
@@ -1116,6 +1169,7 @@ template <class P> __device__ __forceinline__ void fused_scan_body_reg(const Sca
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
+      decode_range<typename P::ColList, 0, P::ColList::N>(vtab, ld[u]);
       const uint32_t row0 = (s + u) * kStepRows + tid * kRowsPerThread;
 #pragma unroll
       for (int j = 0; j < kRowsPerThread; ++j) {
@@ -1331,6 +1385,7 @@ template <class P> __device__ __forceinline__ void fused_scan_body_lds(const Sca
   uint32_t tile = (uint32_t)((uint64_t)blockIdx.x * p.n_tiles / gridDim.x);
   const uint32_t tile_end = (uint32_t)((uint64_t)(blockIdx.x + 1) * p.n_tiles / gridDim.x);
   if (tile >= tile_end) return;
+  const uint64_t *vtab = stage_value_tables<typename P::ColList>(p);
   const uint32_t n_parts = p.n_tiles * kLdsParts;
 #pragma unroll
   for (int l = 0; l < NG * K; ++l) acc[l][tid] = lane_identity(ops.v[l]);
@@ -1363,6 +1418,7 @@ template <class P> __device__ __forceinline__ void fused_scan_body_lds(const Sca
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
+      decode_range<typename P::ColList, 0, P::ColList::N>(vtab, ld[u]);
       const uint32_t row0 = (s + u) * kStepRows + tid * kRowsPerThread;
 #pragma unroll
       for (int j = 0; j < kRowsPerThread; ++j) {
@@ -1453,6 +1509,7 @@ template <class P> __device__ __forceinline__ void image_scan_body(const ScanPar
     else img_all[i] = lane_identity(op);
   }
   if (tid == 0) block_err = 0;
+  const uint64_t *vtab = stage_value_tables<typename P::ColList>(p);
   __syncthreads();
 
   // A tile is U steps of 2 048 rows (engine.cpp: pick_tile_rows — tiles are only a work list here), so one batch of
@@ -1464,9 +1521,10 @@ template <class P> __device__ __forceinline__ void image_scan_body(const ScanPar
 #pragma unroll
     for (int u = 0; u < U; ++u) load_all<typename P::ColList>(p, td.dev_row + (uint64_t)u * kImgStepRows + (uint64_t)tid * kRowsPerThread, ld[u]);
   };
-  auto accumulate = [&](const TileDesc &td, const Loaded (&ld)[U]) {
+  auto accumulate = [&](const TileDesc &td, Loaded (&ld)[U]) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
+      decode_range<typename P::ColList, 0, P::ColList::N>(vtab, ld[u]);
       const uint32_t row0 = u * kImgStepRows + tid * kRowsPerThread;
 #pragma unroll
       for (int j = 0; j < kRowsPerThread; ++j) {

@@ -211,7 +211,8 @@ static std::string cols_string(const LoweredPlan &p, uint64_t *bytes) { // "Cols
   std::string cols = "Cols<";
   uint64_t b = 0;
   for (size_t i = 0; i < p.slot_dtypes.size(); ++i) {
-    cols += (i ? "," : "") + std::string(dtype_tag(p.slot_dtypes[i]));
+    const uint32_t coded = i < p.slot_codes.size() ? p.slot_codes[i] : 0; // a value image: what is streamed changes, the algorithmic bytes do not
+    cols += (i ? "," : "") + (coded ? "D8<" + std::string(dtype_tag(p.slot_dtypes[i])) + "," + std::to_string(coded) + ">" : std::string(dtype_tag(p.slot_dtypes[i])));
     b += dtype_width(p.slot_dtypes[i]);
   }
   if (bytes) *bytes = b;
@@ -1999,6 +2000,28 @@ struct AggLowering {
 
 } // namespace
 
+// Workgroups of a dense plan's kernel that one CU's 160 KB of LDS admit (fused_scan.hip.h: the reduction buffer of a register-state
+// plan, the per-thread accumulator columns, one slice of the shared image in its replicas), with or without the plan's decode
+// tables — capped by what else bounds them: the threads of a CU for the shared image's and the per-thread columns' workgroups, and
+// four for a register-state plan, whose kernels hold their state in 64 … 160 VGPRs (3 … 8 waves per SIMD: the LDS is not what bounds
+// them until fewer than four workgroups fit).  The sizes are the kernels' own (plan.hpp: kPlan…, asserted in catalog.hip).
+uint32_t plan_workgroups_per_cu(const LoweredPlan &p, bool with_tables) {
+  size_t bytes, cap;
+  if (p.acc_image) { // image_scan_body: img_all[R · K · NG] + block_err
+    const size_t cell = p.image_cell32 ? 4 : 8, cells = ((size_t)p.ng + p.image_passes - 1) / p.image_passes * (size_t)p.k_image;
+    bytes = (size_t)plan_image_replicas((int)cells, (int)cell) * cells * cell + 4;
+    cap = kPlanCuThreads / kPlanImageBlock;
+  } else if (p.acc_lds) { // fused_scan_body_lds: acc[NG · K][kBlock]
+    bytes = (size_t)(p.lanes - 1) * kPlanBlock * 8;
+    cap = kPlanCuThreads / kPlanBlock;
+  } else { // fused_scan_body_reg: red[min(LANES, kRedBatch)][kRedRow]
+    bytes = (size_t)std::min(p.lanes, kPlanRedBatch) * kPlanRedRow * 8;
+    cap = 4;
+  }
+  if (with_tables) bytes += (size_t)p.value_table_entries() * 8;
+  return (uint32_t)std::min(cap, kPlanCuLdsBytes / std::max<size_t>(bytes, 1));
+}
+
 static std::atomic<bool> g_exact_f64_sums{false};
 void plan_set_exact_f64_sums(bool on) { g_exact_f64_sums.store(on); }
 bool plan_exact_f64_sums() { return g_exact_f64_sums.load(); }
@@ -2153,6 +2176,23 @@ int lower_plan(const ColumnResolver &resolve, const llkv_filter *filters, uint32
     if (u == 1 || u == 2 || u == 4 || u == 8) p.unroll = u;
   }
 
+  // Value images (dense routes only: the partitioned kernels read plain columns): a value slot of an 8 B/row column that carries
+  // one streams its code bytes.  The decode tables live in LDS beside the plan's own state; a plan whose workgroups per CU they
+  // would reduce keeps its plain columns.
+  if (!partitioned) {
+    std::vector<uint32_t> codes(p.slot_fields.size(), 0);
+    bool any = false;
+    for (size_t s = 0; s < p.slot_fields.size(); ++s) {
+      const ColumnInfo *ci = resolve(p.slot_fields[s]);
+      if (p.slot_is_valid[s] != 0 || dtype_width(p.slot_dtypes[s]) != 8 || !ci || ci->wide128) continue;
+      codes[s] = value_table_entries(ci->value_codes);
+      any |= codes[s] != 0;
+    }
+    if (any) {
+      p.slot_codes = codes;
+      if (plan_workgroups_per_cu(p, true) < plan_workgroups_per_cu(p, false)) p.slot_codes.clear();
+    }
+  }
   const std::string cols = cols_string(p, &p.bytes_per_row);
   // register-state plans with a predicate: the argument-only columns are read for the rows that pass (fused_scan.hip.h:
   // Plan::EARLY, late materialisation — Q6 reads 20 B of every row and the price of the 2 % that pass)

@@ -42,7 +42,17 @@ struct ColumnInfo {
   bool wide128 = false;
   uint64_t wide_absmax_hi = 0, wide_absmax_lo = 0;
   uint64_t wide_min_hi = 0, wide_min_lo = 0, wide_max_hi = 0, wide_max_lo = 0; // i128 smallest / largest value of a wide128 column (every cell, NULL ones too)
+  // an 8 B/row column with a value image (engine.hpp: ValueImage — one code byte per row beside the column): the number of distinct
+  // 64-bit patterns, 1 … 256; 0 = no image.  Never derived from the statistics above: the prepare that found the image sets it.
+  uint32_t value_codes = 0;
 };
+// entries of the decode table of a column with `codes` distinct patterns: the next power of two, 16 at least (0: no table)
+inline uint32_t value_table_entries(uint32_t codes) {
+  if (codes == 0 || codes > 256) return 0;
+  uint32_t n = 16;
+  while (n < codes) n *= 2;
+  return n;
+}
 
 // A Utf8 column of more than kNarrowDictMax distinct strings is staged in the wide form: 4-byte codes, code c = the position of
 // its string in the dictionary sorted by bytes (str::cmp).  At most kNarrowDictMax strings: 1-byte codes in first-appearance
@@ -106,6 +116,10 @@ struct LoweredPlan {
   bool late_columns = false;          // register-state plan whose argument-only columns are read for the passing rows (Plan::EARLY)
   std::vector<int32_t> slot_dtypes;   // slot → storage dtype (UTF8 = 1-byte codes, UINT32 for the codes of a wide Utf8 column)
   std::vector<uint8_t> slot_is_valid; // what of the field the slot reads: 0 its values, 1 its validity mask (1 B/row), 2 the high halves of a wide Decimal128 column
+  // dense Plan<…> routes: entries of the slot's decode table when it streams the field's value image ("D8<F64,16>" in Cols<…>:
+  // 1 B/row, decoded to the same 64 bits in the kernel), 0 for a plain slot; empty = none.  The tables lie back to back in slot order.
+  std::vector<uint32_t> slot_codes;
+  uint32_t value_table_entries() const { uint32_t n = 0; for (uint32_t c : slot_codes) n += c; return n; }
   std::vector<int64_t> lit_i;
   std::vector<double> lit_f;
   std::vector<uint32_t> key_fields, key_slots, key_strides, key_cards;
@@ -152,6 +166,19 @@ struct LoweredPlan {
   // bitmaps of the CodeBits leaves over wide Utf8 columns (ScanParams::code_bits): leaf at word offset S, bit c = code c qualifies
   std::vector<uint64_t> code_bits;
 };
+
+// Workgroups of a dense plan's kernel per CU as its LDS use admits them, with or without the decode tables of its coded slots
+// (plan.cpp); lower_plan keeps a plan's plain columns when the tables would reduce the count.
+uint32_t plan_workgroups_per_cu(const LoweredPlan &p, bool with_tables);
+// What that count assumes of the kernels' LDS use: workgroup sizes, the register-state plans' reduction buffer, the shared image's
+// replica rule.  catalog.hip, which sees both sides, asserts every one of them against fused_scan.hip.h.
+constexpr int kPlanBlock = 256, kPlanRedBatch = 16, kPlanRedRow = kPlanBlock + kPlanBlock / 16, kPlanImageBlock = 1024, kPlanCuThreads = 2048;
+constexpr size_t kPlanCuLdsBytes = 160u * 1024;
+constexpr int plan_image_replicas(int cells, int cell_bytes) {
+  int r = 1;
+  while (r < 32 && (long)(2 * r) * cells * cell_bytes <= 64 * 1024) r *= 2;
+  return r;
+}
 
 // `str.trim().parse::<f64>().unwrap_or(0.0)` of the reference's numeric coercion (llkv-aggregate/src/lib.rs:426-434):
 // Rust's float grammar — sign, decimal digits with an optional point, optional exponent, or inf / infinity / nan in

@@ -36,6 +36,7 @@ static int column_infos(const llkv_column_desc *cols, uint32_t n_cols, std::vect
     infos[i].f_absmax = cols[i].f_absmax;
     infos[i].f_absmin_nz = cols[i].f_absmin_nz;
     infos[i].f_all_finite = cols[i].f_all_finite != 0;
+    infos[i].value_codes = cols[i].value_codes;
     for (uint32_t d = 0; d < cols[i].dict_size; ++d)
       infos[i].dictionary.push_back(cols[i].dictionary && cols[i].dictionary[d] ? cols[i].dictionary[d] : "");
     // a wide Utf8 column's codes are positions in its byte-ordered dictionary: the descriptor must list it so

@@ -137,6 +137,9 @@ struct ScanParams {
   uint32_t rk_help_first, rk_helpers;
   // CodeBits leaves over wide Utf8 columns (fused_scan.hip.h): the plan's bitmaps back to back (LoweredPlan::code_bits)
   const uint64_t *code_bits;
+  // decode tables of the plan's coded slots (fused_scan.hip.h: D8), back to back in slot order: entry c of a slot's table = the 64
+  // bits of the column value with code c; the tail of a table past the column's distinct count is zero
+  const uint64_t *value_tables;
 };
 
 constexpr int kMaxOuts = 8;

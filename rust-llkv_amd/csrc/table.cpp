@@ -133,6 +133,78 @@ int get_key_image(const Table &tc, uint32_t field, uint64_t min_rows, const KeyI
   return LLKV_OK;
 }
 
+// The distinct patterns the workgroups of launch_value_set found, merged: ascending unsigned order, so the codes are a function of
+// the column's contents alone.  False when there are more than kValueCodesMax.
+bool merge_value_sets(const uint64_t *sets, const uint32_t *counts, uint32_t n_sets, std::vector<uint64_t> *dict) {
+  dict->clear();
+  for (uint32_t w = 0; w < n_sets; ++w) {
+    if (counts[w] > kValueCodesMax) return false;
+    dict->insert(dict->end(), sets + (size_t)w * (kValueCodesMax + 1), sets + (size_t)w * (kValueCodesMax + 1) + counts[w]);
+    if (dict->size() > 4 * kValueCodesMax || w + 1 == n_sets) {
+      std::sort(dict->begin(), dict->end());
+      dict->erase(std::unique(dict->begin(), dict->end()), dict->end());
+      if (dict->size() > kValueCodesMax) return false;
+    }
+  }
+  return true;
+}
+
+// (t.mu held)
+static bool value_image_candidate_locked(const Table &t, uint32_t field, uint64_t min_rows) {
+  if (t.local_rows < min_rows || t.local_rows == 0 || t.value_image_refused.count(field)) return false;
+  auto it = t.cols.find(field);
+  if (it == t.cols.end()) return false;
+  const DeviceColumn &c = it->second;
+  return !c.info.wide128 && c.d_values && c.info.dtype != LLKV_DT_UTF8 && dtype_width(storage_dtype(c.info)) == 8;
+}
+bool value_image_candidate(const Table &tc, uint32_t field, uint64_t min_rows) {
+  Table &t = const_cast<Table &>(tc);
+  std::lock_guard<std::mutex> lk(t.mu);
+  return value_image_candidate_locked(t, field, min_rows);
+}
+
+int get_value_image(const Table &tc, uint32_t field, uint64_t min_rows, const ValueImage **out) {
+  *out = nullptr;
+  Table &t = const_cast<Table &>(tc);
+  std::lock_guard<std::mutex> lk(t.mu);
+  if (!value_image_candidate_locked(t, field, min_rows)) return LLKV_OK;
+  auto have = t.value_images.find(field);
+  if (have != t.value_images.end()) { *out = &have->second; return LLKV_OK; }
+  const DeviceColumn &c = t.cols.find(field)->second;
+  // (padding rows between chunks and the slack behind the image are rows like any other here: a tail step may read their codes)
+  const uint64_t rows = t.dev_rows + kSlackRows;
+  PhaseTrace trace("[llkv value_image] %-22s %9.3f ms\n", g_ctx.stream);
+  Scratch sets, counts;
+  int rc;
+  const size_t set_words = (size_t)kValueSetGrid * (kValueCodesMax + 1);
+  if ((rc = sets.alloc(set_words * 8)) || (rc = counts.alloc(((size_t)kValueSetGrid + 1) * 4))) return rc;
+  HIP_TRY(hipMemsetAsync(counts.p, 0, ((size_t)kValueSetGrid + 1) * 4, g_ctx.stream)); // [kValueSetGrid]: the give-up flag
+  HIP_TRY(launch_value_set(c.d_values.get(), rows, sets.as<uint64_t>(), counts.as<uint32_t>(), counts.as<uint32_t>() + kValueSetGrid, g_ctx.stream));
+  std::vector<uint32_t> h_counts(kValueSetGrid + 1);
+  HIP_TRY(hipMemcpyAsync(h_counts.data(), counts.p, h_counts.size() * 4, hipMemcpyDeviceToHost, g_ctx.stream));
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  ValueImage img;
+  bool few = h_counts[kValueSetGrid] == 0;
+  if (few) {
+    std::vector<uint64_t> h_sets(set_words);
+    HIP_TRY(hipMemcpyAsync(h_sets.data(), sets.p, set_words * 8, hipMemcpyDeviceToHost, g_ctx.stream));
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    few = merge_value_sets(h_sets.data(), h_counts.data(), kValueSetGrid, &img.dict) && !img.dict.empty();
+  }
+  trace.mark(few ? "distinct patterns" : "distinct patterns (gave up)");
+  if (!few) { t.value_image_refused.insert(field); return LLKV_OK; }
+  Scratch d_dict;
+  if ((rc = d_dict.alloc(img.dict.size() * 8))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_dict.p, img.dict.data(), img.dict.size() * 8, hipMemcpyHostToDevice, g_ctx.stream));
+  HIP_TRY(img.d.alloc(rows, 1));
+  HIP_TRY(launch_value_code(c.d_values.get(), rows, d_dict.as<uint64_t>(), (uint32_t)img.dict.size(), img.d.get<uint8_t>(), g_ctx.stream));
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream)); // (the dictionary's host and device copies go out of scope)
+  trace.mark("codes");
+  auto ins = t.value_images.emplace(field, std::move(img));
+  *out = &ins.first->second;
+  return LLKV_OK;
+}
+
 uint64_t table_chunk_rows(const llkv_hip_table *table, uint32_t global_chunk) {
   const Table *t = reinterpret_cast<const Table *>(table);
   return t && global_chunk < t->global_chunk_rows.size() ? t->global_chunk_rows[global_chunk] : 0;
@@ -1104,6 +1176,9 @@ static int append_chunks_impl(Table *t, const uint64_t *chunk_rows, uint32_t n_n
     t->tilesets.clear();
     for (auto &kv : t->key_images) if (kv.second.d) t->retired.push_back(std::move(kv.second.d));
     t->key_images.clear();
+    for (auto &kv : t->value_images) if (kv.second.d) t->retired.push_back(std::move(kv.second.d));
+    t->value_images.clear();
+    t->value_image_refused.clear();
   }
   for (auto &kv : t->cols) {
     kv.second.info.rows = t->total_rows;
@@ -1124,6 +1199,14 @@ llkv_status llkv_hip_table_key_images(const llkv_hip_table *table, uint32_t *n_i
   std::lock_guard<std::mutex> lk(t->mu);
   if (n_images) *n_images = (uint32_t)t->key_images.size();
   if (device_bytes) *device_bytes = t->key_images.size() * (t->dev_rows + kSlackRows) * 4;
+  return LLKV_OK;
+}
+llkv_status llkv_hip_table_value_images(const llkv_hip_table *table, uint32_t *n_images, uint64_t *device_bytes) {
+  if (!table) return (llkv_status)set_error(LLKV_INVALID_ARGUMENT, "table is NULL");
+  Table *t = const_cast<Table *>(reinterpret_cast<const Table *>(table));
+  std::lock_guard<std::mutex> lk(t->mu);
+  if (n_images) *n_images = (uint32_t)t->value_images.size();
+  if (device_bytes) *device_bytes = t->value_images.size() * (t->dev_rows + kSlackRows);
   return LLKV_OK;
 }
 uint64_t llkv_hip_table_generation(const llkv_hip_table *table) { return table ? reinterpret_cast<const Table *>(table)->generation : 0; }

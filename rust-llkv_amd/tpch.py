@@ -184,6 +184,11 @@ def q1() -> QueryPlan:
 QUERIES = {"c1": c1, "q6": q6, "q1": q1}
 
 
+# distinct 64-bit patterns of the low-cardinality 8-byte columns as a staged table's value images find them: quantity 1..50,
+# discount 0.00..0.10, tax 0.00..0.08, and the zero of the rows behind the table (already among the discounts and taxes)
+LINEITEM_VALUE_CODES = {L_QUANTITY: 51, L_DISCOUNT: 11, L_TAX: 9}
+
+
 def lineitem_column_descs(rows: int, keep: list, decimal: bool = False):
     """llkv_column_desc[] for plan lowering without data: statistics and dictionaries as
     staging discovers them on the synthetic data (quantity 1..50; flags in first-appearance
