@@ -882,6 +882,36 @@ llkv_status llkv_hip_scan_topn(const llkv_hip_table *table, const llkv_projectio
                                uint64_t offset, uint64_t limit /* UINT64_MAX: no limit */,
                                llkv_on_batch on_batch, void *user, uint64_t *total_rows /* may be NULL */);
 
+/* SELECT DISTINCT over a projection scan, deduplicated in HBM (the DISTINCT step of SelectExecution, llkv-executor/src/lib.rs:
+ * 10984-11011 → distinct_filter_batch :13720-13760 over CanonicalRow, llkv-types/src/canonical.rs; then ORDER BY :11052-11067
+ * and OFFSET / LIMIT :10918-10955; no NULL row is synthesised under DISTINCT, :11026 / :11039).
+ * The rows considered are exactly those of llkv_hip_scan_stream with the same projections, filter and include_nulls, in the
+ * same order — options->order_enabled, the one-column scan order, is part of that order.  A row survives iff no earlier row
+ * has the same canonical row; the first occurrence is delivered with its own cells, bit for bit (−0.0 before +0.0: −0.0
+ * comes out; the same for a NaN's sign and payload).  Per projected column: NULL equals NULL and nothing else (the bytes
+ * under an invalid cell never count); Int64, Date32, Boolean by value; Float64: every NaN one class, −0.0 and +0.0 one
+ * class, anything else by its bits; Decimal128 by raw value (the scale is the column's); Utf8 by string.  Int32, UInt32,
+ * UInt64 and Float32 have no canonical form in the reference: LLKV_INVALID_ARGUMENT "building canonical scalar is not
+ * supported for column type Int32" (…) when at least one row is selected — an empty selection canonicalises nothing and is
+ * LLKV_OK with no batch.
+ * n_order = 0: the survivors cut to [offset, offset + limit), in scan order, any number of them, in dense windows of 65 536
+ * rows, one callback each, none when no row is left (the reference cuts at the windows before DISTINCT: only the
+ * concatenation is promised).  include_row_ids: the first occurrences' ids.
+ * n_order > 0: the survivors ordered by the terms and cut, by the select, rank and gather of llkv_hip_scan_topn and under its
+ * rules and messages — ties keep first-occurrence order, offset + limit <= 1024, at most 8 terms, options->order_enabled
+ * with terms is LLKV_INVALID_ARGUMENT, a term position outside the projections too; one callback.
+ * LLKV_UNSUPPORTED, the message naming the cause: a computed projection, a sharded table, a projected Decimal128 column
+ * staged beyond 64 bits, 2^32 selected rows or more.  LLKV_INVALID_ARGUMENT: a NULL table or on_batch.
+ * *selected_rows: the rows before DISTINCT; *distinct_rows: after it, before OFFSET / LIMIT (both may be NULL).        */
+llkv_status llkv_hip_scan_distinct(const llkv_hip_table *table, const llkv_projection *projections, uint32_t n_projections,
+                                   const llkv_filter *filters, uint32_t n_filters, const llkv_eval_op *ops, uint32_t n_ops,
+                                   const llkv_scan_options *options,
+                                   const llkv_scan_order_term *order, uint32_t n_order, /* applied to the distinct rows */
+                                   uint64_t offset, uint64_t limit /* UINT64_MAX: none */,
+                                   llkv_on_batch on_batch, void *user,
+                                   uint64_t *selected_rows /* may be NULL: rows before DISTINCT */,
+                                   uint64_t *distinct_rows /* may be NULL: rows after DISTINCT, before OFFSET / LIMIT */);
+
 /* ------------------------------------------------------------------------- */
 /* Hash join — `TableJoinExt::join_stream` llkv-join/src/lib.rs:240-282.        */
 /* Build = right, probe = left; output = matching (left row, right row) index  */
@@ -1324,7 +1354,10 @@ typedef struct llkv_select_shape {
   int32_t has_having, has_distinct, has_scalar_subqueries; /* SQL breadth the GPU path leaves to the CPU routes     */
   /* has_having: a HAVING the binding could NOT lower into llkv_hip_query_set_having / _ex (CASE; a compare / NOT / AND / OR
    * used as a value; `Pred` leaves; EXISTS; an expression over Decimal128 / Utf8 / Date32 leaves, which set_having_ex
-   * refuses).  A binding that lowers its HAVING there passes has_having = 0.                                          */
+   * refuses).  A binding that lowers its HAVING there passes has_having = 0.
+   * has_distinct: a SELECT DISTINCT the binding could NOT lower into llkv_hip_scan_distinct (a computed projection, a
+   * sharded table, a Decimal128 column staged beyond 64 bits, anything but a single-table projection).  A binding that
+   * lowers its DISTINCT to that call passes has_distinct = 0.                                                          */
 } llkv_select_shape;
 /* `*route_out`: the route the reference takes.  Returns LLKV_OK when the GPU path serves it, LLKV_UNSUPPORTED when
  * the caller keeps its CPU route (message: why), LLKV_INVALID_ARGUMENT for a shape the reference rejects.          */

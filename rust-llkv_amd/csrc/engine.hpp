@@ -761,6 +761,23 @@ struct BitmapSink {
 int run_selection_lowered(const Table *t, const LoweredPlan &plan, Selection *sel, const KeySetView *key_set = nullptr, int single_pass = -1,
                           const BitmapSink *sink = nullptr, bool sync = true);
 
+// What the scans over a Selection share (stream.cpp).  sort_selection: ScanStreamOptions.order, the stable one-column sort of the
+// selection (o->order_enabled is the caller's to test).  selection_report_ids: the table's own row ids in place of the positions in
+// d_ids (a no-op for dense ids) — after any sort, before the ids are reported.  deliver_windows: rows [first, end) of the selection
+// through the Project kernel of `proj`, in dense windows of 65 536 rows, one callback each.
+int sort_selection(const Table *t, const llkv_scan_options *o, Selection *sel);
+int selection_report_ids(const Table *t, Selection *sel);
+int deliver_windows(const Table *t, const LoweredPlan &proj, const Selection &sel, uint64_t first, uint64_t end, const llkv_scan_options *options,
+                    llkv_on_batch on_batch, void *user);
+// The ORDER BY … OFFSET / LIMIT of llkv_hip_scan_topn (scan_topn.hip), in the two steps llkv_hip_scan_distinct shares with it: the
+// refusals that need no device (`world`: the table's — the sharded refusal keeps its place among them), and select, rank and gather
+// over a selection in scan order whose d_ids are positions and whose term columns are not wide decimals — one callback with rows
+// [offset, offset + limit) of the order.
+int topn_refusals(const llkv_scan_options *options, uint32_t n_projections, const llkv_scan_order_term *order, uint32_t n_order, uint64_t offset, uint64_t limit,
+                  uint32_t world);
+int topn_over_selection(const Table *t, const LoweredPlan &proj, const llkv_projection *projections, const llkv_scan_options *options,
+                        const llkv_scan_order_term *order, uint32_t n_order, uint64_t offset, uint64_t limit, const Selection &sel, llkv_on_batch on_batch, void *user);
+
 int run_join(const Table *left, const Table *right, const llkv_join_key *keys, uint32_t n_keys,
              const llkv_join_options *options, llkv_on_join_batch on_batch, void *user);
 int run_join_batches(const Table *left, const Table *right, const llkv_join_key *keys, uint32_t n_keys,

@@ -276,27 +276,35 @@ uint32_t describe_term(const DeviceColumn &c, const llkv_scan_order_term &o, con
 
 } // namespace
 
-int scan_topn(const Table *t, const llkv_projection *projections, uint32_t n_projections, const llkv_filter *filters, uint32_t n_filters,
-              const llkv_eval_op *ops, uint32_t n_ops, const llkv_scan_options *options, const llkv_scan_order_term *order, uint32_t n_order,
-              uint64_t offset, uint64_t limit, llkv_on_batch on_batch, void *user, uint64_t *total_rows) {
-  if (total_rows) *total_rows = 0;
-  // refusals: before any device work
-  if (!t || !on_batch) return set_error(LLKV_INVALID_ARGUMENT, "NULL argument: llkv_hip_scan_topn needs a table and an on_batch callback");
+// The refusals that need no device, in the order llkv_hip_scan_topn has always made them (`world`: the table's, so that the sharded
+// refusal keeps its place among them).
+int topn_refusals(const llkv_scan_options *options, uint32_t n_projections, const llkv_scan_order_term *order, uint32_t n_order, uint64_t offset, uint64_t limit,
+                  uint32_t world) {
   if (n_order && !order) return set_error(LLKV_INVALID_ARGUMENT, "NULL argument: " + std::to_string(n_order) + " ORDER BY terms without a term array");
   if (options && options->order_enabled)
     return set_error(LLKV_INVALID_ARGUMENT, "llkv_scan_options.order does not combine with the ORDER BY terms of llkv_hip_scan_topn: leave order_enabled 0");
   for (uint32_t j = 0; j < n_order; ++j)
     if (order[j].projection >= n_projections)
       return set_error(LLKV_INVALID_ARGUMENT, "ORDER BY position " + std::to_string((uint64_t)order[j].projection + 1) + " is out of bounds for " + std::to_string(n_projections) + " columns");
-  if (t->world > 1) return set_error(LLKV_UNSUPPORTED, "scan top-N over a sharded table (world " + std::to_string(t->world) + "): order each rank's rows and merge them in the binding");
+  if (world > 1) return set_error(LLKV_UNSUPPORTED, "scan top-N over a sharded table (world " + std::to_string(world) + "): order each rank's rows and merge them in the binding");
   if (n_order > (uint32_t)kMaxTerms) return set_error(LLKV_UNSUPPORTED, "scan top-N with " + std::to_string(n_order) + " ORDER BY terms: more than " + std::to_string(kMaxTerms) + " terms");
   if (limit > UINT64_MAX - offset || offset + limit > kGroupOrderDeviceRows)
     return set_error(LLKV_UNSUPPORTED, "scan top-N with offset + limit above " + std::to_string(kGroupOrderDeviceRows) + ": use llkv_hip_scan_stream");
+  return LLKV_OK;
+}
+
+int scan_topn(const Table *t, const llkv_projection *projections, uint32_t n_projections, const llkv_filter *filters, uint32_t n_filters,
+              const llkv_eval_op *ops, uint32_t n_ops, const llkv_scan_options *options, const llkv_scan_order_term *order, uint32_t n_order,
+              uint64_t offset, uint64_t limit, llkv_on_batch on_batch, void *user, uint64_t *total_rows) {
+  if (total_rows) *total_rows = 0;
+  // refusals: before any device work
+  if (!t || !on_batch) return set_error(LLKV_INVALID_ARGUMENT, "NULL argument: llkv_hip_scan_topn needs a table and an on_batch callback");
+  int rc = topn_refusals(options, n_projections, order, n_order, offset, limit, t->world);
+  if (rc) return rc;
   for (uint32_t i = 0; i < n_projections; ++i)
     if (projections[i].computed)
       return set_error(LLKV_UNSUPPORTED, "scan top-N with a computed projection (projection " + std::to_string(i) + "): its arithmetic errors in rows that are not returned must still fail the query");
-  int rc = ensure_device();
-  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
   LoweredPlan proj;
   std::string err;
   if ((rc = lower_projection(table_resolver(*t), projections, n_projections, &proj, &err))) return set_error(rc, err);
@@ -311,8 +319,17 @@ int scan_topn(const Table *t, const llkv_projection *projections, uint32_t n_pro
     for (uint32_t i = 0; i < n_projections; ++i) gathered.push_back(projections[i].field_id);
   Selection sel;
   if ((rc = run_selection(t, filters, n_filters, ops, n_ops, &sel, gathered.data(), (uint32_t)gathered.size()))) return rc;
+  if (total_rows) *total_rows = sel.n;
+  return topn_over_selection(t, proj, projections, options, order, n_order, offset, limit, sel, on_batch, user);
+}
+
+// Select, rank and gather over a selection in scan order (sel.d_ids: positions): rows [offset, offset + limit) of its order by the
+// terms, in one callback; none when no row is left.
+int topn_over_selection(const Table *t, const LoweredPlan &proj, const llkv_projection *projections, const llkv_scan_options *options,
+                        const llkv_scan_order_term *order, uint32_t n_order, uint64_t offset, uint64_t limit, const Selection &sel, llkv_on_batch on_batch, void *user) {
+  int rc;
+  std::string err;
   const uint64_t n = sel.n;
-  if (total_rows) *total_rows = n;
   if (n >= (1ull << 32)) return set_error(LLKV_UNSUPPORTED, "scan top-N over 2^32 selected rows or more");
   const uint64_t m = std::min<uint64_t>(offset + limit, n);
   if (m <= offset) return LLKV_OK; // nothing left: no batch

@@ -121,7 +121,7 @@ int run_selection_lowered(const Table *t, const LoweredPlan &plan, Selection *se
 
 // A table whose row ids are not its positions (llkv_hip_table_set_row_ids): the ids the callers REPORT — filter_row_ids, the row-id
 // column of scan windows — are the table's; translated in place from the device row indices, after any sort of the selection.
-static int selection_report_ids(const Table *t, Selection *sel) {
+int selection_report_ids(const Table *t, Selection *sel) {
   if (!t->d_row_ids || sel->n == 0) return LLKV_OK;
   HIP_TRY(hj_launch_gather_u64_by_row(t->d_row_ids.get<uint64_t>(), sel->d_dev, sel->n, sel->d_ids, g_ctx.stream));
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
@@ -130,7 +130,7 @@ static int selection_report_ids(const Table *t, Selection *sel) {
 
 // ScanStreamOptions.order: sort the selection by one column (sort_row_ids_with_order, llkv-scan/src/ordering.rs:16-140
 // → arrow sort_to_indices with {descending, nulls_first}); stable, so equal keys keep row-id order.
-static int sort_selection(const Table *t, const llkv_scan_options *o, Selection *sel) {
+int sort_selection(const Table *t, const llkv_scan_options *o, Selection *sel) {
   auto it = t->cols.find(o->order_field);
   if (it == t->cols.end()) return set_error(LLKV_NOT_FOUND, "ORDER BY field " + std::to_string(o->order_field) + " not found");
   const DeviceColumn &c = it->second;
@@ -238,6 +238,128 @@ llkv_status llkv_hip_filter_row_ids(const llkv_hip_table *table, const llkv_filt
   return LLKV_OK;
 }
 
+} // extern "C"
+
+namespace llkv {
+
+// The windows of rows [first, end) of a selection: gather + computed projections on the device, pinned host windows, one callback
+// per 65 536 rows on the calling thread, never an empty batch (what llkv_hip_scan_stream delivers of its whole selection and
+// llkv_hip_scan_distinct of its survivors).  sel.d_ids are what the batches report: translate them first (selection_report_ids).
+int deliver_windows(const Table *t, const LoweredPlan &proj, const Selection &sel, uint64_t first, uint64_t end, const llkv_scan_options *options,
+                    llkv_on_batch on_batch, void *user) {
+  if (end > sel.n) end = sel.n;
+  if (first >= end) return LLKV_OK;
+  int rc;
+  std::string err;
+  JitKernel k;
+  if ((rc = jit_compile(JitKind::Project, proj.type_string, &k, &err))) return set_error(rc, err);
+
+  hipStream_t stream = g_ctx.stream;
+  const uint32_t n_out = (uint32_t)proj.out_dtypes.size();
+  auto out_width = [&](uint32_t o) -> size_t { return proj.out_wide[o] ? 4 : dtype_out_width(proj.out_dtypes[o]); }; // (wide Utf8: u32 codes)
+  const bool with_ids = options && options->include_row_ids;
+  // Two buffers of up to kSuper reference windows each: one gather launch and one copy per output fill a buffer
+  // (65 536-row launches and 512 KB copies leave the PCIe link half idle), the host then hands out its windows
+  // one by one — same batches, same order — while the device fills the other buffer.
+  constexpr uint64_t kSuper = 16;
+  const uint64_t buf_rows = std::min<uint64_t>(kSuper * kRowStreamChunk, (end - first + kRowStreamChunk - 1) / kRowStreamChunk * kRowStreamChunk);
+  struct Win {
+    DeviceBuf d[kMaxOuts], d_valid[kMaxOuts], d_err; // d_err: one arithmetic-error cell per reference window of the buffer
+    PinnedBuf h[kMaxOuts], h_valid[kMaxOuts], h_ids, h_err;
+    hipEvent_t done = nullptr;
+    uint32_t n = 0;
+    ~Win() { if (done) (void)hipEventDestroy(done); }
+  } win[2];
+  // declared after the windows, so it runs before their buffers go back to the pools: on an early return the gather
+  // kernels and copies that are still in flight finish first
+  struct Drain {
+    hipStream_t s;
+    bool armed = true;
+    ~Drain() { if (armed) (void)hipStreamSynchronize(s); }
+  } drain{stream};
+  for (auto &w : win) {
+    if ((rc = w.d_err.alloc(kSuper * 4)) || (rc = w.h_err.alloc(kSuper * 4))) return rc;
+    for (uint32_t o = 0; o < n_out; ++o) {
+      const size_t bytes = (size_t)buf_rows * out_width(o);
+      if ((rc = w.d[o].alloc(bytes)) || (rc = w.h[o].alloc(bytes))) return rc;
+      if (proj.out_nullable[o] && ((rc = w.d_valid[o].alloc(buf_rows / 8)) || (rc = w.h_valid[o].alloc(buf_rows / 8)))) return rc;
+    }
+    if (with_ids && (rc = w.h_ids.alloc((size_t)buf_rows * 8))) return rc;
+    if (hipEventCreateWithFlags(&w.done, hipEventDisableTiming) != hipSuccess) return set_error(LLKV_INTERNAL, "event create failed");
+  }
+  ProjParams pp;
+  bind_plan(proj, *t, &pp);
+  pp.error_stride = (uint32_t)kRowStreamChunk;
+
+  auto enqueue = [&](uint64_t w0, Win &w) -> int {
+    w.n = (uint32_t)std::min<uint64_t>(buf_rows, end - w0);
+    ProjParams q = pp;
+    q.dev_rows = sel.d_dev + w0;
+    q.n = w.n;
+    for (uint32_t o = 0; o < n_out; ++o) { q.out[o] = w.d[o].p; q.out_valid[o] = (uint64_t *)w.d_valid[o].p; }
+    q.error_flag = (uint32_t *)w.d_err.p;
+    HIP_TRY(hipMemsetAsync(w.d_err.p, 0, kSuper * 4, stream));
+    int r = jit_launch_raw(k.fn, (w.n + kBlock - 1) / kBlock, &q, sizeof q, stream);
+    if (r) return r;
+    for (uint32_t o = 0; o < n_out; ++o)
+    {
+      HIP_TRY(hipMemcpyAsync(w.h[o].p, w.d[o].p, (size_t)w.n * out_width(o), hipMemcpyDeviceToHost, stream));
+      if (proj.out_nullable[o]) HIP_TRY(hipMemcpyAsync(w.h_valid[o].p, w.d_valid[o].p, (size_t)((w.n + 63) / 64) * 8, hipMemcpyDeviceToHost, stream));
+    }
+    if (with_ids) HIP_TRY(hipMemcpyAsync(w.h_ids.p, sel.d_ids + w0, (size_t)w.n * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(w.h_err.p, w.d_err.p, kSuper * 4, hipMemcpyDeviceToHost, stream)); // travels with the window
+    HIP_TRY(hipEventRecord(w.done, stream));
+    return LLKV_OK;
+  };
+
+  // dictionaries of passthrough Utf8 columns
+  std::vector<std::vector<const char *>> dicts(n_out);
+  for (uint32_t o = 0; o < n_out; ++o)
+    if (proj.out_dtypes[o] == LLKV_DT_UTF8 && proj.out_fields[o] >= 0)
+      for (auto &s : t->cols.at((uint32_t)proj.out_fields[o]).info.dictionary) dicts[o].push_back(s.c_str());
+
+  int cur = 0;
+  if ((rc = enqueue(first, win[0]))) return rc;
+  for (uint64_t w0 = first; w0 < end; w0 += buf_rows) {
+    const uint64_t next = w0 + buf_rows;
+    if (next < end && (rc = enqueue(next, win[cur ^ 1]))) return rc;
+    Win &w = win[cur];
+    if (hipEventSynchronize(w.done) != hipSuccess) return set_error(LLKV_INTERNAL, "window copy failed");
+    for (uint64_t r0 = 0; r0 < w.n; r0 += kRowStreamChunk) { // the reference's windows, one callback each
+      // a computed projection that failed in this window: the windows before it have been delivered, this one is not
+      // (the reference's arrow kernel fails the batch it is evaluating)
+      if (const uint32_t e = static_cast<const uint32_t *>(w.h_err.p)[r0 / kRowStreamChunk]) return set_error(LLKV_INTERNAL, arith_error_message(e));
+      llkv_column_view cols[kMaxOuts];
+      for (uint32_t o = 0; o < n_out; ++o) {
+        cols[o].dtype = proj.out_dtypes[o];
+        cols[o].values = (const char *)w.h[o].p + r0 * out_width(o);
+        cols[o].validity = proj.out_nullable[o] ? (const uint8_t *)w.h_valid[o].p + r0 / 8 : nullptr;
+        cols[o].dictionary = dicts[o].empty() ? nullptr : dicts[o].data();
+        cols[o].precision = cols[o].scale = 0;
+        if (proj.out_wide[o]) cols[o].precision = 4; // u32 codes of a wide Utf8 column
+        if (proj.out_dtypes[o] == LLKV_DT_DECIMAL128 && proj.out_fields[o] >= 0) {
+          const ColumnInfo &ci = t->cols.at((uint32_t)proj.out_fields[o]).info;
+          cols[o].precision = ci.precision;
+          cols[o].scale = ci.scale;
+        }
+      }
+      llkv_batch_view b;
+      b.num_rows = (uint32_t)std::min<uint64_t>(kRowStreamChunk, w.n - r0);
+      b.num_columns = n_out;
+      b.columns = cols;
+      b.row_ids = with_ids ? (const uint64_t *)w.h_ids.p + r0 : nullptr;
+      on_batch(&b, user); // calling thread, ascending row-id order
+    }
+    cur ^= 1;
+  }
+  drain.armed = false; // every window has been waited for
+  return LLKV_OK;
+}
+
+} // namespace llkv
+
+extern "C" {
+
 llkv_status llkv_hip_scan_stream(const llkv_hip_table *table, const llkv_projection *projections, uint32_t n_projections,
                                  const llkv_filter *filters, uint32_t n_filters, const llkv_eval_op *ops, uint32_t n_ops,
                                  const llkv_scan_options *options, llkv_on_batch on_batch, void *user) {
@@ -265,109 +387,7 @@ llkv_status llkv_hip_scan_stream(const llkv_hip_table *table, const llkv_project
   if (sel.n == 0) return LLKV_OK; // a filter that matches nothing yields no batch
   if (options && options->order_enabled && (rc = sort_selection(t, options, &sel))) return (llkv_status)rc;
   if (options && options->include_row_ids && (rc = selection_report_ids(t, &sel))) return (llkv_status)rc;
-  JitKernel k;
-  if ((rc = jit_compile(JitKind::Project, proj.type_string, &k, &err))) return (llkv_status)set_error(rc, err);
-
-  hipStream_t stream = g_ctx.stream;
-  const uint32_t n_out = (uint32_t)proj.out_dtypes.size();
-  auto out_width = [&](uint32_t o) -> size_t { return proj.out_wide[o] ? 4 : dtype_out_width(proj.out_dtypes[o]); }; // (wide Utf8: u32 codes)
-  const bool with_ids = options && options->include_row_ids;
-  // Two buffers of up to kSuper reference windows each: one gather launch and one copy per output fill a buffer
-  // (65 536-row launches and 512 KB copies leave the PCIe link half idle), the host then hands out its windows
-  // one by one — same batches, same order — while the device fills the other buffer.
-  constexpr uint64_t kSuper = 16;
-  const uint64_t buf_rows = std::min<uint64_t>(kSuper * kRowStreamChunk, (sel.n + kRowStreamChunk - 1) / kRowStreamChunk * kRowStreamChunk);
-  struct Win {
-    DeviceBuf d[kMaxOuts], d_valid[kMaxOuts], d_err; // d_err: one arithmetic-error cell per reference window of the buffer
-    PinnedBuf h[kMaxOuts], h_valid[kMaxOuts], h_ids, h_err;
-    hipEvent_t done = nullptr;
-    uint32_t n = 0;
-    ~Win() { if (done) (void)hipEventDestroy(done); }
-  } win[2];
-  // declared after the windows, so it runs before their buffers go back to the pools: on an early return the gather
-  // kernels and copies that are still in flight finish first
-  struct Drain {
-    hipStream_t s;
-    bool armed = true;
-    ~Drain() { if (armed) (void)hipStreamSynchronize(s); }
-  } drain{stream};
-  for (auto &w : win) {
-    if ((rc = w.d_err.alloc(kSuper * 4)) || (rc = w.h_err.alloc(kSuper * 4))) return (llkv_status)rc;
-    for (uint32_t o = 0; o < n_out; ++o) {
-      const size_t bytes = (size_t)buf_rows * out_width(o);
-      if ((rc = w.d[o].alloc(bytes)) || (rc = w.h[o].alloc(bytes))) return (llkv_status)rc;
-      if (proj.out_nullable[o] && ((rc = w.d_valid[o].alloc(buf_rows / 8)) || (rc = w.h_valid[o].alloc(buf_rows / 8)))) return (llkv_status)rc;
-    }
-    if (with_ids && (rc = w.h_ids.alloc((size_t)buf_rows * 8))) return (llkv_status)rc;
-    if (hipEventCreateWithFlags(&w.done, hipEventDisableTiming) != hipSuccess) return (llkv_status)set_error(LLKV_INTERNAL, "event create failed");
-  }
-  ProjParams pp;
-  bind_plan(proj, *t, &pp);
-  pp.error_stride = (uint32_t)kRowStreamChunk;
-
-  auto enqueue = [&](uint64_t w0, Win &w) -> int {
-    w.n = (uint32_t)std::min<uint64_t>(buf_rows, sel.n - w0);
-    ProjParams q = pp;
-    q.dev_rows = sel.d_dev + w0;
-    q.n = w.n;
-    for (uint32_t o = 0; o < n_out; ++o) { q.out[o] = w.d[o].p; q.out_valid[o] = (uint64_t *)w.d_valid[o].p; }
-    q.error_flag = (uint32_t *)w.d_err.p;
-    HIP_TRY(hipMemsetAsync(w.d_err.p, 0, kSuper * 4, stream));
-    int r = jit_launch_raw(k.fn, (w.n + kBlock - 1) / kBlock, &q, sizeof q, stream);
-    if (r) return r;
-    for (uint32_t o = 0; o < n_out; ++o)
-    {
-      HIP_TRY(hipMemcpyAsync(w.h[o].p, w.d[o].p, (size_t)w.n * out_width(o), hipMemcpyDeviceToHost, stream));
-      if (proj.out_nullable[o]) HIP_TRY(hipMemcpyAsync(w.h_valid[o].p, w.d_valid[o].p, (size_t)((w.n + 63) / 64) * 8, hipMemcpyDeviceToHost, stream));
-    }
-    if (with_ids) HIP_TRY(hipMemcpyAsync(w.h_ids.p, sel.d_ids + w0, (size_t)w.n * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(w.h_err.p, w.d_err.p, kSuper * 4, hipMemcpyDeviceToHost, stream)); // travels with the window
-    HIP_TRY(hipEventRecord(w.done, stream));
-    return LLKV_OK;
-  };
-
-  // dictionaries of passthrough Utf8 columns
-  std::vector<std::vector<const char *>> dicts(n_out);
-  for (uint32_t o = 0; o < n_out; ++o)
-    if (proj.out_dtypes[o] == LLKV_DT_UTF8 && proj.out_fields[o] >= 0)
-      for (auto &s : t->cols.at((uint32_t)proj.out_fields[o]).info.dictionary) dicts[o].push_back(s.c_str());
-
-  int cur = 0;
-  if ((rc = enqueue(0, win[0]))) return (llkv_status)rc;
-  for (uint64_t w0 = 0; w0 < sel.n; w0 += buf_rows) {
-    const uint64_t next = w0 + buf_rows;
-    if (next < sel.n && (rc = enqueue(next, win[cur ^ 1]))) return (llkv_status)rc;
-    Win &w = win[cur];
-    if (hipEventSynchronize(w.done) != hipSuccess) return (llkv_status)set_error(LLKV_INTERNAL, "window copy failed");
-    for (uint64_t r0 = 0; r0 < w.n; r0 += kRowStreamChunk) { // the reference's windows, one callback each
-      // a computed projection that failed in this window: the windows before it have been delivered, this one is not
-      // (the reference's arrow kernel fails the batch it is evaluating)
-      if (const uint32_t e = static_cast<const uint32_t *>(w.h_err.p)[r0 / kRowStreamChunk]) return (llkv_status)set_error(LLKV_INTERNAL, arith_error_message(e));
-      llkv_column_view cols[kMaxOuts];
-      for (uint32_t o = 0; o < n_out; ++o) {
-        cols[o].dtype = proj.out_dtypes[o];
-        cols[o].values = (const char *)w.h[o].p + r0 * out_width(o);
-        cols[o].validity = proj.out_nullable[o] ? (const uint8_t *)w.h_valid[o].p + r0 / 8 : nullptr;
-        cols[o].dictionary = dicts[o].empty() ? nullptr : dicts[o].data();
-        cols[o].precision = cols[o].scale = 0;
-        if (proj.out_wide[o]) cols[o].precision = 4; // u32 codes of a wide Utf8 column
-        if (proj.out_dtypes[o] == LLKV_DT_DECIMAL128 && proj.out_fields[o] >= 0) {
-          const ColumnInfo &ci = t->cols.at((uint32_t)proj.out_fields[o]).info;
-          cols[o].precision = ci.precision;
-          cols[o].scale = ci.scale;
-        }
-      }
-      llkv_batch_view b;
-      b.num_rows = (uint32_t)std::min<uint64_t>(kRowStreamChunk, w.n - r0);
-      b.num_columns = n_out;
-      b.columns = cols;
-      b.row_ids = with_ids ? (const uint64_t *)w.h_ids.p + r0 : nullptr;
-      on_batch(&b, user); // calling thread, ascending row-id order
-    }
-    cur ^= 1;
-  }
-  drain.armed = false; // every window has been waited for
-  return LLKV_OK;
+  return (llkv_status)deliver_windows(t, proj, sel, 0, sel.n, options, on_batch, user);
 }
 
 llkv_status llkv_hip_join_stream(const llkv_hip_table *left, const llkv_hip_table *right, const llkv_join_key *keys,

@@ -962,6 +962,46 @@ def scan_topn(table: HipTable, projections, predicate, order, offset: int = 0, l
     return got[0][0], got[0][1], total.value
 
 
+def scan_distinct(table: HipTable, projections, predicate, order=(), offset: int = 0, limit: Optional[int] = None, include_nulls: bool = False,
+                  include_row_ids: bool = False, scan_order=None, consume=None):
+    """llkv_hip_scan_distinct: the first occurrence of every distinct row of ``scan_stream(projections, predicate,
+    order=scan_order)``, then ORDER BY ``order`` — terms ``(position in projections, descending, nulls_first)`` — and
+    OFFSET / LIMIT, all on the device.  Returns ``(batches, selected_rows, distinct_rows)``: the batches as scan_stream
+    returns them, the rows before DISTINCT and the rows after it (before OFFSET / LIMIT).  ``consume``: called with every
+    raw ``llkv_batch_view`` instead (buffers valid during the call only); the batches are then None."""
+    projs = (abi.CProjection * max(1, len(projections)))()
+    keep: list = []
+    for i, pr in enumerate(projections):
+        if isinstance(pr, int):
+            projs[i].computed, projs[i].field_id = 0, pr
+        else:
+            arr = pr.to_c(keep)
+            projs[i].computed, projs[i].expr, projs[i].expr_len = 1, arr, len(pr.tokens)
+    terms = (abi.CScanOrderTerm * max(1, len(order)))()
+    for i, o in enumerate(order):
+        terms[i].projection, terms[i].descending = o[0], int(o[1]) if len(o) > 1 else 0
+        terms[i].nulls_first = int(o[2]) if len(o) > 2 else 0
+    p = CPlan(predicate)
+    opts = abi.scan_options(include_nulls, include_row_ids, scan_order)
+    batches: list = []
+
+    def on_batch(bp, _user):
+        b = bp.contents
+        if consume is not None:
+            consume(b)
+            return
+        n = int(b.num_rows)
+        cols = [decode_view_column(b.columns[ci], n) for ci in range(b.num_columns)]
+        batches.append((cols, np.frombuffer(C.string_at(b.row_ids, n * 8), dtype=np.uint64).tolist() if b.row_ids else None))
+
+    cb = abi.ON_BATCH(on_batch)
+    selected, distinct = C.c_uint64(), C.c_uint64()
+    check(lib().llkv_hip_scan_distinct(table.handle, projs, C.c_uint32(len(projections)), p.filters, p.n_filters, p.ops, p.n_ops, C.byref(opts),
+                                       terms, C.c_uint32(len(order)), C.c_uint64(offset), C.c_uint64(2**64 - 1 if limit is None else limit),
+                                       cb, None, C.byref(selected), C.byref(distinct)))
+    return (None if consume is not None else batches), selected.value, distinct.value
+
+
 def join_stream(left: HipTable, right: HipTable, keys, join_type: int = abi.JOIN_INNER, batch_size: int = 8192, consume=None, key_rules: int = 0):
     """TableJoinExt::join_stream (llkv-join/src/lib.rs:240-282): list of batches (left_rows, right_rows|None);
     a right row of 2**64-1 is the NULL padding of a LEFT join.  ``consume(n_pairs)``: called per batch instead
