@@ -912,6 +912,58 @@ llkv_status llkv_hip_scan_distinct(const llkv_hip_table *table, const llkv_proje
                                    uint64_t *selected_rows /* may be NULL: rows before DISTINCT */,
                                    uint64_t *distinct_rows /* may be NULL: rows after DISTINCT, before OFFSET / LIMIT */);
 
+/* UNION / INTERSECT / EXCEPT (the DISTINCT quantifier) over two projection scans, combined in HBM (execute_compound_select,
+ * llkv-executor/src/lib.rs:565-695: ensure_distinct_rows over the left rows, then one arm per operator over encode_row
+ * :9255-9312; ensure_schema_compatibility :9221-9237).  UNION ALL is not offered: it is two llkv_hip_scan_stream calls.
+ * The rows of a side are exactly those of llkv_hip_scan_stream with that side's projections and filter and
+ * options->include_nulls (which holds for both sides), in its order.  The two sides may be the same table.
+ * Two rows are equal iff encode_row gives the same bytes.  Per column: NULL equals NULL and nothing else; Int64 and Date32 by
+ * value; Boolean as 0 / 1 (plan_value_from_array, llkv-plan/src/plans.rs:1131-1197); Decimal128 by raw value (the scale is the
+ * column's, and the schema check makes it the same on both sides); Utf8 by bytes, whatever the two dictionaries; Float64 BY ITS
+ * BITS — −0.0 and +0.0 are different rows, two NaNs of different sign or payload too, two NaNs of the same bits are the same
+ * row.  This is not the equality of llkv_hip_scan_distinct (CanonicalRow), as in the reference.
+ * All three operators first reduce the left side to its first occurrences.  UNION: these, in left scan order, then the first
+ * occurrence of every right row that equals no left row and no earlier right row, in right scan order.  INTERSECT: the left
+ * first occurrences that equal some right row, in left order (an empty right side: an empty result).  EXCEPT: those that
+ * equal no right row, in left order.  Every delivered row carries its own cells, bit for bit.
+ * Errors, in the order the reference meets them: (1) the left side is selected — with at least one row and a projected
+ * Int32 / UInt32 / UInt64 / Float32 column: LLKV_INVALID_ARGUMENT "unsupported data type in INSERT SELECT: Int32" (…);
+ * (2) whatever the row counts: LLKV_INVALID_ARGUMENT "compound SELECT requires matching column counts", then "compound SELECT
+ * column type mismatch: Int64 vs Float64" (names as arrow prints them, "Decimal128(15, 2)": precision and scale take part,
+ * nullability does not); (3) the right side's unsupported type, if it has at least one row.
+ * n_order = 0: rows [offset, offset + limit) of the result in dense windows of 65 536 rows, one callback each, none when
+ * nothing is left.  A UNION delivers its left part with the left table's views and dictionaries, then its right part with
+ * the right table's: no batch mixes sides, and only the concatenation is promised.
+ * n_order > 0 (INTERSECT / EXCEPT: the survivors are rows of the left table): ordered and cut by the select, rank and gather
+ * of llkv_hip_scan_topn, under its rules and messages — positions into the left projections, ties keep first-occurrence
+ * order, offset + limit <= 1024, at most 8 terms; one callback.
+ * Refused before any device work, the message naming the cause.  LLKV_INVALID_ARGUMENT: a NULL side, table or on_batch; an op
+ * outside llkv_set_op; options->include_row_ids (a compound row is not a table row); options->order_enabled.
+ * LLKV_UNSUPPORTED: a computed projection; a sharded table; a projected Decimal128 column staged beyond 64 bits; 2^31
+ * selected rows or more on a side; UNION with ORDER BY terms (its survivors live in two tables: a binding sorts the
+ * unordered result).  A chain of more than one operation is the binding's: this call combines two scans.
+ * *left_rows / *right_rows: the selected rows of each side; *result_rows: the rows of the result before OFFSET / LIMIT
+ * (all may be NULL).                                                                                                    */
+typedef enum llkv_set_op { LLKV_SET_UNION = 0, LLKV_SET_INTERSECT = 1, LLKV_SET_EXCEPT = 2 } llkv_set_op; /* the DISTINCT quantifier */
+
+typedef struct llkv_scan_side {
+  const llkv_hip_table *table;
+  const llkv_projection *projections;
+  uint32_t n_projections;
+  const llkv_filter *filters;
+  uint32_t n_filters;
+  const llkv_eval_op *ops;
+  uint32_t n_ops;
+} llkv_scan_side;
+
+llkv_status llkv_hip_scan_setop(const llkv_scan_side *left, const llkv_scan_side *right, int32_t op /* llkv_set_op */,
+                                const llkv_scan_options *options, /* include_nulls, for both sides */
+                                const llkv_scan_order_term *order, uint32_t n_order,
+                                uint64_t offset, uint64_t limit /* UINT64_MAX: none */,
+                                llkv_on_batch on_batch, void *user,
+                                uint64_t *left_rows, uint64_t *right_rows /* selected rows of each side; may be NULL */,
+                                uint64_t *result_rows /* rows of the result before OFFSET / LIMIT; may be NULL */);
+
 /* ------------------------------------------------------------------------- */
 /* Hash join — `TableJoinExt::join_stream` llkv-join/src/lib.rs:240-282.        */
 /* Build = right, probe = left; output = matching (left row, right row) index  */

@@ -123,6 +123,15 @@ class CScanOrderTerm(C.Structure):
     _fields_ = [("projection", C.c_uint32), ("descending", C.c_int32), ("nulls_first", C.c_int32)]
 
 
+SET_UNION, SET_INTERSECT, SET_EXCEPT = range(3)  # llkv_set_op (the DISTINCT quantifier)
+
+
+class CScanSide(C.Structure):
+    """llkv_scan_side: one projection scan of llkv_hip_scan_setop — a table, its projections and its filter."""
+    _fields_ = [("table", C.c_void_p), ("projections", C.POINTER(CProjection)), ("n_projections", C.c_uint32),
+                ("filters", C.POINTER(CFilter)), ("n_filters", C.c_uint32), ("ops", C.POINTER(CEvalOp)), ("n_ops", C.c_uint32)]
+
+
 # llkv_hip_table_append_utf8_column_ex: more than 256 distinct strings may be staged, as u32 codes in byte order of the strings;
 # views of such a column carry precision 4 (values are uint32 codes)
 UTF8_WIDE_CODES = 1

@@ -1002,6 +1002,56 @@ def scan_distinct(table: HipTable, projections, predicate, order=(), offset: int
     return (None if consume is not None else batches), selected.value, distinct.value
 
 
+def scan_setop(left, right, op: int, order=(), offset: int = 0, limit: Optional[int] = None, include_nulls: bool = False, consume=None,
+               include_row_ids: bool = False, scan_order=None):
+    """llkv_hip_scan_setop: ``left`` UNION / INTERSECT / EXCEPT ``right`` (``abi.SET_*``, the DISTINCT quantifier) on the
+    device.  Each side is ``(table, projections, predicate)`` — the rows of ``scan_stream(table, projections, predicate,
+    include_nulls)`` — or None (a NULL side, which the call refuses).  ``order``: terms ``(position in the left projections,
+    descending, nulls_first)`` for INTERSECT / EXCEPT.  Returns ``(batches, left_rows, right_rows, result_rows)``: the batches
+    as scan_stream returns them (a UNION's left part, then its right part), the selected rows of each side and the rows of the
+    result before OFFSET / LIMIT.  ``consume``: called with every raw ``llkv_batch_view`` instead (buffers valid during the
+    call only); the batches are then None.  ``include_row_ids`` / ``scan_order`` only set the option fields the call refuses."""
+    keep: list = []
+
+    def side(s):
+        if s is None:
+            return None
+        table, projections, predicate = s
+        projs = (abi.CProjection * max(1, len(projections)))()
+        for i, pr in enumerate(projections):
+            if isinstance(pr, int):
+                projs[i].computed, projs[i].field_id = 0, pr
+            else:
+                arr = pr.to_c(keep)
+                projs[i].computed, projs[i].expr, projs[i].expr_len = 1, arr, len(pr.tokens)
+        p = CPlan(predicate)
+        keep.extend([projs, p])
+        return abi.CScanSide(table.handle if table is not None else None, projs, len(projections), p.filters, p.n_filters, p.ops, p.n_ops)
+
+    l, r = side(left), side(right)
+    terms = (abi.CScanOrderTerm * max(1, len(order)))()
+    for i, o in enumerate(order):
+        terms[i].projection, terms[i].descending = o[0], int(o[1]) if len(o) > 1 else 0
+        terms[i].nulls_first = int(o[2]) if len(o) > 2 else 0
+    opts = abi.scan_options(include_nulls, include_row_ids, scan_order)
+    batches: list = []
+
+    def on_batch(bp, _user):
+        b = bp.contents
+        if consume is not None:
+            consume(b)
+            return
+        n = int(b.num_rows)
+        batches.append(([decode_view_column(b.columns[ci], n) for ci in range(b.num_columns)], None))
+
+    cb = abi.ON_BATCH(on_batch)
+    n_left, n_right, n_result = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(lib().llkv_hip_scan_setop(C.byref(l) if l is not None else None, C.byref(r) if r is not None else None, C.c_int32(op), C.byref(opts),
+                                    terms, C.c_uint32(len(order)), C.c_uint64(offset), C.c_uint64(2**64 - 1 if limit is None else limit),
+                                    cb, None, C.byref(n_left), C.byref(n_right), C.byref(n_result)))
+    return (None if consume is not None else batches), n_left.value, n_right.value, n_result.value
+
+
 def join_stream(left: HipTable, right: HipTable, keys, join_type: int = abi.JOIN_INNER, batch_size: int = 8192, consume=None, key_rules: int = 0):
     """TableJoinExt::join_stream (llkv-join/src/lib.rs:240-282): list of batches (left_rows, right_rows|None);
     a right row of 2**64-1 is the NULL padding of a LEFT join.  ``consume(n_pairs)``: called per batch instead
