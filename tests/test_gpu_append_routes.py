@@ -2,6 +2,7 @@
 not reach.  Every case builds three tables over the same rows — `grown` (staged with the first chunks, then appended to once or
 twice), `whole` (staged in one go with the SAME chunk list) and the oracle's — and asks: the oracle's answer (exact for ids, keys,
 integers and order; assert_values for f64), and `grown` equal to `whole` bit for bit (same tiles over the same chunk list).
+(scan_topn, scan_distinct and scan_setop over a grown table, in the same form: tests/test_gpu_scan_append.py.)
 
 A. Row ids and scans over ragged layouts — test_row_ids_and_scans_over_ragged_grown_tables
    compute_layout starts every chunk on a 16-row boundary of the device image, so behind the first chunk whose row count is not
