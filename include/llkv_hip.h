@@ -189,18 +189,74 @@ typedef struct llkv_eval_op {
 /* Scalar expressions in postfix form — the token program of                  */
 /* llkv-compute/src/fast_numeric.rs:19-37 (`Token::{Column,Literal,Binary}`).  */
 /* ------------------------------------------------------------------------- */
+/* Conditional expressions — ScalarExpr::{Compare, Not, IsNull, Cast, Case, Coalesce} and the logical And / Or, as the
+ * GROUP BY of the reference evaluates them row by row (evaluate_expr_with_plan_value_aggregates_and_row
+ * llkv-executor/src/lib.rs:7008-7632).  The kinds from LLKV_TOK_COMPARE on, and LLKV_BIN_AND / LLKV_BIN_OR, are served in the
+ * aggregate arguments of llkv_hip_query_prepare_groupby only (not DISTINCT ones); every other call that takes a token program
+ * answers LLKV_UNSUPPORTED.  llkv_hip_scalar_eval_planvalue is the host evaluator of the same rules over one row of cells.
+ *
+ *   kind               pops → pushes         fields
+ *   LLKV_TOK_COMPARE   left, right → 1       binop = llkv_compare_op
+ *   LLKV_TOK_NOT       1 → 1
+ *   LLKV_TOK_IS_NULL   1 → 1                 binop = negated (0 / 1)
+ *   LLKV_TOK_CAST      1 → 1                 binop = target llkv_dtype
+ *   LLKV_TOK_COALESCE  n → 1                 field_id = n >= 1, items in push order
+ *   LLKV_TOK_CASE      see below → 1         field_id = number of WHEN / THEN pairs >= 1; binop bit 0: an operand is present
+ *                                            (simple CASE), bit 1: an ELSE is present; push order
+ *                                            [operand] when1 then1 … whenN thenN [else]
+ *
+ * A program has at most LLKV_COND_MAX_TOKENS tokens, a CASE at most LLKV_COND_MAX_WHENS pairs, a COALESCE at most
+ * LLKV_COND_MAX_ITEMS items (beyond: LLKV_UNSUPPORTED).  Stack underflow, more than one value left, n = 0, an unknown kind or
+ * compare op: LLKV_INVALID_ARGUMENT, the message names the token index.
+ *
+ * Values are Null, Integer (i64), Float (f64) and — as COMPARE sides, simple-CASE operand / candidates and under IS NULL only —
+ * String and Date32.  Inside such a program the literals LLKV_LIT_NULL, LLKV_LIT_BOOLEAN (Integer 0 / 1), LLKV_LIT_STRING and
+ * LLKV_LIT_DATE32 are legal under these rules:
+ *   COMPARE   either side Null → Null.  Integer against Float: the integer `as f64`.  Int / Int, Float / Float, String / String by
+ *             the native operators (a NaN operand: every operator false but !=; strings by bytes).  EVERY other pairing of two
+ *             non-Null values — Date32 against Date32 too — is Integer 0.  The result is Integer 0 / 1.
+ *   NOT       Integer / Float → Integer (v != 0 ? 0 : 1), Null → Null; other classes are refused.
+ *   IS NULL   Integer 0 / 1, any operand class.
+ *   AND / OR  (LLKV_TOK_BINARY with LLKV_BIN_AND / LLKV_BIN_OR) three-valued over the truth of Integer != 0 / Float != 0.0, Null
+ *             unknown; Integer 0 / 1 or Null; other classes are refused.
+ *   CAST      Null → Null.  To Int64 / Int32 (not narrowed): Integer as is, Float by the saturating `as i64` (NaN → 0).  To
+ *             Float64 / Float32 (not narrowed): Integer `as f64`, Float as is.  Other targets / sources are refused.
+ *   CASE      searched: a WHEN is true iff Integer != 0 or Float != 0.0 (a NaN is true), Null is false; the first true branch's
+ *             THEN, else the ELSE, else Null.  Simple: operand == candidate as COMPARE's EQ decides it (a Null on either side
+ *             never matches); Date32 operands are refused.
+ *   COALESCE  the first non-Null item.
+ *   leaves    numeric columns as plain arithmetic arguments admit them.  A Utf8 column (1-byte codes; a wide one is refused)
+ *             against a String literal in COMPARE / simple CASE — all six operators, whatever the dictionary order — or under
+ *             IS NULL.  A Date32 column or literal: a COMPARE side or under IS NULL.  Decimal128 columns / literals anywhere in a
+ *             program with a conditional token: LLKV_UNSUPPORTED.
+ * A group's temp column is typed by its first non-NULL value, so the value branches of every CASE (THENs and ELSE) and the items
+ * of every COALESCE must be all Integer or all Float (NULL literals beside them are fine; only NULL literals are not): otherwise
+ * LLKV_UNSUPPORTED — write `ELSE 0.0`. */
 typedef enum llkv_token_kind {
   LLKV_TOK_COLUMN = 1,
   LLKV_TOK_LITERAL = 2,
-  LLKV_TOK_BINARY = 3
+  LLKV_TOK_BINARY = 3,
+  LLKV_TOK_COMPARE = 4,
+  LLKV_TOK_NOT = 5,
+  LLKV_TOK_IS_NULL = 6,
+  LLKV_TOK_CAST = 7,
+  LLKV_TOK_COALESCE = 8,
+  LLKV_TOK_CASE = 9
 } llkv_token_kind;
+#define LLKV_COND_MAX_TOKENS 64
+#define LLKV_COND_MAX_WHENS 8
+#define LLKV_COND_MAX_ITEMS 8
+#define LLKV_CASE_HAS_OPERAND 1
+#define LLKV_CASE_HAS_ELSE 2
 
 typedef enum llkv_binary_op {
   LLKV_BIN_ADD = 1,
   LLKV_BIN_SUB = 2,
   LLKV_BIN_MUL = 3,
   LLKV_BIN_DIV = 4,
-  LLKV_BIN_MOD = 5
+  LLKV_BIN_MOD = 5,
+  LLKV_BIN_AND = 6, /* conditional programs only (see above) */
+  LLKV_BIN_OR = 7
 } llkv_binary_op;
 
 typedef struct llkv_expr_token {
@@ -717,6 +773,14 @@ llkv_status llkv_hip_query_set_having_ex(llkv_hip_query *query, const llkv_havin
 llkv_status llkv_hip_having_eval_ex(const llkv_having_node *nodes, uint32_t n_nodes, const llkv_having_expr *exprs,
                                     uint32_t n_exprs, const llkv_value *key_cells, const int32_t *key_dtypes, uint32_t n_keys,
                                     const llkv_value *agg_cells, uint32_t n_aggs, int32_t *truth);
+/* The PlanValue rules of a GROUP BY aggregate argument (conditional expressions included: the block next to llkv_token_kind)
+ * over ONE row, host only, no device needed — the counterpart of llkv_hip_having_eval for bindings and CPU tests.  Column
+ * `field_ids[k]` has the cell `cells[k]`: its dtype is the COLUMN's (LLKV_DT_INT64 / INT32 / UINT32 cells carry i64,
+ * LLKV_DT_FLOAT64 / FLOAT32 f64, LLKV_DT_UTF8 str, LLKV_DT_DATE32 days in i64), is_null marks a NULL cell.  The call makes the
+ * static refusals of the lowering that do not depend on column statistics (same statuses and messages).  *out: Null (is_null,
+ * dtype LLKV_DT_INT64), Integer (LLKV_DT_INT64) or Float (LLKV_DT_FLOAT64).                                               */
+llkv_status llkv_hip_scalar_eval_planvalue(const llkv_expr_token *expr, uint32_t expr_len, const uint32_t *field_ids,
+                                           const llkv_value *cells, uint32_t n_cells, llkv_value *out);
 /* Status a finalize step produced for one aggregate (e.g. "integer overflow"
  * is LLKV_INVALID_ARGUMENT, llkv-aggregate/src/lib.rs:816-829).              */
 

@@ -56,8 +56,10 @@ OP_EQUALS, OP_RANGE, OP_GT, OP_GE, OP_LT, OP_LE, OP_IN, OP_IS_NULL, OP_IS_NOT_NU
 CMP_EQ, CMP_NOT_EQ, CMP_LT, CMP_LT_EQ, CMP_GT, CMP_GT_EQ = range(1, 7)
 BOUND_UNBOUNDED, BOUND_INCLUDED, BOUND_EXCLUDED = range(3)
 EVAL_PUSH_PREDICATE, EVAL_PUSH_LITERAL, EVAL_AND, EVAL_OR, EVAL_NOT = range(1, 6)
-TOK_COLUMN, TOK_LITERAL, TOK_BINARY = range(1, 4)
-BIN_ADD, BIN_SUB, BIN_MUL, BIN_DIV, BIN_MOD = range(1, 6)
+TOK_COLUMN, TOK_LITERAL, TOK_BINARY, TOK_COMPARE, TOK_NOT, TOK_IS_NULL, TOK_CAST, TOK_COALESCE, TOK_CASE = range(1, 10)
+BIN_ADD, BIN_SUB, BIN_MUL, BIN_DIV, BIN_MOD, BIN_AND, BIN_OR = range(1, 8)
+COND_MAX_TOKENS, COND_MAX_WHENS, COND_MAX_ITEMS = 64, 8, 8  # LLKV_COND_MAX_*
+CASE_HAS_OPERAND, CASE_HAS_ELSE = 1, 2
 AGG_COUNT_STAR, AGG_COUNT, AGG_SUM, AGG_TOTAL, AGG_AVG, AGG_MIN, AGG_MAX, AGG_COUNT_NULLS = range(1, 9)
 JOIN_INNER, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL, JOIN_SEMI, JOIN_ANTI = range(6)
 JOIN_KEYS_TABLE, JOIN_KEYS_EXECUTOR = 0, 1  # llkv_join_key_rules
@@ -719,10 +721,52 @@ def compile_predicate(expr: Optional[Expr]) -> Tuple[List[Filter], List[Tuple[in
 
 # --------------------------------------------------------------------- scalar exprs
 class ScalarExpr:
-    """llkv_expr::ScalarExpr restricted to Column / Literal / Binary, held in postfix form."""
+    """llkv_expr::ScalarExpr — Column / Literal / Binary and, for GROUP BY aggregate arguments, Compare / Not / IsNull / Cast /
+    Coalesce / Case and the logical And / Or — held in postfix form.  A token is (tag, a[, b]): ("col", field), ("lit", Literal),
+    ("bin", op), ("cmp", op), ("not",), ("isnull", negated), ("cast", dtype), ("coalesce", n), ("case", n_whens, flags)."""
 
     def __init__(self, tokens):
         self.tokens = list(tokens)
+
+    @staticmethod
+    def compare(left, op: int, right) -> "ScalarExpr":
+        return ScalarExpr(_scalar(left).tokens + _scalar(right).tokens + [("cmp", op)])
+
+    @staticmethod
+    def not_(x) -> "ScalarExpr":
+        return ScalarExpr(_scalar(x).tokens + [("not",)])
+
+    @staticmethod
+    def is_null(x, negated: bool = False) -> "ScalarExpr":
+        return ScalarExpr(_scalar(x).tokens + [("isnull", int(bool(negated)))])
+
+    @staticmethod
+    def cast(x, dtype: int) -> "ScalarExpr":
+        return ScalarExpr(_scalar(x).tokens + [("cast", dtype)])
+
+    @staticmethod
+    def coalesce(*items) -> "ScalarExpr":
+        return ScalarExpr([t for it in items for t in _scalar(it).tokens] + [("coalesce", len(items))])
+
+    @staticmethod
+    def case(branches, else_=None, operand=None, has_else: Optional[bool] = None) -> "ScalarExpr":
+        """``branches``: (when, then) pairs; ``operand``: the simple form (CASE operand WHEN candidate THEN …).  ``else_=None``
+        is "no ELSE" unless ``has_else`` says the ELSE is the NULL literal."""
+        has_else = (else_ is not None) if has_else is None else has_else
+        toks = list(_scalar(operand).tokens) if operand is not None else []
+        for when, then in branches:
+            toks += _scalar(when).tokens + _scalar(then).tokens
+        if has_else:
+            toks += _scalar(else_).tokens
+        return ScalarExpr(toks + [("case", len(branches), (CASE_HAS_OPERAND if operand is not None else 0) | (CASE_HAS_ELSE if has_else else 0))])
+
+    @staticmethod
+    def and_(left, right) -> "ScalarExpr":
+        return ScalarExpr.binary(left, BIN_AND, right)
+
+    @staticmethod
+    def or_(left, right) -> "ScalarExpr":
+        return ScalarExpr.binary(left, BIN_OR, right)
 
     @staticmethod
     def column(field_id: int) -> "ScalarExpr":
@@ -769,8 +813,22 @@ class ScalarExpr:
             elif t[0] == "lit":
                 arr[i].kind = TOK_LITERAL
                 arr[i].literal = t[1].to_c(keep)
-            else:
+            elif t[0] == "bin":
                 arr[i].kind, arr[i].binop = TOK_BINARY, t[1]
+            elif t[0] == "cmp":
+                arr[i].kind, arr[i].binop = TOK_COMPARE, t[1]
+            elif t[0] == "not":
+                arr[i].kind = TOK_NOT
+            elif t[0] == "isnull":
+                arr[i].kind, arr[i].binop = TOK_IS_NULL, t[1]
+            elif t[0] == "cast":
+                arr[i].kind, arr[i].binop = TOK_CAST, t[1]
+            elif t[0] == "coalesce":
+                arr[i].kind, arr[i].field_id = TOK_COALESCE, t[1]
+            elif t[0] == "case":
+                arr[i].kind, arr[i].field_id, arr[i].binop = TOK_CASE, t[1], t[2]
+            else:
+                raise ValueError(f"unknown scalar token {t!r}")
         keep.append(arr)
         return arr
 

@@ -31,6 +31,7 @@
 #endif
 
 #include "scan_params.h"
+#include "planvalue_rules.h"
 
 namespace llkv {
 
@@ -510,6 +511,107 @@ template <class L, class R> struct DivIntPV {
   static __device__ __forceinline__ int64_t eval(Ctx &c, int j) {
     const int64_t a = (int64_t)L::eval(c, j), b = (int64_t)R::eval(c, j);
     return b == 0 ? 0 : b == -1 ? (int64_t)(0ull - (uint64_t)a) : a / b;
+  }
+};
+// --------------------------------------------------------------------------
+// Conditional PlanValue nodes (ScalarExpr::{Compare, Not, IsNull, Cast, Case, Coalesce}, logical And / Or inside GROUP BY
+// aggregate arguments, llkv-executor/src/lib.rs:7008-7632).  What a value is comes from planvalue_rules.h, shared with the host
+// evaluator; a node adds only which of its operands' values and validities go in.  Booleans are Integer 0 / 1 (Type I64).
+// EVERY operand and EVERY branch is evaluated for every row and the result is picked with selects: the program is the type,
+// there is no per-row token loop and no per-lane branch.  The reference evaluates only the branch it takes, and the difference
+// is unobservable BECAUSE NO PlanValue NODE WRITES Ctx::err (BinViaF64, DivPV, DivIntPV, DecBin, DecDiv, the f64 Bin and the
+// nodes below raise nothing: PlanValue arithmetic saturates, and x / 0 is NULL) — a node that raised an error from a branch not
+// taken would fail queries the reference answers.  Keep to it: a new PlanValue node carries NULL as validity, never as an error.
+// Validity is a boolean of its own next to the value, as in Div / DivPV.
+// --------------------------------------------------------------------------
+template <class Ty> struct NullPV { // the NULL literal, typed by where it stands (a CASE branch among Floats is a Float NULL)
+  using Type = Ty;
+  static __device__ __forceinline__ typename Ty::T eval(Ctx &, int) { return (typename Ty::T)0; }
+  static __device__ __forceinline__ bool valid(Ctx &, int) { return false; }
+};
+template <class E> __device__ __forceinline__ auto pv_value(Ctx &c, int j) { // a numeric node's value in its class: i64 or f64
+  if constexpr (E::Type::is_float) return (double)E::eval(c, j);
+  else return (int64_t)E::eval(c, j);
+}
+// COMPARE; OP = llkv_compare_op, 0: a pairing of classes that does not compare by value — Integer 0 where both sides are non-NULL
+template <int OP, class L, class R> struct CmpPV {
+  using Type = I64;
+  static __device__ __forceinline__ bool valid(Ctx &c, int j) { return L::valid(c, j) & R::valid(c, j); }
+  static __device__ __forceinline__ int64_t eval(Ctx &c, int j) {
+    if constexpr (OP == 0) return 0;
+    else return pv_compare(OP, pv_value<L>(c, j), pv_value<R>(c, j)) ? 1 : 0;
+  }
+};
+// a predicate of the filter vocabulary as an Integer 0 / 1 that is NULL outside V — the 256-bit code masks of Utf8 compares
+// (InMask), and `True` with a validity mask: a column of which only "is it NULL" is asked
+template <class P, class V> struct PredPV {
+  using Type = I64;
+  static __device__ __forceinline__ bool valid(Ctx &c, int j) { return V::eval(c, j); }
+  static __device__ __forceinline__ int64_t eval(Ctx &c, int j) { return P::eval(c, j) ? 1 : 0; }
+};
+template <class E> struct NotPV {
+  using Type = I64;
+  static __device__ __forceinline__ bool valid(Ctx &c, int j) { return E::valid(c, j); }
+  static __device__ __forceinline__ int64_t eval(Ctx &c, int j) { return pv_not(pv_truth(pv_value<E>(c, j))); }
+};
+template <class E, int NEGATED> struct IsNullPV { // only the operand's validity is read
+  using Type = I64;
+  static __device__ __forceinline__ bool valid(Ctx &, int) { return true; }
+  static __device__ __forceinline__ int64_t eval(Ctx &c, int j) { return (E::valid(c, j) == (NEGATED != 0)) ? 1 : 0; }
+};
+template <int IS_OR, class L, class R> struct LogicPV { // three-valued AND / OR
+  using Type = I64;
+  static __device__ __forceinline__ bool both(Ctx &c, int j, bool *known) {
+    const bool lt = pv_truth(pv_value<L>(c, j)), rt = pv_truth(pv_value<R>(c, j));
+    if constexpr (IS_OR) return pv_or(lt, L::valid(c, j), rt, R::valid(c, j), known);
+    else return pv_and(lt, L::valid(c, j), rt, R::valid(c, j), known);
+  }
+  static __device__ __forceinline__ bool valid(Ctx &c, int j) { bool k; (void)both(c, j, &k); return k; }
+  static __device__ __forceinline__ int64_t eval(Ctx &c, int j) { bool k; return both(c, j, &k) ? 1 : 0; }
+};
+template <class Ty, class E> struct CastPV { // Ty = I64: Float by the saturating `as i64`; Ty = F64: Integer `as f64`
+  using Type = Ty;
+  static __device__ __forceinline__ bool valid(Ctx &c, int j) { return E::valid(c, j); }
+  static __device__ __forceinline__ typename Ty::T eval(Ctx &c, int j) {
+    if constexpr (Ty::is_float) return pv_cast_f64(pv_value<E>(c, j));
+    else return pv_cast_i64(pv_value<E>(c, j));
+  }
+};
+// Searched CASE: CasePV<Ty, W1, T1, …, Wn, Tn, E> — E is the ELSE, NullPV<Ty> without one; every T and E of class Ty (the
+// lowering refuses mixed branches).  A simple CASE arrives as the searched one over CmpPV<1, operand, candidate>: its match
+// rule is COMPARE's ==, and a NULL there is no match, as a NULL WHEN is no true one.
+template <class Ty, class... Ns> struct CasePV;
+template <class Ty, class E> struct CasePV<Ty, E> {
+  using Type = Ty;
+  static __device__ __forceinline__ bool valid(Ctx &c, int j) { return E::valid(c, j); }
+  static __device__ __forceinline__ typename Ty::T eval(Ctx &c, int j) { return (typename Ty::T)E::eval(c, j); }
+};
+template <class Ty, class W, class T, class... Rest> struct CasePV<Ty, W, T, Rest...> {
+  using Type = Ty;
+  using Tail = CasePV<Ty, Rest...>;
+  static __device__ __forceinline__ bool hit(Ctx &c, int j) { return W::valid(c, j) & pv_truth(pv_value<W>(c, j)); }
+  static __device__ __forceinline__ bool valid(Ctx &c, int j) {
+    const bool mine = T::valid(c, j), rest = Tail::valid(c, j);
+    return hit(c, j) ? mine : rest;
+  }
+  static __device__ __forceinline__ typename Ty::T eval(Ctx &c, int j) {
+    const typename Ty::T mine = (typename Ty::T)T::eval(c, j), rest = Tail::eval(c, j);
+    return hit(c, j) ? mine : rest;
+  }
+};
+template <class Ty, class... Es> struct CoalescePV; // the first non-NULL item, every item of class Ty
+template <class Ty, class E> struct CoalescePV<Ty, E> {
+  using Type = Ty;
+  static __device__ __forceinline__ bool valid(Ctx &c, int j) { return E::valid(c, j); }
+  static __device__ __forceinline__ typename Ty::T eval(Ctx &c, int j) { return (typename Ty::T)E::eval(c, j); }
+};
+template <class Ty, class E, class... Rest> struct CoalescePV<Ty, E, Rest...> {
+  using Type = Ty;
+  using Tail = CoalescePV<Ty, Rest...>;
+  static __device__ __forceinline__ bool valid(Ctx &c, int j) { return E::valid(c, j) | Tail::valid(c, j); }
+  static __device__ __forceinline__ typename Ty::T eval(Ctx &c, int j) {
+    const typename Ty::T mine = (typename Ty::T)E::eval(c, j), rest = Tail::eval(c, j);
+    return E::valid(c, j) ? mine : rest;
   }
 };
 // Predicate form of an expression's validity.

@@ -18,6 +18,7 @@
 // holds plus the straddlers it holds first; the union is merged on the host.
 #include "comm.hpp"
 #include "engine.hpp"
+#include "planvalue_expr.hpp"
 #include "join.hpp"
 
 #include <algorithm>
@@ -275,6 +276,10 @@ int JoinAgg::prepare(const llkv_join_side *fact, const llkv_join_side *dim, uint
   if (td->world != 1 || (t2 && t2->world != 1))
     return set_error(LLKV_INVALID_ARGUMENT, "dimension tables are replicated: stage them whole (world = 1) on every rank; only the fact table is sharded");
   n_payload = n_payload_;
+  { // (before tokens_name and the key images look at the program: they read COLUMN tokens only)
+    std::string why;
+    if ((rc = cond_refuse_elsewhere(sum_expr, sum_expr_len, "the join → GROUP BY calls", &why))) return set_error(rc, why);
+  }
   if (int_sums) { // what the call refuses does not depend on the dimension side: lowered once up front, over the table as staged
     if (tf->world != 1) return set_error(LLKV_UNSUPPORTED, "integer sums in the join-aggregate pipeline take an unsharded fact table (world = 1)");
     LoweredPlan ignore;

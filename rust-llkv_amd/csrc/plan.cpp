@@ -1,5 +1,6 @@
 // plan.cpp — see plan.hpp.
 #include "plan.hpp"
+#include "planvalue_expr.hpp"
 #include "scan_params.h" // kMaxCols, kMaxLits, kMaxKeys and the lane algebra (LaneOp) the kernels are built with
 
 #include <algorithm>
@@ -246,6 +247,7 @@ struct Lowered {
   bool is_f64 = false;
   int fit32 = 0;
   PlanValueInfo pv = {};
+  bool never_null = false; // conditional programs (expr_planvalue): no row makes the value NULL — the aggregate needs no IfValid, no count lane
 };
 
 // the conversions of a numeric literal the reference's constant paths apply (literal_to_array: `*v as i64`)
@@ -300,17 +302,43 @@ struct Lowering {
     bool all_finite = true;  // no column of the expression holds NaN / ±∞
   };
   Bounds expr_bounds(const llkv_expr_token *e, uint32_t n) {
-    struct I { Interval<double> v; double nz; };
+    // `finite`: no column the VALUE comes from holds NaN / ±∞ (the columns of a condition decide, they are not summed); `skip`:
+    // nothing to bound — the NULL literal, and the String / Date32 leaves of a conditional program, which only COMPARE / IS NULL /
+    // a simple CASE consume
+    // `unknown`: a column of a conditional program without usable statistics — fine inside a condition, no bound as a value
+    struct I { Interval<double> v; double nz; bool finite = true; bool skip = false; bool unknown = false; };
     std::vector<I> st;
     Bounds out;
+    const bool cond = cond_program(e, n); // (statically checked by expr_planvalue before any aggregate asks for bounds)
+    const I truth{{0.0, 1.0}, 1.0};
+    // CASE branches / COALESCE items → what the picked one can be
+    const auto one_of = [](const std::vector<I> &xs) {
+      I o{{0.0, 0.0}, 0.0};
+      bool first = true, nz_known = true;
+      double nz = 0.0;
+      for (const I &x : xs) {
+        if (x.skip) continue;
+        o.unknown |= x.unknown;
+        o.v = first ? x.v : Interval<double>{std::min(o.v.lo, x.v.lo), std::max(o.v.hi, x.v.hi)};
+        o.finite &= x.finite;
+        first = false;
+        if (x.v.lo == 0.0 && x.v.hi == 0.0) continue; // always zero: no non-zero value to bound from below
+        if (x.nz == 0.0) nz_known = false;
+        else nz = nz == 0.0 ? x.nz : std::min(nz, x.nz);
+      }
+      o.nz = nz_known ? (nz == 0.0 ? 1.0 : nz) : 0.0;
+      return o;
+    };
     for (uint32_t i = 0; i < n; ++i) {
       if (e[i].kind == LLKV_TOK_COLUMN) {
         const ColumnInfo *ci = resolve(e[i].field_id);
         if (!ci) return out;
         table_rows = std::max(table_rows, ci->rows);
+        if (cond && (ci->dtype == LLKV_DT_UTF8 || ci->dtype == LLKV_DT_DATE32)) { I b{{0.0, 0.0}, 0.0}; b.skip = true; st.push_back(b); continue; }
         if ((ci->dtype == LLKV_DT_FLOAT64 || ci->dtype == LLKV_DT_FLOAT32) && ci->has_fstats) {
-          st.push_back({{-ci->f_absmax, ci->f_absmax}, ci->f_absmin_nz});
-          out.all_finite &= ci->f_all_finite;
+          I b{{-ci->f_absmax, ci->f_absmax}, ci->f_absmin_nz};
+          b.finite = ci->f_all_finite;
+          st.push_back(b);
         }
         else if (ci->dtype == LLKV_DT_BOOLEAN) st.push_back({{0.0, 1.0}, 1.0});
         else if (ci->dtype == LLKV_DT_UTF8) { // numeric image of the dictionary
@@ -325,26 +353,33 @@ struct Lowering {
           st.push_back(b);
         }
         else if (is_int_class(ci->dtype) && ci->has_stats) st.push_back({{(double)ci->min_i, (double)ci->max_i}, 1.0});
+        else if (cond) { I b{{0.0, 0.0}, 0.0}; b.unknown = true; st.push_back(b); }
         else return out;
       } else if (e[i].kind == LLKV_TOK_LITERAL) {
         const llkv_literal &lit = e[i].literal;
         double v;
         if (lit.tag == LLKV_LIT_FLOAT64) v = lit.f64;
         else if (lit.tag == LLKV_LIT_INT128) v = (double)lit_i128(lit);
+        else if (cond && lit.tag == LLKV_LIT_BOOLEAN) v = lit.lo ? 1.0 : 0.0;
+        else if (cond && (lit.tag == LLKV_LIT_NULL || lit.tag == LLKV_LIT_STRING || lit.tag == LLKV_LIT_DATE32)) { I b{{0.0, 0.0}, 0.0}; b.skip = true; st.push_back(b); continue; }
         else return out;
         if (!std::isfinite(v)) return out;
         st.push_back({{v, v}, std::fabs(v)});
-      } else {
+      } else if (e[i].kind == LLKV_TOK_BINARY) {
         if (st.size() < 2) return out;
         const I r = st.back(); st.pop_back();
         const I l = st.back(); st.pop_back();
+        if (e[i].binop == LLKV_BIN_AND || e[i].binop == LLKV_BIN_OR) { st.push_back(truth); continue; }
         I o;
+        if (l.unknown || r.unknown) return out;
+        if (l.skip || r.skip) { o = I{{0.0, 0.0}, 0.0}; o.skip = true; st.push_back(o); continue; } // arithmetic with the NULL literal: always NULL
         switch (e[i].binop) {
         case LLKV_BIN_ADD: o = {l.v + r.v, 0.0}; break;
         case LLKV_BIN_SUB: o = {l.v - r.v, 0.0}; break;
         case LLKV_BIN_MUL: o = {l.v * r.v, l.nz * r.nz * 0.999999}; break;
         default: return out;
         }
+        o.finite = l.finite && r.finite;
         if (!std::isfinite(o.v.lo) || !std::isfinite(o.v.hi)) return out;
         if (e[i].binop != LLKV_BIN_MUL) { // the rounded endpoints of a sum: move them outwards a little before trusting their sign
           const double slack = 1e-12 * o.v.mag();
@@ -352,12 +387,41 @@ struct Lowering {
           else if (o.v.hi + slack < 0.0) o.nz = -(o.v.hi + slack);
         }
         st.push_back(o);
-      }
+      } else if (e[i].kind == LLKV_TOK_COMPARE) {
+        if (st.size() < 2) return out;
+        st.resize(st.size() - 2);
+        st.push_back(truth);
+      } else if (e[i].kind == LLKV_TOK_NOT || e[i].kind == LLKV_TOK_IS_NULL) {
+        if (st.empty()) return out;
+        st.back() = truth;
+      } else if (e[i].kind == LLKV_TOK_CAST) {
+        if (st.empty()) return out;
+        // to Float: the same values; to Integer: truncated toward zero (inside the interval, non-zero ones ≥ 1) — a NaN becomes 0,
+        // ±∞ saturate: only a finite source is bounded
+        if (e[i].binop == LLKV_DT_INT64 || e[i].binop == LLKV_DT_INT32) { if (!st.back().finite) return out; if (!st.back().skip) st.back().nz = 1.0; }
+      } else if (e[i].kind == LLKV_TOK_COALESCE) {
+        const uint32_t k = e[i].field_id;
+        if (k == 0 || st.size() < k) return out;
+        const I o = one_of(std::vector<I>(st.end() - k, st.end()));
+        st.resize(st.size() - k);
+        st.push_back(o);
+      } else if (e[i].kind == LLKV_TOK_CASE) {
+        const uint32_t w = e[i].field_id;
+        const bool simple = e[i].binop & LLKV_CASE_HAS_OPERAND, has_else = e[i].binop & LLKV_CASE_HAS_ELSE;
+        const size_t total = (simple ? 1 : 0) + 2 * (size_t)w + (has_else ? 1 : 0);
+        if (w == 0 || st.size() < total) return out;
+        std::vector<I> branches;
+        for (uint32_t k = 0; k < w; ++k) branches.push_back(st[st.size() - total + (simple ? 1 : 0) + 2 * k + 1]);
+        if (has_else) branches.push_back(st.back());
+        st.resize(st.size() - total);
+        st.push_back(one_of(branches));
+      } else return out;
     }
-    if (st.size() != 1) return out;
+    if (st.size() != 1 || st[0].skip || st[0].unknown) return out;
     out.ok = true;
     out.absmax = st[0].v.mag();
     out.nzmin = st[0].nz;
+    out.all_finite = st[0].finite;
     return out;
   }
 
@@ -485,7 +549,10 @@ struct Lowering {
     return LLKV_OK;
   }
   // NULL propagates through arithmetic: an expression is valid where all of its columns are.
+  // conditional tokens outside GROUP BY aggregate arguments: refused by name (one message: planvalue_expr.cpp)
+  int no_conditionals(const llkv_expr_token *e, uint32_t n, const char *where) { return cond_refuse_elsewhere(e, n, where, err); }
   int valid_of_expr(const llkv_expr_token *e, uint32_t n, std::vector<std::string> *vs, bool *some_never_null = nullptr) {
+    if (int rc = no_conditionals(e, n, "the validity of an expression")) return rc; // (NULL does not simply propagate through CASE / COALESCE / IS NULL)
     for (uint32_t i = 0; i < n; ++i)
       if (e[i].kind == LLKV_TOK_COLUMN)
         if (int rc = add_valid_of_field(e[i].field_id, vs, some_never_null)) return rc;
@@ -537,6 +604,8 @@ struct Lowering {
   }
   // Validity of a lowered expression node as a predicate: "" when it can never be NULL.
   int valid_of_node(const llkv_expr_token *e, uint32_t n, const std::string &node, bool grouped_semantics, std::string *v) {
+    // a conditional program (GROUP BY aggregate arguments: expr_planvalue lowered `node`): what is NULL is the node's own answer
+    if (grouped_semantics && cond_program(e, n)) { *v = "VE<" + node + ">"; return LLKV_OK; }
     std::vector<std::string> vs;
     int rc = valid_of_expr(e, n, &vs);
     if (rc) return rc;
@@ -1179,6 +1248,7 @@ struct Lowering {
   // errors (integer overflow, x % 0) leaves the node as it was: such a plan is handed back.
   int fold_constants(const llkv_expr_token *e, uint32_t n, std::vector<llkv_expr_token> *out) {
     out->clear();
+    if (int rc = no_conditionals(e, n, "constant folding of a computed expression")) return rc;
     auto is_num = [](const llkv_expr_token &t) { return t.kind == LLKV_TOK_LITERAL && numeric_or_null(t.literal); };
     for (uint32_t i = 0; i < n; ++i) {
       const size_t m = out->size();
@@ -1224,6 +1294,7 @@ struct Lowering {
 
   int expr_fast(const llkv_expr_token *e_in, uint32_t n_in, Lowered *out) {
     *out = Lowered{};
+    if (int rc = no_conditionals(e_in, n_in, "computed projections and ungrouped aggregate arguments")) return rc;
     std::vector<llkv_expr_token> folded;
     int frc = fold_constants(e_in, n_in, &folded);
     if (frc) return frc;
@@ -1306,6 +1377,7 @@ struct Lowering {
     struct V { std::string s; bool f; };
     std::vector<V> st;
     int rc;
+    if ((rc = no_conditionals(e, n, "computed projections and ungrouped aggregate arguments"))) return rc;
     for (uint32_t i = 0; i < n; ++i) {
       if (e[i].kind == LLKV_TOK_COLUMN) {
         const ColumnInfo *ci;
@@ -1349,7 +1421,73 @@ struct Lowering {
     bool bounded = false;
     Interval<i128> iv = {};
     bool lit = false;   // an integer / decimal literal (lo == hi)
+    // conditional programs (cond_static_check decided what may stand where):
+    bool nn = false;                  // never NULL, whatever the row holds (columns without NULL cells, literals, and what keeps that)
+    bool null_lit = false;            // the NULL literal: s = NullPV<I64>, retyped where it is a CASE branch / COALESCE item
+    int other = 0;                    // kPvString / kPvDate32: s is a validity-only node (PredPV<True, …>), nothing reads a value
+    const ColumnInfo *str_col = nullptr; // … a Utf8 column, compared through a code mask over its dictionary
+    uint32_t field = 0;
+    std::string str;                  // … a String literal
   };
+  int pv_class(const PV &v) const { return v.other ? v.other : v.f ? kPvFloat : kPvInteger; }
+  static PV pv_truth_value(const std::string &node, bool nn) { PV o; o.s = node; o.bounded = true; o.iv = {0, 1}; o.nn = nn; return o; }
+  // a leaf of which only "is it NULL" can be asked
+  int validity_only(uint32_t field, std::string *node) {
+    std::string v;
+    if (int rc = valid_of_field(field, &v)) return rc;
+    *node = "PredPV<True," + (v.empty() ? std::string("True") : v) + ">";
+    return LLKV_OK;
+  }
+  // COMPARE over two lowered sides (and the match of a simple CASE, which is COMPARE's ==): the pairings of planvalue_rules.h
+  int compare_planvalue(int op, const PV &l, const PV &r, PV *out) {
+    int rc;
+    if (l.null_lit || r.null_lit) { *out = pv_truth_value("NullPV<I64>", false); return LLKV_OK; } // either side Null → Null
+    const bool nn = l.nn && r.nn;
+    const int lc = pv_class(l), rc_ = pv_class(r);
+    if (!pv_comparable(lc, rc_)) { *out = pv_truth_value("CmpPV<0," + l.s + "," + r.s + ">", nn); return LLKV_OK; } // Integer 0 where both are non-NULL
+    if (lc != kPvString) { *out = pv_truth_value("CmpPV<" + std::to_string(op) + "," + l.s + "," + r.s + ">", nn); return LLKV_OK; }
+    const auto order = [](const std::string &a, const std::string &b) { const int c = a.compare(b); return (c > 0) - (c < 0); }; // bytes, then lengths
+    if (!l.str_col && !r.str_col) { // two literals
+      std::string k;
+      if ((rc = lit_i(pv_compare_bytes(op, order(l.str, r.str)) ? 1 : 0, &k))) return rc;
+      *out = pv_truth_value(k, true);
+      return LLKV_OK;
+    }
+    // a Utf8 column against a String literal: the 256-bit set of the codes whose strings pass, whatever the dictionary's order
+    const bool col_left = l.str_col != nullptr;
+    const PV &col = col_left ? l : r, &lit = col_left ? r : l;
+    uint64_t mask[4] = {0, 0, 0, 0};
+    for (size_t i = 0; i < col.str_col->dictionary.size() && i < 256; ++i) {
+      const int o = order(col.str_col->dictionary[i], lit.str);
+      if (pv_compare_bytes(op, col_left ? o : -o)) mask[i >> 6] |= 1ull << (i & 63);
+    }
+    const ColumnInfo *ci;
+    int slot;
+    if ((rc = slot_of(col.field, &ci, &slot))) return rc; // (refuses a wide Utf8 column)
+    std::string m[4], v;
+    for (int w = 0; w < 4; ++w) if ((rc = lit_i((int64_t)mask[w], &m[w], "LitU"))) return rc;
+    if ((rc = valid_of_field(col.field, &v))) return rc;
+    *out = pv_truth_value("PredPV<InMask<" + col_node(slot, ci->dtype) + "," + m[0] + "," + m[1] + "," + m[2] + "," + m[3] + ">," + (v.empty() ? std::string("True") : v) + ">", nn);
+    return LLKV_OK;
+  }
+  // CASE branches / COALESCE items of class `f`: their nodes (the NULL literal typed like the others) and what the picked one can be
+  static void value_branches(const std::vector<PV> &xs, bool f, std::vector<std::string> *nodes, PV *out, bool *all_nn, bool *any_nn) {
+    bool first = true;
+    out->f = f;
+    out->bounded = !f;
+    *all_nn = true;
+    *any_nn = false;
+    for (const PV &x : xs) {
+      *all_nn = *all_nn && x.nn;
+      *any_nn = *any_nn || x.nn;
+      nodes->push_back(x.null_lit ? std::string(f ? "NullPV<F64>" : "NullPV<I64>") : x.s);
+      if (x.null_lit || f) continue;
+      out->bounded = out->bounded && x.bounded;
+      out->iv = first ? x.iv : Interval<i128>{std::min(out->iv.lo, x.iv.lo), std::max(out->iv.hi, x.iv.hi)};
+      first = false;
+    }
+    if (!out->bounded) out->iv = {};
+  }
 
   static i128 pow10_i128(int k) { i128 v = 1; for (int i = 0; i < k; ++i) v *= 10; return v; }
 
@@ -1358,8 +1496,108 @@ struct Lowering {
     std::vector<PV> st;
     int rc;
     *out = Lowered{};
+    // A program with a conditional token (Compare, Not, IsNull, Cast, Case, Coalesce, And / Or — :7008-7632): its shape, caps and
+    // which class may stand where are checked first, once, by the check the host evaluator makes too; below, every such token
+    // becomes a node of fused_scan.hip.h's conditional family, with its class (PV::f) and the interval of its integer values
+    const bool cond = cond_program(e, n);
+    std::vector<CondNode> cn;
+    if (cond) {
+      const CondLeafClass leaf = [&](uint32_t field) { const ColumnInfo *ci = resolve(field); return ci ? cond_class_of_dtype(ci->dtype) : -2; };
+      if ((rc = cond_static_check(e, n, leaf, &cn, err))) return rc;
+    }
     for (uint32_t i = 0; i < n; ++i) {
-      if (e[i].kind == LLKV_TOK_COLUMN) {
+      if (cond && e[i].kind == LLKV_TOK_COLUMN && (cn[i].cls == kPvString || cn[i].cls == kPvDate32)) {
+        PV v;
+        v.other = cn[i].cls;
+        v.field = e[i].field_id;
+        if (cn[i].cls == kPvString) {
+          v.str_col = resolve(e[i].field_id);
+          if (utf8_wide(*v.str_col)) return fail(LLKV_UNSUPPORTED, wide_utf8_refusal(*v.str_col, "a conditional expression"));
+        }
+        if ((rc = validity_only(e[i].field_id, &v.s))) return rc;
+        v.nn = !resolve(e[i].field_id)->nullable;
+        st.push_back(v);
+      } else if (cond && e[i].kind == LLKV_TOK_LITERAL && e[i].literal.tag != LLKV_LIT_INT128 && e[i].literal.tag != LLKV_LIT_FLOAT64) {
+        const llkv_literal &lit = e[i].literal; // (cond_static_check refused the Decimal128 literal)
+        PV v;
+        if (lit.tag == LLKV_LIT_NULL) { v.s = "NullPV<I64>"; v.null_lit = true; v.bounded = true; }
+        else if (lit.tag == LLKV_LIT_BOOLEAN) { // Integer 0 / 1
+          const int64_t x = lit.lo ? 1 : 0;
+          if ((rc = lit_i(x, &v.s))) return rc;
+          v.bounded = true; v.iv = {x, x}; v.lit = true; v.nn = true;
+        } else { // String / Date32: a COMPARE side, a simple CASE's operand or candidate, or under IS NULL — never NULL
+          v.other = cn[i].cls;
+          v.s = "PredPV<True,True>";
+          v.nn = true;
+          if (lit.tag == LLKV_LIT_STRING) v.str = lit.str;
+        }
+        st.push_back(v);
+      } else if (e[i].kind == LLKV_TOK_COMPARE) {
+        PV r = st.back(); st.pop_back();
+        PV l = st.back(); st.pop_back();
+        PV o;
+        if ((rc = compare_planvalue(e[i].binop, l, r, &o))) return rc;
+        st.push_back(o);
+      } else if (e[i].kind == LLKV_TOK_NOT) {
+        st.back() = pv_truth_value("NotPV<" + st.back().s + ">", st.back().nn);
+      } else if (e[i].kind == LLKV_TOK_IS_NULL) {
+        st.back() = pv_truth_value("IsNullPV<" + st.back().s + "," + (e[i].binop ? "1" : "0") + ">", true);
+      } else if (e[i].kind == LLKV_TOK_CAST) {
+        PV v = st.back(); st.pop_back();
+        PV o;
+        if (cn[i].cls == kPvFloat) { o.f = true; o.s = v.f ? v.s : "CastPV<F64," + v.s + ">"; }
+        else if (!v.f) { o = v; o.null_lit = false; o.lit = false; } // Integer stays as it is
+        else { o.s = "CastPV<I64," + v.s + ">"; o.bounded = true; o.iv = {INT64_MIN, INT64_MAX}; } // the saturating `as i64`: anything an i64 holds
+        o.nn = v.nn;
+        st.push_back(o);
+      } else if (e[i].kind == LLKV_TOK_COALESCE) {
+        const uint32_t k = e[i].field_id;
+        const std::vector<PV> items(st.end() - k, st.end());
+        st.resize(st.size() - k);
+        const bool f = cn[i].cls == kPvFloat;
+        PV o;
+        std::vector<std::string> nodes;
+        bool all_nn, any_nn;
+        value_branches(items, f, &nodes, &o, &all_nn, &any_nn);
+        o.nn = any_nn;
+        o.s = std::string("CoalescePV<") + (f ? "F64" : "I64");
+        for (const std::string &x : nodes) o.s += "," + x;
+        o.s += ">";
+        st.push_back(o);
+      } else if (e[i].kind == LLKV_TOK_CASE) {
+        const uint32_t w = e[i].field_id;
+        const bool simple = e[i].binop & LLKV_CASE_HAS_OPERAND, has_else = e[i].binop & LLKV_CASE_HAS_ELSE;
+        const size_t total = (simple ? 1 : 0) + 2 * (size_t)w + (has_else ? 1 : 0);
+        const std::vector<PV> a(st.end() - total, st.end());
+        st.resize(st.size() - total);
+        const bool f = cn[i].cls == kPvFloat;
+        const char *ty = f ? "F64" : "I64";
+        std::vector<PV> branches;
+        std::string whens[kCondMaxWhens];
+        std::vector<std::string> nodes;
+        for (uint32_t k = 0; k < w; ++k) {
+          const PV &when = a[(simple ? 1 : 0) + 2 * k];
+          if (simple) { // operand == candidate, COMPARE's rule; a NULL on either side is no match, as a NULL WHEN is not true
+            PV m;
+            if ((rc = compare_planvalue(LLKV_CMP_EQ, a[0], when, &m))) return rc;
+            whens[k] = m.s;
+          } else whens[k] = when.s;
+          branches.push_back(a[(simple ? 1 : 0) + 2 * k + 1]);
+        }
+        if (has_else) branches.push_back(a.back());
+        PV o;
+        bool all_nn, any_nn;
+        value_branches(branches, f, &nodes, &o, &all_nn, &any_nn);
+        o.nn = has_else && all_nn; // (without an ELSE a row that no WHEN takes is NULL)
+        o.s = std::string("CasePV<") + ty; // CasePV<Ty, W1, T1, …, Wn, Tn, E>
+        for (uint32_t k = 0; k < w; ++k) o.s += "," + whens[k] + "," + nodes[k];
+        o.s += "," + (has_else ? nodes[w] : std::string("NullPV<") + ty + ">") + ">";
+        st.push_back(o);
+      } else if (e[i].kind == LLKV_TOK_BINARY && (e[i].binop == LLKV_BIN_AND || e[i].binop == LLKV_BIN_OR)) {
+        PV r = st.back(); st.pop_back();
+        PV l = st.back(); st.pop_back();
+        st.push_back(pv_truth_value(std::string("LogicPV<") + (e[i].binop == LLKV_BIN_OR ? "1," : "0,") + l.s + "," + r.s + ">", l.nn && r.nn));
+      } else if (e[i].kind == LLKV_TOK_COLUMN) {
         const ColumnInfo *ci;
         std::string c;
         if ((rc = expr_col_node(e[i].field_id, &ci, &c))) return rc;
@@ -1375,6 +1613,7 @@ struct Lowering {
           v.s = c; v.dec = true; v.scale = ci->scale;
         }
         else return fail(LLKV_UNSUPPORTED, std::string("aggregate expression over ") + dtype_name(ci->dtype));
+        v.nn = !ci->nullable;
         if (!v.f) {
           v.bounded = true;
           if (ci->has_stats) v.iv = {ci->min_i, ci->max_i};
@@ -1400,9 +1639,10 @@ struct Lowering {
           v.dec = true; v.scale = lit.scale; v.bounded = true; v.iv = {raw, raw}; v.lit = true;
         }
         else return fail(LLKV_UNSUPPORTED, "literal kind in aggregate expression");
+        v.nn = true;
         v.s = l;
         st.push_back(v);
-      } else {
+      } else { // LLKV_TOK_BINARY, + − * / % (cond_program sends every other kind through cond_static_check, which knows them all by name)
         if (st.size() < 2) return fail(LLKV_INTERNAL, "expression stack underflow");
         PV r = st.back(); st.pop_back();
         PV l = st.back(); st.pop_back();
@@ -1505,6 +1745,7 @@ struct Lowering {
           o.s = "Bin<" + std::to_string(op) + "," + a + "," + b + nan_flag(true) + ">";
           o.f = true;
         }
+        o.nn = l.nn && r.nn && op != 4; // (x % 0 is NULL; the divisions above leave nn off)
         st.push_back(o);
       }
     }
@@ -1515,6 +1756,7 @@ struct Lowering {
     out->pv.scale = st[0].scale;
     out->pv.iv = st[0].iv;
     out->pv.bounded = st[0].bounded && !st[0].f;
+    out->never_null = st[0].nn;
     return LLKV_OK;
   }
 };
@@ -1564,6 +1806,7 @@ struct AggLowering {
     std::string valid;              // rows where the argument is non-NULL ("": all)
     PlanValueInfo pv = {};          // grouped computed arguments
     uint64_t rows = 0;              // most rows of any column of the expression
+    bool cond = false;              // a conditional program (its integer bounds are true bounds: SumI64Fast off them)
     const char *fn() const { return s.kind == LLKV_AGG_SUM ? "SUM" : s.kind == LLKV_AGG_TOTAL ? "TOTAL" : s.kind == LLKV_AGG_AVG ? "AVG" : s.kind == LLKV_AGG_MIN ? "MIN" : "MAX"; }
   };
   uint64_t expr_rows(const llkv_aggregate_spec &s) const {
@@ -1676,6 +1919,8 @@ struct AggLowering {
   }
   int distinct(const llkv_aggregate_spec &s, AggOut &o) {
     int rc;
+    // (on every route, before one is named: same_tokens below compares COLUMN / LITERAL / BINARY programs only)
+    if ((rc = L.no_conditionals(s.expr, s.expr_len, "DISTINCT aggregates inside GROUP BY"))) return rc;
     if (!L.allow_sorted_distinct) return L.fail(LLKV_UNSUPPORTED, "DISTINCT aggregates inside GROUP BY run on the sort-based route");
     if (s.kind != LLKV_AGG_COUNT && s.kind != LLKV_AGG_SUM && s.kind != LLKV_AGG_TOTAL && s.kind != LLKV_AGG_AVG)
       return L.fail(LLKV_UNSUPPORTED, "DISTINCT form of aggregate kind " + std::to_string(s.kind));
@@ -1731,8 +1976,12 @@ struct AggLowering {
     // constants is gone from it — where the GROUP BY route reads the original)
     std::vector<llkv_expr_token> folded;
     if (!grouped && (rc = L.fold_constants(s.expr, s.expr_len, &folded))) return rc;
-    if ((rc = grouped ? L.valid_of_node(s.expr, s.expr_len, a->node, grouped, &a->valid) : L.valid_of_node(folded.data(), (uint32_t)folded.size(), a->node, grouped, &a->valid))) return rc;
-    if (a->pv.is_decimal) a->rows = expr_rows(s);
+    // (a conditional program that no row makes NULL — CASE … ELSE 0.0 over columns without NULL cells — needs no IfValid and no count
+    // lane; valid_of_node, which does not see that, would answer VE<node>)
+    a->cond = grouped && cond_program(s.expr, s.expr_len);
+    if (a->cond && x.never_null) a->valid.clear();
+    else if ((rc = grouped ? L.valid_of_node(s.expr, s.expr_len, a->node, grouped, &a->valid) : L.valid_of_node(folded.data(), (uint32_t)folded.size(), a->node, grouped, &a->valid))) return rc;
+    if (a->pv.is_decimal || a->cond) a->rows = expr_rows(s);
     return LLKV_OK;
   }
   // a bare column as an accumulator's input (validate_aggregate_type llkv-executor/src/lib.rs:5946-5988)
@@ -1886,9 +2135,12 @@ struct AggLowering {
     const bool f64_column = a.simple && a.ci->dtype == LLKV_DT_FLOAT64;
     // statistics that exclude i64 overflow of any prefix sum: rows · max|v| ≤ i64::MAX — one wrapping lane; shared-image plans
     // may then keep it in a 4-byte cell (SumI64Fast over a plain integer column: max |v|; with IfValid: + a count lane)
-    const bool fast_i64 = !a.is_f64 && a.simple && a.ci->has_stats && stats_mag(*a.ci) * (u128)a.ci->rows <= (u128)INT64_MAX;
+    // … and a conditional argument whose interval (the union of its branches, {0, 1} for a truth value) does the same
+    const bool fast_cond = !a.is_f64 && a.cond && a.pv.bounded && a.rows > 0 && (u128)a.pv.iv.mag() * (u128)a.rows <= (u128)INT64_MAX;
+    const bool fast_i64 = fast_cond || (!a.is_f64 && a.simple && a.ci->has_stats && stats_mag(*a.ci) * (u128)a.ci->rows <= (u128)INT64_MAX);
     const auto sum_i64 = [&]() {
-      if (fast_i64) add_agg(a, o, "SumI64Fast<" + node + ">", {OP_ADD_I64}, {}, std::max(1.0, std::max(std::fabs((double)a.ci->min_i), std::fabs((double)a.ci->max_i))));
+      if (fast_cond) add_agg(a, o, "SumI64Fast<" + node + ">", {OP_ADD_I64}, {}, std::max(1.0, (double)a.pv.iv.mag()));
+      else if (fast_i64) add_agg(a, o, "SumI64Fast<" + node + ">", {OP_ADD_I64}, {}, std::max(1.0, std::max(std::fabs((double)a.ci->min_i), std::fabs((double)a.ci->max_i))));
       else add_agg(a, o, "SumI64<" + node + ">", {OP_ADD_I64, OP_ADD_I64, OP_MAX_U64});
     };
     // MinFloat64 / MaxFloat64 (llkv-aggregate/src/lib.rs:1309-1331,1377-1399) fold sequentially by partial_cmp: a leading NaN sticks,
@@ -2333,6 +2585,7 @@ int lower_probe(const ColumnResolver &resolve, const llkv_filter *filters, uint3
       return L.fail(LLKV_UNSUPPORTED, "NULL aggregate arguments in the join-aggregate pipeline");
   if ((rc = L.key_node(*ci, slot, &key))) return rc;
   if (!expr || expr_len == 0) return L.fail(LLKV_INVALID_ARGUMENT, "aggregate requires an argument");
+  if ((rc = L.no_conditionals(expr, expr_len, "the join → GROUP BY calls"))) return rc;
   const size_t early = out->slot_fields.size(); // the slots so far feed the predicate and the key; what the value adds is read late
   Lowered val;
   if ((rc = L.expr_planvalue(expr, expr_len, &val))) return rc;

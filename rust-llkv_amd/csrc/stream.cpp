@@ -4,6 +4,7 @@
 // windows (execute.rs:31) → gather + computed projections on the device → pinned host
 // window → on_batch on the calling thread, in row-id order, never an empty batch.
 #include "engine.hpp"
+#include "planvalue_expr.hpp"
 #include "join.hpp"
 
 #include <cstring>
@@ -378,6 +379,8 @@ llkv_status llkv_hip_scan_stream(const llkv_hip_table *table, const llkv_project
   std::vector<uint32_t> gathered;
   if (!(options && options->include_nulls)) {
     for (uint32_t i = 0; i < n_projections; ++i) {
+      // (COLUMN / LITERAL / BINARY programs only: which fields a conditional expression gathers is not restated here)
+      if (projections[i].computed && (rc = cond_refuse_elsewhere(projections[i].expr, projections[i].expr_len, "computed scan projections", &err))) return (llkv_status)set_error(rc, err);
       if (!projections[i].computed) gathered.push_back(projections[i].field_id);
       else for (uint32_t k = 0; k < projections[i].expr_len; ++k)
         if (projections[i].expr[k].kind == LLKV_TOK_COLUMN) gathered.push_back(projections[i].expr[k].field_id);

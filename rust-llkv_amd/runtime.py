@@ -780,6 +780,22 @@ def having_eval(having, key_cells: Sequence["abi.Value"] = (), key_dtypes: Seque
     return None if truth.value < 0 else bool(truth.value)
 
 
+def scalar_eval_planvalue(expr: "abi.ScalarExpr", cells: Dict[int, "abi.Value"]) -> Value:
+    """The PlanValue rules of a GROUP BY aggregate argument over one row, host only (llkv_hip_scalar_eval_planvalue): ``cells`` maps
+    a field id to its cell, whose dtype is the column's; returns the Null / Int64 / Float64 cell, or raises what the lowering
+    would refuse."""
+    keep: list = []
+    toks = expr.to_c(keep)
+    fields = list(cells)
+    ids = (C.c_uint32 * max(1, len(fields)))(*fields)
+    cs = (abi.CValue * max(1, len(fields)))(*[cells[f].to_c(keep) for f in fields])
+    out = abi.CValue()
+    L = lib()
+    L.llkv_hip_scalar_eval_planvalue.argtypes = [C.POINTER(abi.CExprToken), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(abi.CValue), C.c_uint32, C.POINTER(abi.CValue)]
+    check(L.llkv_hip_scalar_eval_planvalue(toks, C.c_uint32(len(expr.tokens)), ids, cs, C.c_uint32(len(fields)), C.byref(out)))
+    return Value.from_c(out)
+
+
 def groupby(table: HipTable, predicate, keys: Sequence[int], aggs: Sequence[AggregateSpec], order_by_keys: bool = False,
             order: Sequence["abi.GroupOrder"] = (), offset: int = 0, limit: Optional[int] = None, having=None) -> List[GroupRow]:
     """execute_group_by_single_table (llkv-executor/src/lib.rs:4405); ``having``: an ``abi.Having`` over the output cells

@@ -2,7 +2,7 @@
 // six lower_* entry points, cast_literal_for_column, dictionary_ranks and parse_numeric_or_zero and writes one canonical text
 // record per case (entry point, flags, status, error text, every field of the LoweredPlan; doubles as bit patterns).  Two
 // builds — one against an older plan.cpp, one against the tree's — must write byte-identical dumps.  Includes plan.hpp only.
-//   g++ -std=c++17 -O2 -I include -I rust-llkv_amd/csrc -o tools/plan_dump tools/plan_dump.cpp rust-llkv_amd/csrc/plan.cpp
+//   g++ -std=c++17 -O2 -I include -I rust-llkv_amd/csrc -o tools/plan_dump tools/plan_dump.cpp rust-llkv_amd/csrc/plan.cpp rust-llkv_amd/csrc/planvalue_expr.cpp
 //   tools/plan_dump > dump.txt                                  the records; per-entry-point counts on stderr
 //   tools/plan_dump --coverage-report plan.cpp jit_seed_plans.txt   which node names / fail() messages of that source the corpus reaches
 //   tools/plan_dump --time                                      median host time of seven representative lowerings

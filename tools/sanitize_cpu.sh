@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 gcc -O1 -g -fPIC -std=gnu11 -fsanitize=address,undefined -fno-omit-frame-pointer -I"$ROOT/include" -shared \
     -o "$OUT/libllkv_oracle.so" "$ROOT/oracle/llkv_oracle.c" "$ROOT/oracle/llkv_oracle_fast.c" -lm -lpthread
 g++ -std=c++17 -O1 -g -fPIC -fsanitize=address,undefined -fno-omit-frame-pointer -I"$ROOT/include" -I"$ROOT/rust-llkv_amd/csrc" -shared \
-    -o "$OUT/libllkv_plan.so" "$ROOT/rust-llkv_amd/csrc/plan.cpp" "$ROOT/rust-llkv_amd/csrc/plan_capi.cpp"
+    -o "$OUT/libllkv_plan.so" "$ROOT/rust-llkv_amd/csrc/plan.cpp" "$ROOT/rust-llkv_amd/csrc/plan_capi.cpp" "$ROOT/rust-llkv_amd/csrc/planvalue_expr.cpp"
 export LD_PRELOAD="$(gcc -print-file-name=libasan.so)" ASAN_OPTIONS=detect_leaks=0
 cd "$ROOT"
 LLKV_ORACLE_LIB="$OUT/libllkv_oracle.so" python -m pytest tests/test_oracle_golden.py -x -q
