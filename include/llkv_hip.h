@@ -1350,6 +1350,61 @@ llkv_status llkv_hip_join_rows_get(const llkv_hip_join_rows *rows, uint64_t i, i
 void llkv_hip_join_rows_free(llkv_hip_join_rows *rows);
 
 /* ------------------------------------------------------------------------- */
+/* Join columns: dimension attributes looked up onto the fact table, in HBM.   */
+/* The calls above group a join by the dimension's unique KEY only.  A join     */
+/* column turns a join against a primary key into a column of the fact table:   */
+/*   fact.out_field[r] = dim.dim_field[row of dim whose key == fact.fact_key_field[r]]                                        */
+/* NULL when the fact key is NULL, or no qualifying dim row has that key, or the dim cell is NULL.  A lookup kernel builds it    */
+/* (join_column.hip): no PCIe traffic, no joined batch.  From then on it is a column like any other — GROUP BY a dimension      */
+/* attribute, filter on one, CASE over one (TPC-H Q12: GROUP BY l_shipmode, SUM(CASE WHEN o_orderpriority = …)), DISTINCT and    */
+/* ORDER BY … LIMIT over joined rows are the existing calls over `fact`.                                                      */
+/*                                                                                                                              */
+/* Equivalence.  After the call `fact` answers EVERY call of the library — aggregates, all GROUP BY routes, scans, top-N,         */
+/* DISTINCT, set operations, joins, filters on the new column, conditional arguments, value and key images — exactly as a table  */
+/* on which the same cells had been staged from the host with append_column / append_utf8_column[_ex] /                           */
+/* append_decimal128_column + validity (NULL cells staged as zero values; a Utf8 column staged with the dimension's dictionary). */
+/* Same dtype and the same dictionary: a narrow Utf8 column keeps the dimension's 1-byte codes and dictionary, a wide one its     */
+/* 4-byte codes and byte-ordered dictionary.  Same (precision, scale) for a Decimal128 staged in 64 bits.  Statistics are       */
+/* computed over the result, by the staging path's own device pass; a validity mask exists exactly when some cell is NULL (a     */
+/* dimension column without a mask still yields one when a fact row finds no dimension row; when every fact row matched and no   */
+/* dimension cell is NULL the column is not nullable).  Padding rows between ragged chunks and the slack behind the image follow */
+/* the staging convention (zeroed slack, validity 0 in padding): the dense scans rely on it.                                     */
+/* Join semantics.  The cells are the right-side columns of the reference's LEFT join of `fact` with the qualifying rows of      */
+/* `dim` (dim->filters, a conjunction) on (fact_key_field, dim->key_field): one output row per fact row, in fact order.  An       */
+/* INNER join is the same query with IS NOT NULL on a join column whose dimension column has no NULL cell — bringing the key      */
+/* itself over (dim_field = dim->key_field) always gives one.  There is no separate match flag.                                  */
+/* Keys.  Both sides Int64 / Int32 / Date32 / UInt32; they may differ in type and are compared by value.  A NULL dimension key   */
+/* matches nothing.  The dimension key must be unique among the qualifying rows: otherwise LLKV_UNSUPPORTED ("a fact row would   */
+/* become several joined rows").                                                                                                 */
+/* Refusals — `fact` is unchanged by every one of them.  LLKV_UNSUPPORTED, the message naming the cause: the dimension key has   */
+/* no statistics-bounded range, or its range spans more than 2^28 keys (the lookup table would pass 1 GiB); a dimension column   */
+/* staged as a wide (128-bit) Decimal128; a sharded fact or dimension table (world != 1).  LLKV_INVALID_ARGUMENT: NULL           */
+/* arguments; n_cols 0 or above 8; an out_field listed twice or already staged in `fact`.  LLKV_NOT_FOUND: a missing key or      */
+/* dimension field.  All of these are answered before a device is needed.                                                        */
+/* Lifetime.  A join column is a SNAPSHOT: a later append to `dim` does not change it — llkv_hip_table_join_column_source tells  */
+/* which dimension image (table id, generation, field) it was looked up from, so a binding can see that it is stale.             */
+/* llkv_hip_table_append_chunks on a fact table that holds join columns answers LLKV_UNSUPPORTED ("drop the join columns         */
+/* first") before touching anything; tables without join columns behave as before.  llkv_hip_table_drop_join_columns frees all   */
+/* of them and starts a new generation of `fact`, so prepared queries, which may name them, refuse at launch (prepare them       */
+/* again); it keeps key images, value images of other fields and tile lists — their buffers did not move — and drops the images  */
+/* of the dropped fields; on a table without join columns it does nothing.  No execution may be in flight during add or drop     */
+/* (the rule of llkv_hip_table_append_chunks).  Device memory: per column (cell width + 1) B per fact row while it is built; the */
+/* validity byte is freed again when no cell is NULL.                                                                            */
+/* ------------------------------------------------------------------------- */
+typedef struct llkv_table_join_column {
+  uint32_t dim_field; /* column of dim to bring over (may be dim's key itself) */
+  uint32_t out_field; /* new field id in fact                                    */
+} llkv_table_join_column;
+
+llkv_status llkv_hip_table_add_join_columns(llkv_hip_table *fact, uint32_t fact_key_field,
+                                            const llkv_join_side *dim /* table, filters (conjunction), key_field */,
+                                            const llkv_table_join_column *cols, uint32_t n_cols /* 1..8 */,
+                                            uint64_t *matched_rows /* may be NULL: fact rows that found a dim row */);
+llkv_status llkv_hip_table_drop_join_columns(llkv_hip_table *fact);
+llkv_status llkv_hip_table_join_column_source(const llkv_hip_table *fact, uint32_t out_field, uint16_t *dim_table_id,
+                                              uint64_t *dim_generation, uint32_t *dim_field);
+
+/* ------------------------------------------------------------------------- */
 /* Multi-GPU combine, host pieces (no device needed).  The chunk list is cut    */
 /* into 8 canonical octants (boundaries floor(j·C/8)); rank r of `world` owns   */
 /* octants [r·8/world, (r+1)·8/world).  Partial aggregate state is exchanged    */

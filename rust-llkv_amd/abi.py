@@ -444,6 +444,10 @@ class CJoinSide(C.Structure):
     _fields_ = [("table", C.c_void_p), ("filters", C.POINTER(CFilter)), ("n_filters", C.c_uint32), ("key_field", C.c_uint32)]
 
 
+class CTableJoinColumn(C.Structure):  # llkv_table_join_column
+    _fields_ = [("dim_field", C.c_uint32), ("out_field", C.c_uint32)]
+
+
 class CJoinGroupRow(C.Structure):
     _fields_ = [("key", C.c_int64), ("sum", C.c_double), ("count", C.c_uint64), ("payload", C.c_int64 * 4),
                 ("group_index", C.c_uint64)]

@@ -182,6 +182,12 @@ struct DeviceColumn {
   bool local_f_no_nan = false; // … nor NaN
   DeviceBuffer d_valid; // uint8_t: 1 B/row validity mask (info.nullable), same row layout as d_values
   DeviceBuffer d_hi;    // Decimal128 values beyond 64 bits (info.wide128): d_values holds the low halves, this the high halves
+  // A join column (llkv_hip_table_add_join_columns, join_column.hip): the cells were looked up from column `src_field` of the
+  // dimension image (src_table_id, src_generation) — a snapshot of it; llkv_hip_table_drop_join_columns frees the column.
+  bool join_column = false;
+  uint16_t src_table_id = 0;
+  uint64_t src_generation = 0;
+  uint32_t src_field = 0;
 };
 
 // The key kernels' view of a staged column (join.hip: load_key, key_cell): width and sign by storage dtype — 1-byte codes for a
@@ -359,6 +365,17 @@ struct PhaseTrace {
 };
 
 void compute_layout(Table &t);
+// What every way of bringing a column into a table shares (table.cpp).  check_new_column: the refusals of a field that is staged
+// already and of a chunk count that is not the table's.  alloc_column: a zeroed image of `width` B/row with the slack behind it.
+// register_column: padding rows and statistics (Utf8 columns carry none) of a column whose image is complete on the device, which
+// then joins `into` — the table's `cols` map, or a map the caller moves into it once every column of a call has succeeded.
+int check_new_column(Table *t, uint32_t field_id, uint32_t n_chunks);
+int alloc_column(Table &t, uint32_t width, DeviceBuffer &out, bool rows_overwritten = false);
+int register_column(Table &t, std::map<uint32_t, DeviceColumn> &into, uint32_t field_id, DeviceColumn &&c);
+inline bool has_join_columns(const Table &t) {
+  for (const auto &kv : t.cols) if (kv.second.join_column) return true;
+  return false;
+}
 uint32_t octant_of_chunk(const Table &t, uint32_t global_chunk);
 void build_tiles_host(const Table &t, uint32_t tile_rows, std::vector<TileDesc> &tiles,
                       uint32_t (&octant_tile_begin)[kOctantsHost + 1]);

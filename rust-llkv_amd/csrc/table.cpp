@@ -214,7 +214,7 @@ uint64_t table_chunk_rows(const llkv_hip_table *table, uint32_t global_chunk) {
 // `rows_overwritten`: every row of the image is about to be staged over (value buffers of a table without padding rows
 // between its chunks): only the slack behind the image is zeroed — the runtime's fill moves ~130 GB/s, which made zeroing
 // SF10's five 480 MB columns a fifth of their staging time
-static int alloc_column(Table &t, uint32_t width, DeviceBuffer &out, bool rows_overwritten = false) {
+int alloc_column(Table &t, uint32_t width, DeviceBuffer &out, bool rows_overwritten) {
   const uint64_t rows = t.dev_rows + kSlackRows;
   HIP_TRY(out.alloc(rows, width));
   if (rows_overwritten && t.dev_rows == t.local_rows) HIP_TRY(hipMemsetAsync(out.get<char>() + t.dev_rows * width, 0, kSlackRows * width, g_ctx.stream));
@@ -325,6 +325,21 @@ static int column_stats_device(Table &t, DeviceColumn &c) {
     c.info.max_i = mm[1];
     c.info.ascending = ts != nullptr && mm[2] == 0;
   }
+  return LLKV_OK;
+}
+
+int check_new_column(Table *t, uint32_t field_id, uint32_t n_chunks) {
+  if (!t) return set_error(LLKV_INVALID_ARGUMENT, "table is NULL");
+  if (t->cols.count(field_id)) return set_error(LLKV_INVALID_ARGUMENT, "field " + std::to_string(field_id) + " already staged");
+  if (n_chunks != t->n_local_chunks)
+    return set_error(LLKV_INVALID_ARGUMENT, "expected " + std::to_string(t->n_local_chunks) + " local chunks, got " + std::to_string(n_chunks));
+  return LLKV_OK;
+}
+
+int register_column(Table &t, std::map<uint32_t, DeviceColumn> &into, uint32_t field_id, DeviceColumn &&c) {
+  if (c.info.dtype != LLKV_DT_UTF8 && !c.info.wide128)
+    if (const int rc = column_stats_device(t, c)) return rc;
+  into.emplace(field_id, std::move(c));
   return LLKV_OK;
 }
 
@@ -644,14 +659,6 @@ llkv_status llkv_hip_table_local_chunks(const llkv_hip_table *table, uint32_t *f
 }
 uint64_t llkv_hip_table_total_rows(const llkv_hip_table *table) { return table ? reinterpret_cast<const Table *>(table)->total_rows : 0; }
 uint64_t llkv_hip_table_local_rows(const llkv_hip_table *table) { return table ? reinterpret_cast<const Table *>(table)->local_rows : 0; }
-
-static int check_new_column(Table *t, uint32_t field_id, uint32_t n_chunks) {
-  if (!t) return set_error(LLKV_INVALID_ARGUMENT, "table is NULL");
-  if (t->cols.count(field_id)) return set_error(LLKV_INVALID_ARGUMENT, "field " + std::to_string(field_id) + " already staged");
-  if (n_chunks != t->n_local_chunks)
-    return set_error(LLKV_INVALID_ARGUMENT, "expected " + std::to_string(t->n_local_chunks) + " local chunks, got " + std::to_string(n_chunks));
-  return LLKV_OK;
-}
 
 llkv_status llkv_hip_table_set_row_ids(llkv_hip_table *table, const uint64_t *const *chunk_row_ids, uint32_t n_chunks) {
   Table *t = reinterpret_cast<Table *>(table);
@@ -1015,6 +1022,8 @@ static int append_chunks_impl(Table *t, const uint64_t *chunk_rows, uint32_t n_n
                               const uint64_t *const *chunk_row_ids) {
   if (!t || (n_new && !chunk_rows) || (n_columns && !columns)) return set_error(LLKV_INVALID_ARGUMENT, "NULL argument");
   if (t->world != 1) return set_error(LLKV_UNSUPPORTED, "append to a sharded table (the canonical octants move with the chunk count): re-stage the shards");
+  // (a join column has no rows to append: its cells come from a dimension image, llkv_hip_table_add_join_columns)
+  if (has_join_columns(*t)) return set_error(LLKV_UNSUPPORTED, "append to a table that holds join columns: drop the join columns first (llkv_hip_table_drop_join_columns), append, add them again");
   if (n_new == 0) return LLKV_OK;
   int rc = ensure_device();
   if (rc) return rc;
@@ -1230,9 +1239,7 @@ llkv_status llkv_hip_table_adopt_device_column(llkv_hip_table *table, uint32_t f
   if (hipMemcpyAsync(c.d_values.get(), device_values, t->dev_rows * w, hipMemcpyDeviceToDevice, g_ctx.stream) != hipSuccess ||
       hipStreamSynchronize(g_ctx.stream) != hipSuccess)
     return (llkv_status)set_error(LLKV_INTERNAL, "device copy failed");
-  if ((rc = column_stats_device(*t, c))) return (llkv_status)rc;
-  t->cols.emplace(field_id, std::move(c));
-  return LLKV_OK;
+  return (llkv_status)register_column(*t, t->cols, field_id, std::move(c));
 }
 
 } // extern "C"

@@ -538,6 +538,37 @@ class HipTable:
     def adopt_device_column(self, field_id: int, dtype: int, device_ptr: int):
         check(lib().llkv_hip_table_adopt_device_column(self._h, C.c_uint32(field_id), C.c_int32(dtype), C.c_void_p(device_ptr)))
 
+    def add_join_columns(self, fact_key: int, dim: "HipTable", dim_key: int, columns: Dict[int, int], dim_filters=None) -> int:
+        """llkv_hip_table_add_join_columns: ``columns`` maps a field of ``dim`` to the new field id here; every row of this table gets
+        the cell of the dimension row (among those passing ``dim_filters``, a list of filters) whose ``dim_key`` equals the row's
+        ``fact_key`` — NULL without one.  Made in HBM; from then on a column like any other.  Returns the rows that found a dimension row."""
+        plan = CPlan(list(dim_filters or []))
+        side = abi.CJoinSide()
+        side.table, side.filters, side.n_filters, side.key_field = dim.handle, plan.filters, plan.n_filters, dim_key
+        pairs = list(columns.items()) if isinstance(columns, dict) else list(columns)
+        cols = (abi.CTableJoinColumn * max(1, len(pairs)))()
+        for i, (dim_field, out_field) in enumerate(pairs):
+            cols[i].dim_field, cols[i].out_field = dim_field, out_field
+        matched = C.c_uint64()
+        f = lib().llkv_hip_table_add_join_columns
+        f.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(abi.CJoinSide), C.POINTER(abi.CTableJoinColumn), C.c_uint32, C.POINTER(C.c_uint64)]
+        check(f(self._h, fact_key, C.byref(side), cols, len(pairs), C.byref(matched)))
+        return int(matched.value)
+
+    def drop_join_columns(self):
+        """llkv_hip_table_drop_join_columns: frees every join column; queries prepared before the call must be prepared again."""
+        f = lib().llkv_hip_table_drop_join_columns
+        f.argtypes = [C.c_void_p]
+        check(f(self._h))
+
+    def join_column_source(self, out_field: int):
+        """(dimension table id, dimension generation, dimension field) a join column was looked up from."""
+        tid, gen, fld = C.c_uint16(), C.c_uint64(), C.c_uint32()
+        f = lib().llkv_hip_table_join_column_source
+        f.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        check(f(self._h, out_field, C.byref(tid), C.byref(gen), C.byref(fld)))
+        return int(tid.value), int(gen.value), int(fld.value)
+
     def close(self):
         if self._h:
             lib().llkv_hip_table_free(self._h)
