@@ -210,9 +210,11 @@ __global__ __launch_bounds__(256) void value_set_kernel(const unsigned long long
     for (uint32_t b = 0; b < kValueBatch; ++b, row += stride) {
       if (row >= n) continue;
       const unsigned long long v = values[row];
+      // (before the comparison with `last`, which starts as this very pattern: a thread whose rows begin with all-ones must not skip them —
+      // below kValueSetGrid · 256 rows a thread reads one row only, and the pattern was never found: its rows decoded to the table's padding)
+      if (v == kValueFree) { has_free_pattern = 1; continue; }
       if (v == last) continue;
       last = v;
-      if (v == kValueFree) { has_free_pattern = 1; continue; }
       uint32_t h = (uint32_t)mix64(v) & (kValueSetSlots - 1);
       for (uint32_t probe = 0; probe < kValueSetSlots; ++probe, h = (h + 1) & (kValueSetSlots - 1)) {
         unsigned long long seen = keys[h];

@@ -16,6 +16,8 @@ import struct
 import numpy as np
 import pytest
 
+import cond_expr_model as M
+
 pytestmark = pytest.mark.gpu
 
 FCH, DCH = [30000, 1, 40001], [3000, 7, 1993]
@@ -331,6 +333,77 @@ def test_group_by_a_join_column_on_every_route(w, case, monkeypatch):
                 assert g[j] is not None and abs(struct.unpack("<d", g[j][1])[0] - v.value) <= 1e-9 * abs(v.value), (case, j)
             else:
                 assert g[j] == cell_bits(v), (case, j, g[j], v)
+
+
+def conditional_aggs(abi, bounded):
+    """COALESCE / CASE … IS NULL / a Date32 compare / CAST over join columns, where an unmatched fact row is a NULL cell.  `bounded`: the
+    first argument modulo 2^20 — D_I64N spans the whole of i64, so its plain sum leaves i64 in every large group.  The PlanValue
+    interpreter takes a remainder of Integers in f64 (`as f64`, fmod, back to i64) and a comparison with a Date32 side is never TRUE
+    (tests/cond_expr_model.py: arith, compare): the third aggregate adds up its ELSE branch, 0.0."""
+    S, A, col, L = abi.ScalarExpr, abi.AggregateSpec, abi.col, abi.Literal
+    i64n = col(J(D_I64N)) % (1 << 20) if bounded else col(J(D_I64N))
+    return [A.sum(S.coalesce(i64n, 0)),
+            A.count(S.case([(S.is_null(col(J(DK))), 1)])),                                         # the unmatched and NULL-key fact rows
+            A.sum(S.case([(S.compare(col(J(D_DATE)), abi.CMP_LT, L.date32(10000)), col(V))], 0.0)),
+            A.avg(S.cast(col(J(D_I32)), abi.DT_FLOAT64))]
+
+
+@pytest.mark.parametrize("case", list(GROUPS))
+def test_conditional_arguments_over_join_columns(w, case, monkeypatch):
+    """SUM(COALESCE(joined, 0)), COUNT(CASE WHEN joined IS NULL THEN 1 END), SUM(CASE WHEN joined date < … THEN v ELSE 0.0 END) and
+    AVG(CAST(joined AS DOUBLE)) per route: the join columns and the host-staged cells answer alike (rows, route note, kernel signature),
+    and both equal numpy over the looked-up cells — exactly: the addends are quarters below 2^20 and integers below 2^31."""
+    abi, rt = w.abi, w.rt
+    key, env, note = GROUPS[case]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    kc, i64n, dk, date, i32 = (w.want[f] for f in (key, D_I64N, DK, D_DATE, D_I32))
+    gkey = [k if ok else None for k, ok in zip(kc.values if isinstance(kc.values, list) else kc.values.tolist(), kc.valid.tolist())]
+    groups = {}
+    for r, g in enumerate(gkey):
+        groups.setdefault(g, []).append(r)
+    groups = {g: np.array(rows) for g, rows in groups.items()}
+    assert None in groups and len(groups) > 2
+    # the sum as the issue of these tests states it: Python integers decide whether a group's total (or a prefix of it) can leave i64
+    plain = np.where(i64n.valid, i64n.values, 0)
+    leaves = any(not I64.min <= sum(int(v) for v in plain[rows]) <= I64.max or int(np.abs(plain[rows].astype(object)).max()) * len(rows) > I64.max for rows in groups.values())
+    assert leaves  # (D_I64N spans i64: true on every route — so the values are compared on the bounded form below)
+    errors = []
+    for t in (w.fact, w.ref):
+        pq = rt.PreparedQuery(t, None, conditional_aggs(abi, False), [J(key)])
+        assert pq.route_note.startswith(note), (case, pq.route_note)
+        with pytest.raises(abi.LlkvError) as err:
+            pq.run()
+        errors.append((err.value.status, err.value.message, pq.route_note, pq.kernel_signature))
+        pq.close()
+    assert errors[0] == errors[1] and "overflow" in errors[0][1], (case, errors)
+    aggs = conditional_aggs(abi, True)
+    answers = []
+    for t in (w.fact, w.ref):
+        pq = rt.PreparedQuery(t, None, aggs, [J(key)])
+        rows = pq.run()
+        assert pq.route_note.startswith(note), (case, pq.route_note)
+        answers.append((group_rows(rows), pq.route_note, pq.kernel_signature))
+        pq.close()
+    assert answers[0] == answers[1], case  # the same plan, the same route, the same bits
+    got = {(None if k[0] is None else k[0][1]): cells for k, cells in answers[0][0].items()}
+    bounded = np.where(i64n.valid, np.fmod(i64n.values.astype(np.float64), float(1 << 20)).astype(np.int64), 0)  # `as f64`, fmod (the dividend's sign), back
+    unmatched = ~dk.valid
+    before = np.zeros(NF)  # a Date32 comparison is not TRUE: the ELSE branch
+    # the two numpy columns above are the model's, row by row, on a sample of the fact rows
+    for r in np.random.default_rng(5).integers(0, NF, 300).tolist() + [int(np.flatnonzero(date.valid & (date.values < 10000))[0])]:
+        row = {J(D_I64N): (M.INT, int(i64n.values[r]) if i64n.valid[r] else None), J(D_DATE): (M.DATE, int(date.values[r]) if date.valid[r] else None),
+               V: (M.FLOAT, float(w.v[r]))}
+        assert M.evaluate(aggs[0].expr, row) == int(bounded[r]) and M.evaluate(aggs[2].expr, row) == float(before[r]), r
+    f64 = lambda v: (abi.DT_FLOAT64, struct.pack("<d", v))
+    want = {}
+    for g, rows in groups.items():
+        n32 = int(i32.valid[rows].sum())
+        want[g] = [(abi.DT_INT64, int(bounded[rows].sum())), (abi.DT_INT64, int(unmatched[rows].sum())), f64(float(before[rows].sum())),
+                   f64(float(i32.values[rows][i32.valid[rows]].astype(np.int64).sum()) / n32) if n32 else None]
+    assert got == want, case
+    assert sum(cells[1][1] for cells in got.values()) == NF - w.n_matched  # every fact row without a dimension row, counted once
+    assert any(cells[0][1] != 0 for cells in got.values())
 
 
 def test_filters_on_join_columns(w):

@@ -137,6 +137,29 @@ def test_integer_extremes_decimals_and_null_cells(rt, abi, monkeypatch):
 
 
 @gpu
+@pytest.mark.parametrize("rows", [N, 150_000])
+def test_the_all_ones_pattern_is_a_code_of_its_own(rt, abi, monkeypatch, rows):
+    """Int64 −1 and the NaN of all-ones bits are the pattern that marks a free slot of the pattern discovery (catalog.hip:
+    value_set_kernel), which tracks it by a flag.  Below 131 072 rows a thread of that kernel reads one row; above, the column here
+    BEGINS with its −1 cells and holds none further on, so every thread that meets the pattern meets it first.  SUM reads the decoded
+    values: a −1 that decodes to the table's padding is a 0."""
+    rng = np.random.default_rng(rows)
+    chunks = CHUNKS if rows == N else [65536, rows - 65536]
+    v = rng.integers(0, 7, size=rows).astype(np.int64) - 3
+    v[v == -1] = 2
+    v[:3000] = -1
+    f = rng.integers(0, 5, size=rows).astype(np.float64)
+    f[:3000:2] = np.array([0xFFFFFFFFFFFFFFFF], dtype=np.uint64).view(np.float64)[0]
+    key = (np.arange(rows) % 4).astype(np.int64)
+    t = table_of(rt, abi, {1: (abi.DT_INT64, key), 2: (abi.DT_INT64, v), 3: (abi.DT_FLOAT64, f)}, chunks=chunks)
+    A = abi.AggregateSpec
+    got, sig = both(rt, monkeypatch, t, None, [A.sum(2), A.min(2), A.count_star(), A.min(3)], keys=[1], ordered=True)
+    assert sig.count("D8<I64,16>") == 2 and "D8<F64,16>" in sig
+    assert [r[1][:3] for r in got] == [(int(v[key == g].sum()), -3, int((key == g).sum())) for g in range(4)]
+    assert sum(r[1][0] for r in got) == int(v.sum()) and (v == -1).sum() == 3000
+
+
+@gpu
 def test_register_state_eager_and_late_forms(rt, abi, monkeypatch):
     """Ungrouped plans: the predicate on a coded column and the argument on a coded column, with every column up front (no predicate /
     LLKV_HIP_SCAN_NO_LATE) and in the late form (argument columns read for the passing rows)."""
