@@ -1405,6 +1405,67 @@ llkv_status llkv_hip_table_join_column_source(const llkv_hip_table *fact, uint32
                                               uint64_t *dim_generation, uint32_t *dim_field);
 
 /* ------------------------------------------------------------------------- */
+/* Aggregate columns: correlated subquery aggregates looked up in HBM.         */
+/* A join column needs a UNIQUE dimension key.  An aggregate column is the      */
+/* other half — the correlated scalar subquery over a NON-unique key:           */
+/*   outer.out_field[r] = SELECT agg(inner_field) FROM inner WHERE <inner->filters> AND inner.key_field = outer.outer_key_field[r] */
+/* (TPC-H Q17: avg(l_quantity) per l_partkey; Q4 / Q21 / Q22: EXISTS / NOT EXISTS as COUNT(*) > 0 / = 0; Q2: min(ps_supplycost);   */
+/* the inner half of Q18: sum(l_quantity) per order).  The reference runs the bound subquery once per distinct binding           */
+/* (evaluate_scalar_subquery_with_bindings llkv-executor/src/lib.rs:788-834, the per-batch cache :836-961); here one call makes   */
+/* the column in HBM (aggregate_column.hip) and every existing call serves the rest: EXISTS is a filter on the count column, the  */
+/* Q17 predicate an expression compare over two columns of one table.                                                            */
+/* Cell rule.  The cell is the single cell of the ungrouped aggregate (llkv_hip_aggregate) of the same kind over the qualifying   */
+/* inner rows with that key — the same type and the same bits.  The empty set: a NULL outer key (key = NULL matches nothing), a  */
+/* key outside the inner key's range, a key without a qualifying inner row; a NULL inner key matches nothing.  Over the empty     */
+/* set COUNT and COUNT(*) are 0, TOTAL is 0.0, SUM / AVG / MIN / MAX are NULL — except SUM over a Decimal128 column, which the    */
+/* reference's accumulator finalises as 0, never NULL (llkv-aggregate: `vec![sum]`), as the ungrouped aggregate here does.        */
+/* Arguments.  The bare column only: Int64; Float64; Decimal128 staged in 64 bits for COUNT / SUM / MIN / MAX; COUNT(x) over any  */
+/* staged column (only its validity is read); COUNT(*) without one (inner_field ignored).  Keys follow the join columns' rule:    */
+/* Int64 / Int32 / Date32 / UInt32 on either side, compared by value.                                                            */
+/* Output types (the ungrouped aggregate's).  COUNT / COUNT(*): Int64, never nullable.  SUM(Int64): Int64.  SUM(Decimal128): the  */
+/* argument's (precision, scale), 64-bit image, never nullable.  AVG and TOTAL: Float64 (TOTAL never nullable).  MIN / MAX: the   */
+/* argument's type (and precision, scale).                                                                                       */
+/* Float64 SUM / AVG, and TOTAL (over Float64 or Int64, which it adds as (double)v): every key's sum is the left-to-right f64 sum */
+/* of its qualifying rows in ascending table order — the reference's accumulation order — made by a stable sort and one           */
+/* sequential chain per key: bit-equal to the ungrouped aggregate's oracle, the same on every call and launch geometry; no float  */
+/* atomics.  A NaN sum of a column without NaN cells is the default NaN, as in the ungrouped aggregate.  Everything else is       */
+/* order-free and exact: counts, integer and decimal sums (one wrapping 64-bit lane, admitted only when the statistics exclude    */
+/* overflow), MIN / MAX.                                                                                                         */
+/* Refusals — `outer` is unchanged by every one of them, and all are answered before a device is needed.  LLKV_UNSUPPORTED, the   */
+/* message naming the cause: the inner key has no statistics-bounded range; the range spans 2^28 keys or more; the per-key state  */
+/* (span + 1) x 8 B x lanes (the accumulator lanes plus one cell per column) would pass 1 GiB; a sharded table on either side; a  */
+/* wide (128-bit) Decimal128 argument of anything but COUNT; AVG or TOTAL over Decimal128; SUM / AVG / TOTAL / MIN / MAX over any */
+/* other dtype (Date32, Utf8, Boolean, Int32, ...); an integer or decimal SUM (or integer AVG) whose rows x max|v| may pass i64    */
+/* ("possible i64 overflow": the reference's checked_add chain is order dependent) or whose column has no statistics; Float64     */
+/* MIN / MAX without all_finite statistics that also exclude -0.0 (the reference's fold is order dependent there); COUNT_NULLS.   */
+/* LLKV_INVALID_ARGUMENT and LLKV_NOT_FOUND: the join columns' cases — NULL arguments, n_cols 0 or above 8, an out_field listed   */
+/* twice or already staged, a missing key or inner field.  An inner table without rows has no cell to bound: its key range,      */
+/* statistics and overflow are not asked about (every cell is then the empty set's), whatever statistics were installed on it.    */
+/* Lifetime.  An aggregate column IS a join column for every lifetime rule: a snapshot of the inner table;                        */
+/* llkv_hip_table_join_column_source reports (inner table id, generation, inner_field — the inner key field for COUNT(*));        */
+/* llkv_hip_table_append_chunks on `outer` refuses while it is there; llkv_hip_table_drop_join_columns frees it with the others   */
+/* and starts a new generation.  outer == inner->table is allowed (Q17: lineitem's own avg(l_quantity) per l_partkey).            */
+/* Registration.  As a join column: from then on every call reads it as a column staged from the host with the same cells — NULL  */
+/* cells hold zero values, the validity mask is kept exactly when some cell is NULL, padding rows follow the staging convention,  */
+/* statistics come from the staging path's device pass.  Device memory during the call: the per-key state above, for an f64 sum   */
+/* 16 B per qualifying inner row plus the sort's temporary storage, and 9 B per outer row and column.                             */
+/* Not here (the binding's affair, or a later call): computed arguments; composite or non-integer correlation keys; a hash        */
+/* fallback for unbounded key ranges; sharded tables; decimal AVG / TOTAL; DISTINCT aggregates; subqueries with their own GROUP BY, */
+/* HAVING or LIMIT; the reference's data-dependent coercion of a decimal subquery result in a numeric context (lib.rs:934-961) —  */
+/* the column holds the subquery's own cell, the consumer's cast is the binding's.                                               */
+/* ------------------------------------------------------------------------- */
+typedef struct llkv_table_aggregate_column {
+  int32_t  kind;        /* llkv_aggregate_kind: COUNT_STAR, COUNT, SUM, TOTAL, AVG, MIN, MAX */
+  uint32_t inner_field; /* argument column of the inner table (ignored for COUNT_STAR)       */
+  uint32_t out_field;   /* new field id in outer                                             */
+} llkv_table_aggregate_column;
+
+llkv_status llkv_hip_table_add_aggregate_columns(llkv_hip_table *outer, uint32_t outer_key_field,
+                                                 const llkv_join_side *inner /* table, filters (conjunction), key_field */,
+                                                 const llkv_table_aggregate_column *cols, uint32_t n_cols /* 1..8 */,
+                                                 uint64_t *matched_rows /* may be NULL: outer rows whose key has >= 1 qualifying inner row */);
+
+/* ------------------------------------------------------------------------- */
 /* Multi-GPU combine, host pieces (no device needed).  The chunk list is cut    */
 /* into 8 canonical octants (boundaries floor(j·C/8)); rank r of `world` owns   */
 /* octants [r·8/world, (r+1)·8/world).  Partial aggregate state is exchanged    */

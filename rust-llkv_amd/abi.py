@@ -448,6 +448,10 @@ class CTableJoinColumn(C.Structure):  # llkv_table_join_column
     _fields_ = [("dim_field", C.c_uint32), ("out_field", C.c_uint32)]
 
 
+class CTableAggregateColumn(C.Structure):  # llkv_table_aggregate_column
+    _fields_ = [("kind", C.c_int32), ("inner_field", C.c_uint32), ("out_field", C.c_uint32)]
+
+
 class CJoinGroupRow(C.Structure):
     _fields_ = [("key", C.c_int64), ("sum", C.c_double), ("count", C.c_uint64), ("payload", C.c_int64 * 4),
                 ("group_index", C.c_uint64)]

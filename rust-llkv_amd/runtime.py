@@ -555,6 +555,25 @@ class HipTable:
         check(f(self._h, fact_key, C.byref(side), cols, len(pairs), C.byref(matched)))
         return int(matched.value)
 
+    def add_aggregate_columns(self, outer_key: int, inner: "HipTable", inner_key: int, cols, filters=()) -> int:
+        """llkv_hip_table_add_aggregate_columns: ``cols`` lists (aggregate kind, field of ``inner`` or None for COUNT(*), new field id
+        here); every row of this table gets the cell of the ungrouped aggregate over the rows of ``inner`` that pass ``filters`` and
+        whose ``inner_key`` equals the row's ``outer_key`` — the correlated scalar subquery, the empty set included (COUNT 0, TOTAL 0.0,
+        SUM / AVG / MIN / MAX NULL).  Made in HBM; a join column for every lifetime rule.  Returns the rows whose key has a qualifying
+        inner row."""
+        plan = CPlan(list(filters or []))
+        side = abi.CJoinSide()
+        side.table, side.filters, side.n_filters, side.key_field = inner.handle, plan.filters, plan.n_filters, inner_key
+        specs = list(cols)
+        arr = (abi.CTableAggregateColumn * max(1, len(specs)))()
+        for i, (kind, inner_field, out_field) in enumerate(specs):
+            arr[i].kind, arr[i].inner_field, arr[i].out_field = kind, 0 if inner_field is None else inner_field, out_field
+        matched = C.c_uint64()
+        f = lib().llkv_hip_table_add_aggregate_columns
+        f.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(abi.CJoinSide), C.POINTER(abi.CTableAggregateColumn), C.c_uint32, C.POINTER(C.c_uint64)]
+        check(f(self._h, outer_key, C.byref(side), arr, len(specs), C.byref(matched)))
+        return int(matched.value)
+
     def drop_join_columns(self):
         """llkv_hip_table_drop_join_columns: frees every join column; queries prepared before the call must be prepared again."""
         f = lib().llkv_hip_table_drop_join_columns
